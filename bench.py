@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fastmax attention forward (p=1, masked) at N=4096, d=64 on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +13,12 @@ bracket the timed region ("scaling": "weak" -- per-GPU work is fixed).  Rank 0 p
 roofline.achieved = algorithmic bytes per launch / mean launch duration, where algorithmic bytes =
 4*B*H*N*D*sizeof(dtype) (read Q,K,V once, write O once) and the duration is measured
 with HIP events on the stream the kernel is launched on (torch's current stream).
-cpu_baseline (rank 0, N=1 only) times the CPU oracle on a bounded sample of the same workload.
+
+A plain run measures the headline only.  --full adds what takes runs of its own: the from-idle pass ("cold_start") and
+cpu_baseline (rank 0, N=1 only), which times the CPU oracle on a bounded sample of the same workload.
+--dump-outputs DIR writes what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float32 or float64:
+o (and dq, dk, dv with --mode fwd+bwd), or loss for --workload dp_step.  An array larger than its share of 60 MB is
+written as a fixed, seeded sample of its flattened elements (the same indices for the same arguments).
 """
 import argparse
 import json
@@ -60,7 +65,34 @@ def parse():
                          "\"headline\": false.  Without it bench.py refuses such a run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the from-idle pass (cold_start) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32/float64, at most 60 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 60_000_000      # --dump-outputs: total size of the .npy payloads
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: {name: tensor}.  Each goes to out_dir/<name>.npy as float32 (float64 stays float64); one larger than its share
+    of DUMP_BYTES is replaced by the elements at a fixed, seeded, sorted set of flat indices (the same for the same shape)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=share // t.element_size()))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def cpu_baseline(args, seconds):
@@ -149,6 +181,9 @@ def dp_step_main(args, dev, rank, world, multi, json_fd):
             "trainable_params": res["trainable_params"], "last_loss": round(res["last_loss"], 5),
             "precondition_ms": 0.0 if args.toy else args.precondition_ms, "hip_graph": bool(args.graph and not args.toy),
         }
+        if args.dump_outputs:
+            import torch
+            dump_outputs(args.dump_outputs, {"loss": torch.tensor([res["last_loss"]], dtype=torch.float64)})
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if multi:
         dist.destroy_process_group()
@@ -250,6 +285,7 @@ def main():
 
     path = _lib.PATH_NAMES.get(ops.selected_path(q, k, args.p, True), "?")
     launches = {"n": 0}                                   # steps issued so far (each is one launch of the dominant kernel)
+    last = {}                                             # the last timed step's output, for --dump-outputs
 
     def protocol():
         """W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize pairs.
@@ -266,7 +302,12 @@ def main():
         t0 = time.perf_counter()
         ev[0].record()
         for i in range(args.steps):
-            step()
+            # only the last step's output is kept (for --dump-outputs): holding one across steps would make the next step
+            # allocate a second output buffer inside the timed region
+            if i + 1 < args.steps:
+                step()
+            else:
+                last["o"] = step()
             ev[i + 1].record()
         torch.cuda.synchronize(dev)
         if multi:
@@ -283,13 +324,15 @@ def main():
 
     # From an idle device the chip runs the first launches at boost clock, then its power controller pulls the clock down and
     # lets it recover over ~30 ms (profiles/r02_transient.md: the same memory traffic without the matrix instructions shows
-    # no such dip).  With W = 5, K = 20 the whole timed region sits inside that start-up transient, so it is measured and
-    # reported on its own ("cold_start"), and the headline numbers are the SAME protocol run after --precondition-ms of
+    # no such dip).  With W = 5, K = 20 the whole timed region sits inside that start-up transient, so --full measures it and
+    # reports it on its own ("cold_start"), and the headline numbers are the SAME protocol run after --precondition-ms of
     # back-to-back steps, i.e. at the clock the chip sustains -- what a training job sees.  --precondition-ms 0 makes the
     # headline the from-idle measurement.
     cold = None
     if args.precondition_ms > 0:
-        cold = protocol()
+        if args.full:
+            cold = protocol()
+            last.clear()
         t_end = time.perf_counter() + args.precondition_ms * 1e-3
         while time.perf_counter() < t_end:
             for _ in range(16):
@@ -297,6 +340,12 @@ def main():
             launches["n"] += 16
             torch.cuda.synchronize(dev)
     elapsed, kernel_ms, per_launch = protocol()
+
+    if rank == 0 and args.dump_outputs:
+        if train:
+            last.update(dq=q.grad, dk=k.grad, dv=v.grad)
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
 
     if rank == 0:
         es = {"f32": 4, "bf16": 2, "f16": 2}[args.dtype]
@@ -321,7 +370,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.dtype, "data": "synthetic",
             # every launch of the step before the first timed one: the W warm-up steps of the timed pass and, ahead of them, the
-            # from-idle pass ("cold_start": W + K launches) and the --precondition-ms of back-to-back steps
+            # from-idle pass ("cold_start": W + K launches, --full only) and the --precondition-ms of back-to-back steps
             "effective_warmup_launches": launches["before_timed"],
             "headline": bool(default_kernel),
             "config": {"workload": f"{args.op} p={args.p} masked {args.mode}, (B,H,N,D)=({B},{H},{N},{D}) per GPU, "
@@ -347,7 +396,7 @@ def main():
                 "kernel_ms": round(c_ms, 4), "per_launch_ms": {"min": round(min(c_per), 4), "max": round(max(c_per), 4)},
                 "achieved": round(alg_bytes / (c_ms * 1e-3) / 1e9, 1),
                 "frac": round(alg_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if multi:

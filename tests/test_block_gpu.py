@@ -341,6 +341,28 @@ def test_bench_dp_step_on_device():
     assert two["last_loss"] == two["last_loss"] and two["allreduce"]["bucket_bytes"] == 4 * two["trainable_params"]
 
 
+def test_bench_headline_dump_outputs_and_full(tmp_path):
+    """the headline workload at a small size: `--dump-outputs` writes the last timed step's O (and dQ, dK, dV when training)
+    computed from the bench's seeded inputs; the from-idle pass and the CPU baseline appear with --full only"""
+    from attention_mechanisms.fastmax import fastmax
+    from test_dp_gloo import _run_bench
+    B, H, N, D = 1, 2, 256, 64
+    common = ["--batch", str(B), "--heads", str(H), "--seq", str(N), "--dim", str(D), "--steps", "3", "--warmup", "1",
+              "--precondition-ms", "5"]
+    plain = _run_bench(common + ["--mode", "fwd+bwd", "--dump-outputs", str(tmp_path)], 1)
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and "cold_start" not in plain and "cpu_baseline" not in plain
+    gen = torch.Generator(device="cuda:0").manual_seed(0)                  # bench.py's inputs: seed = rank
+    q, k, v, go = (torch.randn(B, H, N, D, device="cuda:0", generator=gen).requires_grad_(True) for _ in range(4))
+    o = fastmax(q, k, v, mask=True, p=1)
+    o.backward(go.detach())
+    for name, want in (("o", o), ("dq", q.grad), ("dk", k.grad), ("dv", v.grad)):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (B, H, N, D), name
+        assert rel_err(got, want.detach().cpu().numpy()) < 1e-5, name
+    full = _run_bench(common + ["--full", "--cpu-seconds", "0.2"], 1)
+    assert full["cold_start"]["ms_per_step"] > 0 and full["cpu_baseline"]["value"] > 0
+
+
 @pytest.mark.parametrize("alg", ["fastmax", "linearmax"])
 @pytest.mark.parametrize("train", [True, False])
 def test_group_views_match_the_expanded_copies_bit_for_bit(alg, train):

@@ -160,6 +160,32 @@ def test_bench_dp_step_mode_two_ranks_over_gloo():
     assert two["value"] > 0 and two["ms_per_step"] > 0 and two["last_loss"] == two["last_loss"]
 
 
+def test_bench_dump_outputs_dp_step(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned -- for dp_step the loss -- as float64 .npy"""
+    import numpy as np
+    line = _run_bench(["--workload", "dp_step", "--toy", "--steps", "2", "--warmup", "1", "--seq", "16",
+                       "--dump-outputs", str(tmp_path)], 1)
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float64 and loss.shape == (1,) and round(float(loss[0]), 5) == line["last_loss"]
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """an output larger than its share of the dump budget is written as the same seeded sample of its elements every time"""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8000)
+    arrays = {"big": torch.arange(10000, dtype=torch.float32).reshape(100, 100), "small": torch.randn(3, 5, dtype=torch.float64),
+              "half": torch.tensor([[1.5, -2.0]], dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and 0 < a.nbytes <= 8000 // 3 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.isin(a, arrays["big"].numpy()).all()       # sorted distinct elements of the array
+    s, h = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "half.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, arrays["small"].numpy())
+    assert h.dtype == np.float32 and np.array_equal(h, [[1.5, -2.0]])
+
+
 def test_bench_gpus_without_a_launcher_spawns_its_ranks_or_fails():
     """`python bench.py --gpus N` started WITHOUT torch.distributed.run (no WORLD_SIZE) must not quietly run one rank and report
     n_gpus 1: it starts the N ranks itself (before touching a GPU) and passes their one JSON line through; a WORLD_SIZE that

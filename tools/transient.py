@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Per-launch durations of the headline forward from an IDLE device (what `bench.py --steps 20 --warmup 5` sees): the chip
-starts at boost clocks, the power controller then pulls them down and settles, so the first ~25 launches are a transient.
+"""Per-launch durations of the headline forward from an IDLE device (what the `cold_start` pass of `bench.py --full --steps 20
+--warmup 5` sees): the chip starts at boost clocks, the power controller then pulls them down and settles, so the first ~25
+launches are a transient.
 usage: python tools/transient.py VAR=val1,val2,... [--launches 40] [--idle 2.0] [--repeat 2] [--shape B,H,N,D]
 Prints one line of per-launch microseconds per (variant, repeat) and the mean over launches 6..25 (the bench's timed region)."""
 import os
