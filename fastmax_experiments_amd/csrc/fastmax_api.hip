@@ -55,13 +55,19 @@ bool aligned16(const void* ptr, const int64_t* s, int dtype) {
 }  // namespace
 
 namespace fastmax {
-// "mfma_variant" numbers whose kernels leave out matrix instructions or memory passes (timing-only, wrong results): they exist
-// in -DFASTMAX_ABLATIONS builds only
-static bool wrong_result_variant(int v) { return v == 119 || v == 129 || v == 219 || v == 201 || (v >= 204 && v <= 209); }
+// "mfma_variant": 200 is the headline kernel (fastmax_mfma_v2.hip) and the only number a production build takes.
+// -DFASTMAX_ABLATIONS builds also take its ablations 201 and 204..209, which leave out matrix instructions or memory passes
+// (timing-only, wrong results)
+static bool mfma_variant_ok(int v) {
+#ifdef FASTMAX_ABLATIONS
+    if (v == 201 || (v >= 204 && v <= 209)) return true;
+#endif
+    return v == 200;
+}
 namespace {
 struct TuneEntry { const char* name; const char* env; int value; };
 TuneEntry g_tune[TUNE_COUNT] = {
-    {"mfma_variant", "FASTMAX_MFMA_VARIANT", 200},    // headline forward kernel: 200 = second generation (fastmax_mfma_v2.hip)
+    {"mfma_variant", "FASTMAX_MFMA_VARIANT", 200},    // headline forward kernel: 200 = fastmax_mfma_v2.hip, see mfma_variant_ok
     {"bf16_kernel", "FASTMAX_BF16_KERNEL", 1},
     {"gemm_sched", "FASTMAX_GEMM_SCHED", 0},          // QLoRA GEMM: vector instructions per matrix instruction in the decode steps
     {"gemm_group_m", "FASTMAX_GEMM_GROUP_M", 16},     // QLoRA / head GEMM: row blocks per group of the workgroup -> tile map (0: column blocks fastest over the whole matrix)
@@ -75,9 +81,7 @@ void tune_load() {
         if (!e) continue;
         if (i == TUNE_BF16_KERNEL) g_tune[i].value = e[0] == 'g' ? 0 : 1;
         else g_tune[i].value = atoi(e);
-#ifndef FASTMAX_ABLATIONS
-        if (i == TUNE_MFMA_VARIANT && wrong_result_variant(g_tune[i].value)) g_tune[i].value = 200;   // not in this build
-#endif
+        if (i == TUNE_MFMA_VARIANT && !mfma_variant_ok(g_tune[i].value)) g_tune[i].value = 200;   // not in this build
     }
     g_tune_loaded = true;
 }
@@ -90,9 +94,7 @@ int tune_set(const char* name, int value) {
     tune_load();
     for (int i = 0; i < TUNE_COUNT; ++i)
         if (!strcmp(name, g_tune[i].name)) {
-#ifndef FASTMAX_ABLATIONS
-            if (i == TUNE_MFMA_VARIANT && wrong_result_variant(value)) return FASTMAX_E_BAD_SHAPE;
-#endif
+            if (i == TUNE_MFMA_VARIANT && !mfma_variant_ok(value)) return FASTMAX_E_BAD_SHAPE;
             g_tune[i].value = value;
             return FASTMAX_OK;
         }

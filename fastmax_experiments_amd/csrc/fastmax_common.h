@@ -114,16 +114,13 @@ struct BwdArgs {
 int launch_fwd_quadratic(const FwdArgs& a);
 int launch_fwd_recurrent_p1(const FwdArgs& a);
 int launch_fwd_mfma_p1(const FwdArgs& a);
-int launch_fwd_mfma_p1_v2(const FwdArgs& a, int ablation);
-bool mfma_p1_v2_supported(const FwdArgs& a);
+bool mfma_p1_supported(const fastmax_problem& p);
 // Run-time tuning knobs (A/B runs, ablations): read from the FASTMAX_* environment ONCE at first use, afterwards changed
 // only through fastmax_hip_tune(); launch paths read a plain int, never getenv.
 enum TuneKey { TUNE_MFMA_VARIANT = 0, TUNE_BF16_KERNEL = 1, TUNE_GEMM_SCHED = 2, TUNE_GEMM_GROUP_M = 3, TUNE_GEMM_XCD = 4, TUNE_COUNT };
 int tune_get(int key);
 int tune_set(const char* name, int value);
 int tune_get_by_name(const char* name);
-bool mfma_p1_supported(const fastmax_problem& p);
-size_t mfma_p1_workspace(const fastmax_problem& p);
 int launch_fwd_mfma_gen(const FwdArgs& a, const float* qscale, const float* kscale);
 int launch_fwd_mfma_bf16(const FwdArgs& a, const float* qscale, const float* kscale);
 bool mfma_bf16_supported(const fastmax_problem& p);

@@ -12,7 +12,7 @@
 //  * normalize       linearmax prologue (fastmax.py:326-334 / fastmax_hack.py:38-43).
 //
 // These are the correctness-first paths; the matrix-core kernel for the headline shape is
-// in fastmax_mfma.hip.
+// in fastmax_mfma_v2.hip.
 #include "fastmax_common.h"
 
 namespace fastmax {

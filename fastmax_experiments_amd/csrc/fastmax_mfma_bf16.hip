@@ -1,6 +1,6 @@
 // fastmax p=1 masked forward for bf16 tensors, linear in N -- every sum on the matrix cores.
 //
-// Same chunked scan as fastmax_mfma.hip / fastmax_mfma_gen.hip, specialised for exact single-part bf16 operands:
+// Same chunked scan as fastmax_mfma_v2.hip / fastmax_mfma_gen.hip, specialised for exact single-part bf16 operands:
 // the "ones" terms that the fp32 kernels keep on the vector ALU ride on spare MFMA tiles here
 //     S1   = sum_j v_j      = (1^T V)      one extra A fragment of ones against the V fragments of step (4)
 //     ksum = sum_j k_j      = (K^T 1)      the K^T fragments of step (4) against a ones B fragment
@@ -9,8 +9,6 @@
 // partial-sum arrays exist and the workgroup needs 45 KB of LDS at D <= 64: three workgroups per CU.
 // NORM fuses the linearmax prologue (fastmax_hack.py:38-43) into staging as in the generic kernel.
 #include "fastmax_mfma_common.h"
-
-#include <cstdlib>
 
 namespace fastmax {
 
@@ -26,16 +24,16 @@ struct Bf16Params {
     int nseg, cps;
 };
 
-// LEAN >= 1: the (a S2)^T state image is ONE rounded bf16 part instead of hi + lo: its rounding (2^-9 relative on entries
-// whose products with q are summed over D terms, in a term that is itself ~1/8 of the numerator) is far below the bf16
-// rounding of the result.  LEAN == 1 also carries P = 1 + a s as one part (the choice the tile kernels make for
-// bf16 -> bf16 problems); that one shows on the first rows of a sequence, where the in-chunk sum is the whole numerator.
-template <int DP, bool NORM, int LEAN>
+// The (a S2)^T state image is ONE rounded bf16 part instead of hi + lo: its rounding (2^-9 relative on entries whose
+// products with q are summed over D terms, in a term that is itself ~1/8 of the numerator) is far below the bf16 rounding
+// of the result (measured 1.578e-3 normwise against 1.572e-3 with a two-part image, which was 8 % slower).  P = 1 + a s
+// keeps two parts: as one part (12 % faster) its rounding shows on the first rows of a sequence, where the in-chunk sum is
+// the whole numerator -- 1.4x the error.
+template <int DP, bool NORM>
 __global__ __launch_bounds__(256, DP == 64 ? 2 : 1) void fwd_p1_mfma_bf16_kernel(Bf16Params prm) {
     using TIN = bf16_t;
     constexpr int EPL = 8, C = 64, IMG = C * DP * 2, SIMG = (DP + 16) * DP * 2;
-    constexpr int SP = LEAN ? 1 : 2, PP = LEAN == 1 ? 1 : 2;      // parts of the state image / of P
-    constexpr int QI = 0, KI = IMG, VI = 2 * IMG, S2I = 3 * IMG, S1V = S2I + SP * SIMG;
+    constexpr int QI = 0, KI = IMG, VI = 2 * IMG, S2I = 3 * IMG, S1V = S2I + SIMG;
     constexpr int COLS = DP / EPL, RPP = 256 / COLS, NPASS = C / RPP;
     constexpr int KS = DP / 32, DT = DP / 16, MT = DP / 16, NSL = DP / 64;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -81,30 +79,16 @@ __global__ __launch_bounds__(256, DP == 64 ? 2 : 1) void fwd_p1_mfma_bf16_kernel
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const int off = img_off<DP>(16 * (w + 4 * sl) + r, 2 * mt + (q4 >> 1)) + ((q4 & 1) << 3);
-                if constexpr (LEAN) {
-                    *reinterpret_cast<bf16x4*>(smem + S2I + off) = to_bf16x4(s2acc[sl][mt] * a);
-                } else {
-                    bf16x4 hi, lo;
-                    split4(s2acc[sl][mt] * a, hi, lo);
-                    *reinterpret_cast<bf16x4*>(smem + S2I + off) = hi;
-                    *reinterpret_cast<bf16x4*>(smem + S2I + SIMG + off) = lo;
-                }
+                *reinterpret_cast<bf16x4*>(smem + S2I + off) = to_bf16x4(s2acc[sl][mt] * a);
             }
             if (r == 0) {                                        // image row DP = a * ksum, columns m of tile w + 4sl
                 const int off = img_off<DP>(DP, 2 * (w + 4 * sl) + (q4 >> 1)) + ((q4 & 1) << 3);
-                if constexpr (LEAN) {
-                    *reinterpret_cast<bf16x4*>(smem + S2I + off) = to_bf16x4(ksacc[sl] * a);
-                } else {
-                    bf16x4 hi, lo;
-                    split4(ksacc[sl] * a, hi, lo);
-                    *reinterpret_cast<bf16x4*>(smem + S2I + off) = hi;
-                    *reinterpret_cast<bf16x4*>(smem + S2I + SIMG + off) = lo;
-                }
+                *reinterpret_cast<bf16x4*>(smem + S2I + off) = to_bf16x4(ksacc[sl] * a);
             }
             if (q4 == 0) reinterpret_cast<float*>(smem + S1V)[16 * (w + 4 * sl) + r] = s1acc[sl][0];
         }
     };
-    for (int i = tid; i < (SP * SIMG) / 16; i += 256) *reinterpret_cast<f32x4*>(smem + S2I + 16 * i) = f32x4{0, 0, 0, 0};
+    for (int i = tid; i < SIMG / 16; i += 256) *reinterpret_cast<f32x4*>(smem + S2I + 16 * i) = f32x4{0, 0, 0, 0};
     if (tid < DP) reinterpret_cast<float*>(smem + S1V)[tid] = 0.f;
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl) {
@@ -175,17 +159,14 @@ __global__ __launch_bounds__(256, DP == 64 ? 2 : 1) void fwd_p1_mfma_bf16_kernel
             f32x4 acc = {0, 0, 0, 0};
             if (dt < DT) acc = *reinterpret_cast<const f32x4*>(smem + S1V + (16 * dt + 4 * q4) * 4);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
+            for (int ks = 0; ks < KS; ++ks)
                 acc = mfma(*reinterpret_cast<const bf16x8*>(smem + S2I + img_off<DP>(16 * dt + r, 4 * ks + q4)), qf[ks], acc);
-                if constexpr (!LEAN)
-                    acc = mfma(*reinterpret_cast<const bf16x8*>(smem + S2I + SIMG + img_off<DP>(16 * dt + r, 4 * ks + q4)), qf[ks], acc);
-            }
             if (dt < DT) oacc[dt < DT ? dt : 0] = acc;
             else qkacc = acc;
         }
         const float qk = __shfl(qkacc[0], r, 64);                    // row 0 of the extra tile lives in lanes q4 == 0
         float gsum = 0.f;
-        Frag<PP> pf[2];
+        Frag<2> pf[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             f32x4 pt[2];
@@ -205,15 +186,11 @@ __global__ __launch_bounds__(256, DP == 64 ? 2 : 1) void fwd_p1_mfma_bf16_kernel
                     pt[e][i] = keep ? 1.0f + sv : 0.f;
                 }
             }
-            if constexpr (PP == 1) {
-                pf[s].p[0] = cat4(to_bf16x4(pt[0]), to_bf16x4(pt[1]));
-            } else {
-                bf16x4 h0, l0, h1, l1;
-                split4(pt[0], h0, l0);
-                split4(pt[1], h1, l1);
-                pf[s].p[0] = cat4(h0, h1);
-                pf[s].p[1] = cat4(l0, l1);
-            }
+            bf16x4 h0, l0, h1, l1;
+            split4(pt[0], h0, l0);
+            split4(pt[1], h1, l1);
+            pf[s].p[0] = cat4(h0, h1);
+            pf[s].p[1] = cat4(l0, l1);
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -222,7 +199,7 @@ __global__ __launch_bounds__(256, DP == 64 ? 2 : 1) void fwd_p1_mfma_bf16_kernel
                 for (int dt = 0; dt < DT; ++dt) {
                     const bf16x8 vf = ld_tr8<DP>(smem, VI, 32 * s, 16 * dt, lane);
                     oacc[dt] = mfma(vf, pf[s].p[0], oacc[dt]);
-                    if constexpr (PP == 2) oacc[dt] = mfma(vf, pf[s].p[1], oacc[dt]);
+                    oacc[dt] = mfma(vf, pf[s].p[1], oacc[dt]);
                 }
             }
         }
@@ -478,10 +455,10 @@ static int launch_bf16_d128(const Bf16Params& prm, int nb, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-template <int DP, bool NORM, int LEAN>
-static int launch_bf16_l(const Bf16Params& prm, int nb, hipStream_t stream) {
-    constexpr int lds = 3 * 64 * DP * 2 + (LEAN ? 1 : 2) * (DP + 16) * DP * 2 + DP * 4;
-    auto kern = fwd_p1_mfma_bf16_kernel<DP, NORM, LEAN>;
+template <int DP, bool NORM>
+static int launch_bf16_t(const Bf16Params& prm, int nb, hipStream_t stream) {
+    constexpr int lds = 3 * 64 * DP * 2 + (DP + 16) * DP * 2 + DP * 4;
+    auto kern = fwd_p1_mfma_bf16_kernel<DP, NORM>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -490,15 +467,6 @@ static int launch_bf16_l(const Bf16Params& prm, int nb, hipStream_t stream) {
     }
     hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, stream, prm);
     return (int)hipGetLastError();
-}
-
-template <int DP, bool NORM>
-static int launch_bf16_t(const Bf16Params& prm, int nb, hipStream_t stream) {
-    // default 2 = single-part state image, two-part P: measured error = the bf16 rounding of the result (1.578e-3 vs 1.572e-3
-    // normwise), 8 % faster than 0 (both two-part); 1 = P single-part as well: 12 % faster, 1.4x the rounding error
-    static const int lean = [] { const char* e = getenv("FASTMAX_BF16_LEAN"); return e ? atoi(e) : 2; }();
-    if (lean == 2) return launch_bf16_l<DP, NORM, 2>(prm, nb, stream);
-    return lean ? launch_bf16_l<DP, NORM, 1>(prm, nb, stream) : launch_bf16_l<DP, NORM, 0>(prm, nb, stream);
 }
 
 bool mfma_bf16_supported(const fastmax_problem& p) {

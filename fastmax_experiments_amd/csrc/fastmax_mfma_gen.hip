@@ -1,4 +1,4 @@
-// fastmax p=1 masked forward, linear in N, matrix cores -- the generic sibling of fastmax_mfma.hip:
+// fastmax p=1 masked forward, linear in N, matrix cores -- the generic sibling of fastmax_mfma_v2.hip:
 // any input dtype (fp32 / fp16 as bf16 hi+lo parts, bf16 as exact single parts), head sizes padded to
 // DP = 64 or 128 columns in LDS, optional fused linearmax prologue.
 //

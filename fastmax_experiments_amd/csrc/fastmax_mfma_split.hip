@@ -8,7 +8,6 @@
 // Cost: K and V of all but the last segment are read twice (+ <= 50 % of the K,V bytes, 0 when nseg = 1).
 #include "fastmax_mfma_common.h"
 
-#include <cstdlib>
 
 namespace fastmax {
 
@@ -306,9 +305,8 @@ __global__ __launch_bounds__(256) void p1_state_prefix_scale_kernel(float* state
 
 SplitPlan split_plan(const fastmax_problem& p) {
     // aim at two workgroups per CU for D <= 64 and one for D > 64 (those kernels hold a 128 x 128 state: one 8-wave
-    // workgroup per CU); FASTMAX_SPLIT_TARGET overrides for experiments (measured: 512 is the optimum at D = 64)
-    static const int forced = [] { const char* e = getenv("FASTMAX_SPLIT_TARGET"); return e ? atoi(e) : 0; }();
-    const int target = forced ? forced : (p.D > 64 ? 256 : 512);
+    // workgroup per CU; measured: 512 is the optimum at D = 64)
+    const int target = p.D > 64 ? 256 : 512;
     const int BH = p.B * p.H, nchunks = (p.Nq + 63) / 64;
     if (BH >= target * 3 / 4 || nchunks < 8) return SplitPlan{1, nchunks};
     int nseg = (target + BH - 1) / BH;

@@ -1,11 +1,33 @@
-// fastmax p=1 masked forward, D = 64, fp32 I/O -- second generation of the headline kernel (gfx950).
+// fastmax p=1 masked forward on the CDNA4 matrix cores (gfx950), linear in N: the headline kernel, D = 64, fp32 I/O.
 //
-// Same algorithm and work split as fastmax_mfma.hip (64-token chunks, carried S2 = sum k v^T in MFMA accumulators, split-bf16
-// products, attention_mechanisms/fastmax.py:236-241 and 306-312 without the (N,D,D) temporaries), rebuilt to ISSUE LESS per
-// chunk.  Measured reason (profiles/r02_transient.md): from an idle device the chip runs the first launches at boost clock,
-// then its power controller pulls the clock down and lets it recover over ~60 launches -- but only when the kernel does
-// matrix / vector work; the same memory traffic with no arithmetic shows no dip.  Inside the dip the kernel is issue-bound,
-// not HBM-bound, so every vector / LDS instruction removed counts twice: fewer cycles at the low clock and a shallower dip.
+// One workgroup (4 waves) walks one (b,h) head in chunks of C = 64 tokens, carrying
+//     S2 = sum_{j<chunk} k_j v_j^T   (D x D, fp32, in MFMA accumulators; a bf16 hi/lo image of it in LDS)
+//     S1 = sum v_j,  ksum = sum k_j   (fp32, exact vector-ALU sums, in LDS)
+// and computes per chunk, with q' = a*q (a = 1/nt):
+//     O^T[d][i]  = S1[d] + (S2^T q'_i)[d]                  inter-chunk   (3)
+//                + sum_{j<=i} (1 + q'_i.k_j) v_j[d]        intra-chunk   (1) S^T = K Q'^T, (2) O^T += V^T P^T
+//     g_i        = (i+1) + q'_i.ksum_prev + sum_{j<=i in chunk} q'_i.k_j
+//     S2        += K^T V                                    state update  (4)
+// which is attention_mechanisms/fastmax.py:236-241 (F) and 306-312 (g) without the (N,D,D) temporaries.
+//
+// Numerics: fp32 inputs are split into bf16 hi + bf16 lo and every product uses 3 MFMAs
+// (hi*hi + lo*hi + hi*lo, fp32 accumulate): ~2^-16 relative per product.  gfx950 has no xf32 and its
+// fp32-input MFMA runs at 1/16 of the bf16 rate, which would leave this kernel matrix-bound.
+//
+// Work split: wave w owns one 16-query tile of the chunk (all D output columns) for (1)-(3) -- the tile rotates with the
+// chunk, so the heavy (late) tile moves round the waves -- and the value-column slab 16w..16w+15 of S2 for (4).  All
+// operands are MFMA 16x16x32 bf16 fragments:
+//   * Q' B fragments straight from global memory (see below), K rows (ds_read_b128) from a row-major [token][m] image,
+//   * V^T, K^T transposed reads (ds_read_b64_tr_b16) from the row-major images,
+//   * P^T and S2 come straight from accumulator registers.
+// LDS images use 128-byte rows with the 16-byte chunk index XOR-ed with (row & 7): conflict-free for both kinds of read.
+// Heads whose byte span does not fit the 31-bit buffer offsets go to the generic kernel (fastmax_mfma_gen.hip).
+//
+// This is the second generation of the kernel, rebuilt to ISSUE LESS per chunk than the first.  Measured reason
+// (profiles/r02_transient.md): from an idle device the chip runs the first launches at boost clock, then its power controller
+// pulls the clock down and lets it recover over ~60 launches -- but only when the kernel does matrix / vector work; the same
+// memory traffic with no arithmetic shows no dip.  Inside the dip the kernel is issue-bound, not HBM-bound, so every vector /
+// LDS instruction removed counts twice: fewer cycles at the low clock and a shallower dip.
 //
 // What changed against the first generation:
 //   * Q is never staged: a wave's 16 query rows go from global memory straight into split B fragments (16 floats per
@@ -415,12 +437,8 @@ __global__ __launch_bounds__(256, 2) void fwd_p1_d64_f32_v2_kernel(MfmaV2Params 
     }
 }
 
-bool mfma_p1_v2_supported(const FwdArgs& a) {
-    const fastmax_problem& p = a.prob;
-    if (!(p.p == 1 && p.causal && p.D == 64 && p.in_dtype == FASTMAX_F32 && p.out_dtype == FASTMAX_F32)) return false;
-    // 32-bit byte offsets inside one head
-    const int64_t lim = (int64_t)1 << 31;
-    return (int64_t)p.Nq * a.qs.sn * 4 < lim && (int64_t)p.Nq * a.ks.sn * 4 < lim && (int64_t)p.Nq * a.vs.sn * 4 < lim;
+bool mfma_p1_supported(const fastmax_problem& p) {
+    return p.p == 1 && p.causal && p.D == 64 && p.in_dtype == FASTMAX_F32 && p.out_dtype == FASTMAX_F32;
 }
 
 template <int ABL, bool RAGGED, int NMF = 3>
@@ -437,8 +455,12 @@ static int launch_v2_variant(const MfmaV2Params& prm, int nblocks, hipStream_t s
     return (int)hipGetLastError();
 }
 
-int launch_fwd_mfma_p1_v2(const FwdArgs& a, int ablation) {
-    if (!mfma_p1_v2_supported(a)) return FASTMAX_E_BAD_SHAPE;
+int launch_fwd_mfma_p1(const FwdArgs& a) {
+    if (!mfma_p1_supported(a.prob)) return FASTMAX_E_BAD_SHAPE;
+    // 31-bit buffer offsets inside one head; anything larger goes to the generic kernel (64-bit addresses)
+    const int64_t lim = (int64_t)1 << 31;
+    if (!((int64_t)a.prob.Nq * a.qs.sn * 4 < lim && (int64_t)a.prob.Nq * a.ks.sn * 4 < lim && (int64_t)a.prob.Nq * a.vs.sn * 4 < lim))
+        return launch_fwd_mfma_gen(a, nullptr, nullptr);
     const SplitPlan plan = split_plan(a.prob);
     if (plan.nseg > 1) {
         if (!a.workspace || a.workspace_bytes < split_workspace_bytes(a.prob, 64)) return FASTMAX_E_WORKSPACE;
@@ -450,7 +472,9 @@ int launch_fwd_mfma_p1_v2(const FwdArgs& a, int ablation) {
     const int nb = a.prob.B * a.prob.H * plan.nseg;
     const bool ragged = (a.prob.Nq & 63) != 0;
 #ifdef FASTMAX_ABLATIONS
-    switch (ablation) {                                              // timing-only ablations: WRONG RESULTS, ablation builds only
+    // tuning key "mfma_variant" (FASTMAX_MFMA_VARIANT at load): 200 = the kernel; 201 / 204..209 timing-only ablations
+    const int variant = tune_get(TUNE_MFMA_VARIANT);
+    switch (variant == 209 ? 1 : variant - 200) {                    // timing-only ablations: WRONG RESULTS, ablation builds only
         case 1: return launch_v2_variant<1, true>(prm, nb, a.stream);        // memory passes only
         case 6: return launch_v2_variant<2, true>(prm, nb, a.stream);
         case 7: return launch_v2_variant<3, true>(prm, nb, a.stream);
@@ -459,8 +483,6 @@ int launch_fwd_mfma_p1_v2(const FwdArgs& a, int ablation) {
         case 5: return launch_v2_variant<0, true, 0>(prm, nb, a.stream);      // no matrix instructions
         default: break;
     }
-#else
-    (void)ablation;
 #endif
     return ragged ? launch_v2_variant<0, true>(prm, nb, a.stream) : launch_v2_variant<0, false>(prm, nb, a.stream);
 }

@@ -7,8 +7,6 @@
 // Rows are spread over LPR lanes with 16-byte loads (scalar loads for unaligned views).  The backward is two launches:
 // the row pass (every row without the dL/dM term + per-block partials sum gy.xc, best (norm^2, n)), then one wave per head
 // that combines the partials in a fixed order (bitwise reproducible) and rewrites the one row that has the extra term.
-#include <stdlib.h>
-
 #include "fastmax_common.h"
 
 namespace fastmax {
@@ -91,108 +89,11 @@ __global__ __launch_bounds__(256) void normalize_cast_kernel(const void* x, Stri
     }
 }
 
-// ---- backward, pass 1: per block  sum_n gy_n . xc_n  and the best (||xc_n||^2, first n) ------------------------------------
-template <typename T, int LPR>
-__global__ __launch_bounds__(256) void normalize_bwd_reduce_kernel(const void* x, Strides3 xs, const T* gy, int H, int N, int D,
-                                                                   float* part_dot, unsigned long long* part_best, int vec) {
-    constexpr int EPL = 16 / sizeof(T), RPB = 256 / LPR, TOK = 256;
-    __shared__ float sdot[4];
-    __shared__ unsigned long long sbest[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = tid % LPR, rgrp = tid / LPR;
-    const int bh = blockIdx.y, b = bh / H, h = bh % H;
-    const float invD = 1.0f / (float)D;
-    const int n_begin = blockIdx.x * TOK, n_end = min(N, n_begin + TOK);
-    float dot = 0.f;
-    unsigned long long best = 0ull;
-    for (int n = n_begin + rgrp; n < n_end; n += RPB) {
-        float v[EPL], gv[EPL];
-        load_row_piece<T>(row_ptr<T>(x, xs.sb, xs.sh, xs.sn, b, h, n), sub, D, vec, v);
-        load_row_piece<T>(gy + ((int64_t)bh * N + n) * D, sub, D, vec, gv);
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) s += v[e];
-        const float mean = group_sum<LPR>(s) * invD;
-        float nn = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-            const float c = (sub * EPL + e) < D ? v[e] - mean : 0.f;
-            nn = fmaf(c, c, nn);
-            dot = fmaf(gv[e], c, dot);
-        }
-        nn = group_sum<LPR>(nn);
-        // squared norms are >= 0: their bit patterns order like unsigned integers; ties -> the smallest n (torch.argmax)
-        const unsigned long long key = ((unsigned long long)__float_as_uint(nn) << 32) | (unsigned long long)(0xffffffffu - (unsigned)n);
-        best = key > best ? key : best;
-    }
-    dot = wave_sum(dot);
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-    }
-    if (lane == 0) { sdot[wave] = dot; sbest[wave] = best; }
-    __syncthreads();
-    if (tid == 0) {
-        const int idx = bh * gridDim.x + blockIdx.x;
-        part_dot[idx] = (sdot[0] + sdot[1]) + (sdot[2] + sdot[3]);
-        unsigned long long m = sbest[0];
-#pragma unroll
-        for (int i = 1; i < 4; ++i) m = sbest[i] > m ? sbest[i] : m;
-        part_best[idx] = m;
-    }
-}
-
-// ---- backward, pass 2: the row pass ---------------------------------------------------------------------------------------
-template <typename T, int LPR>
-__global__ __launch_bounds__(256) void normalize_bwd_apply_kernel(const void* x, Strides3 xs, const T* gy, const float* inv_norm,
-                                                                  const float* part_dot, const unsigned long long* part_best,
-                                                                  int H, int N, int D, T* gx, int vec) {
-    constexpr int EPL = 16 / sizeof(T), RPB = 256 / LPR, TOK = 256;
-    const int tid = threadIdx.x, sub = tid % LPR, rgrp = tid / LPR;
-    const int bh = blockIdx.y, b = bh / H, h = bh % H;
-    const float inv = inv_norm[bh], invD = 1.0f / (float)D;
-    float S = 0.f;
-    unsigned long long best = 0ull;
-    for (int i = 0; i < (int)gridDim.x; ++i) {                     // fixed order: reproducible
-        S += part_dot[bh * gridDim.x + i];
-        const unsigned long long o = part_best[bh * gridDim.x + i];
-        best = o > best ? o : best;
-    }
-    const int nstar = (int)(0xffffffffu - (unsigned)(best & 0xffffffffull));
-    const float dLdM = -(S * inv) * inv;                           // -sum(gy y) / M,  y = xc / M
-    const int n_begin = blockIdx.x * TOK, n_end = min(N, n_begin + TOK);
-    for (int n = n_begin + rgrp; n < n_end; n += RPB) {
-        float gv[EPL];
-        load_row_piece<T>(gy + ((int64_t)bh * N + n) * D, sub, D, vec, gv);
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) gv[e] *= inv;
-        if (n == nstar) {                                          // uniform per row group
-            float v[EPL];
-            load_row_piece<T>(row_ptr<T>(x, xs.sb, xs.sh, xs.sn, b, h, n), sub, D, vec, v);
-            float s = 0.f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) s += v[e];
-            const float mean = group_sum<LPR>(s) * invD;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e)
-                if (sub * EPL + e < D) gv[e] = fmaf(dLdM, (v[e] - mean) * inv, gv[e]);
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) s += gv[e];
-        const float gm = group_sum<LPR>(s) * invD;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) gv[e] -= gm;
-        store_row_piece<T>(gx + ((int64_t)bh * N + n) * D, sub, D, vec, gv);
-    }
-}
-
 // ---- backward in one row pass + a one-row fix-up ----------------------------------------------------------------------------
 // Only the row that attains the maximum (n*) sees the dL/dM term, so every row can be written as  gx = inv gy - mean_D(inv gy)
 // in the SAME pass that accumulates the block's  sum gy.xc  and best (||xc||^2, n); a one-workgroup-per-head kernel then
-// combines the partials (fixed order) and rewrites row n* with the full formula.  x and gy are read once instead of twice;
-// same formulas as the reduce + apply pair above (kept for A/B runs); results differ from it by last-bit float32 rounding only
-// (the compiler contracts the two forms differently).
+// combines the partials (fixed order) and rewrites row n* with the full formula.  x and gy are read once, not twice as by a
+// reduce pass followed by an apply pass.
 template <typename T, int LPR>
 __global__ __launch_bounds__(256) void normalize_bwd_rows_kernel(const void* x, Strides3 xs, const T* gy, const float* inv_norm, int H, int N,
                                                                  int D, T* gx, float* part_dot, unsigned long long* part_best, int vec, int rep, int tok) {
@@ -412,20 +313,11 @@ static int normalize_bwd_t(const void* x, Strides3 xs, const void* gy, const flo
     unsigned long long* part_best = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(ws) + 7) & ~(uintptr_t)7);
     float* part_dot = reinterpret_cast<float*>(part_best + (size_t)B * H * nblk);
     const dim3 grid(nblk, B * H), block(256);
-    static const bool two_pass_env = getenv("FASTMAX_NORMALIZE_BWD_TWO_PASS") != nullptr;  // the reduce + apply pair, for A/B runs
-    const bool two_pass = two_pass_env && rep == 1;
 #define CALL(L)                                                                                                                   \
-    if (two_pass) {                                                                                                               \
-        hipLaunchKernelGGL((normalize_bwd_reduce_kernel<T, L>), grid, block, 0, stream, x, xs, reinterpret_cast<const T*>(gy), H, N, D, \
-                           part_dot, part_best, vec);                                                                             \
-        hipLaunchKernelGGL((normalize_bwd_apply_kernel<T, L>), grid, block, 0, stream, x, xs, reinterpret_cast<const T*>(gy), inv_norm, \
-                           part_dot, part_best, H, N, D, reinterpret_cast<T*>(gx), vec);                                          \
-    } else {                                                                                                                      \
-        hipLaunchKernelGGL((normalize_bwd_rows_kernel<T, L>), grid, block, 0, stream, x, xs, reinterpret_cast<const T*>(gy), inv_norm, H, N, \
-                           D, reinterpret_cast<T*>(gx), part_dot, part_best, vec, rep, tok);                                      \
-        hipLaunchKernelGGL((normalize_bwd_fix_kernel<T, L>), dim3(B * H), dim3(64), 0, stream, x, xs, reinterpret_cast<const T*>(gy),   \
-                           inv_norm, part_dot, part_best, nblk, H, N, D, reinterpret_cast<T*>(gx), vec, rep);                     \
-    }
+    hipLaunchKernelGGL((normalize_bwd_rows_kernel<T, L>), grid, block, 0, stream, x, xs, reinterpret_cast<const T*>(gy), inv_norm, H, N,   \
+                       D, reinterpret_cast<T*>(gx), part_dot, part_best, vec, rep, tok);                                              \
+    hipLaunchKernelGGL((normalize_bwd_fix_kernel<T, L>), dim3(B * H), dim3(64), 0, stream, x, xs, reinterpret_cast<const T*>(gy),       \
+                       inv_norm, part_dot, part_best, nblk, H, N, D, reinterpret_cast<T*>(gx), vec, rep);
     NRM_LPR_SWITCH(need, CALL)
 #undef CALL
     return (int)hipGetLastError();

@@ -387,25 +387,16 @@ static int launch_quad32_w(Quad32Params prm, hipStream_t stream) {
 }
 template <int DP, int P, typename TIN, int NPP, bool UNIT>
 static int launch_quad32_n(const Quad32Params& prm, hipStream_t stream) {
-    static const int sched = [] { const char* e = getenv("FASTMAX_QUAD32_SCHED"); return e ? atoi(e) : -1; }();
-    static const int qbenv = [] { const char* e = getenv("FASTMAX_QUAD32_QB"); return e ? atoi(e) : 0; }();
-    constexpr bool SINGLE = InTraits<TIN>::NP == 1 && NPP == 1;
-    if constexpr (SINGLE && DP == 64) {
-        // bf16, D <= 64, 16-bit result: two query blocks per wave once a head has enough query tiles of 256
-        const int qb = qbenv ? qbenv : (prm.Nq >= 1024 ? 2 : 1);
-        if (qb == 2) {
-            if (sched == 0) return launch_quad32_w<DP, P, TIN, NPP, 4, UNIT, 0, 2>(prm, stream);
-            return launch_quad32_w<DP, P, TIN, NPP, 4, UNIT, 1, 2>(prm, stream);
-        }
-        if (sched == 1) return launch_quad32_w<DP, P, TIN, NPP, 4, UNIT, 1, 1>(prm, stream);
+    if constexpr (InTraits<TIN>::NP == 1 && NPP == 1 && DP == 64) {
+        // bf16, D <= 64, 16-bit result: two query blocks per wave, with the grouped issue order, once a head has enough query
+        // tiles of 256
+        if (prm.Nq >= 1024) return launch_quad32_w<DP, P, TIN, NPP, 4, UNIT, 1, 2>(prm, stream);
         return launch_quad32_w<DP, P, TIN, NPP, 4, UNIT, 0, 1>(prm, stream);
     } else {
         // everything else: one query block per wave; eight waves unless the operands are bf16 at D <= 64; D = 128 with the
         // grouped issue order
         constexpr int NWD = (DP == 64 && InTraits<TIN>::NP == 1) ? 4 : 8;
-        constexpr int DEF_SCHED = DP == 128 ? 1 : 0;
-        if ((sched >= 0 ? sched : DEF_SCHED) == 1) return launch_quad32_w<DP, P, TIN, NPP, NWD, UNIT, 1, 1>(prm, stream);
-        return launch_quad32_w<DP, P, TIN, NPP, NWD, UNIT, 0, 1>(prm, stream);
+        return launch_quad32_w<DP, P, TIN, NPP, NWD, UNIT, DP == 128 ? 1 : 0, 1>(prm, stream);
     }
 }
 // a = 2^e exactly: scaling single-part (bf16) query fragments by it loses nothing

@@ -374,8 +374,7 @@ static int launch_scan_t(const ScanParams& prm, int nb, hipStream_t stream) {
 // few heads: segments of at least 8 chunks (512 tokens) until ~256 workgroups exist (one per CU: 132 KB of LDS each)
 static void scan_split_plan(const fastmax_problem& p, int& nseg, int& cps) {
     const int nchunks = (p.Nq + 63) / 64, BH = p.B * p.H;
-    static const int target = [] { const char* e = getenv("FASTMAX_SCAN_SPLIT_TARGET"); return e ? atoi(e) : 256; }();
-    int want = target / (BH > 0 ? BH : 1);
+    int want = 256 / (BH > 0 ? BH : 1);
     if (want > nchunks / 8) want = nchunks / 8;
     if (want < 1) want = 1;
     cps = (nchunks + want - 1) / want;

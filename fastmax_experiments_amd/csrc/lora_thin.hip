@@ -17,8 +17,6 @@
 //         the row's R coefficients are wave-uniform (one dword per lane + v_readlane), Bn lives in registers.  As many waves
 //         as the device holds at once, each walking its column slab with two row blocks in flight.
 //         16 R FMAs per 16 bytes: VALU, under the HBM time.
-#include <stdlib.h>
-
 #include "fastmax_mfma_common.h"
 
 namespace fastmax {
@@ -165,6 +163,8 @@ __global__ __launch_bounds__(256) void lora_down_kernel(const DownParams p) {
 // ---------------------------------------------------------------------------------------------------------------------
 // tn
 // ---------------------------------------------------------------------------------------------------------------------
+constexpr int TN_KS = 2;   // 32-row MFMA k-steps per stage: the X stage is 32 TN_KS rows
+
 struct TnParams {
     const __bf16* et; int64_t ldet; int etcols;    // columns >= M up to etcols are zero; etcols % 4 == 0
     const __bf16* x; int64_t ldx;
@@ -173,11 +173,11 @@ struct TnParams {
     DropParams drop;                               // DROP: X is dropout(x), the mask regenerated per piece (the scale is applied by the caller's reduce pass)
 };
 
-template <int RPB, int KS, bool DROP = false>   // stages of 32 KS rows
+template <int RPB, bool DROP = false>
 __global__ __launch_bounds__(256) void lora_tn_kernel(const TnParams p) {
-    constexpr int SR = 32 * KS, SB = SR * 128;                  // X stage: SR rows x 64 columns
+    constexpr int SR = 32 * TN_KS, SB = SR * 128;               // X stage: SR rows x 64 columns
     constexpr int RSA = 2 * SR + 16, AB = 16 * RPB * RSA;       // E^T stage: 16 RPB rows x SR columns, padded rows
-    constexpr int NP8 = (RPB * KS + 1) / 2;                     // 8-byte pieces of the E^T stage per thread
+    constexpr int NP8 = (RPB * TN_KS + 1) / 2;                  // 8-byte pieces of the E^T stage per thread
     __shared__ __attribute__((aligned(16))) char smem[2 * SB + 2 * AB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int n0 = blockIdx.x * 64, s = blockIdx.y;
@@ -188,18 +188,18 @@ __global__ __launch_bounds__(256) void lora_tn_kernel(const TnParams p) {
     for (int cb = 0; cb < RPB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // both operands go global -> registers (two stages ahead) -> LDS (one stage ahead) -> fragments
-    struct Regs { tu32x4 x[KS]; tu32x2 a[NP8]; };
+    struct Regs { tu32x4 x[TN_KS]; tu32x2 a[NP8]; };
     auto fetch = [&](int st, Regs& t) {
         const int mb = mbeg + st * SR;
 #pragma unroll
-        for (int i = 0; i < KS; ++i) {
+        for (int i = 0; i < TN_KS; ++i) {
             const int piece = tid + 256 * i, row = piece >> 3, chunk = piece & 7;
             t.x[i] = tu32x4{0, 0, 0, 0};
             if (mb + row < mend) t.x[i] = THIN_STREAM_LOAD(reinterpret_cast<const tu32x4*>(p.x + (int64_t)(mb + row) * p.ldx + n0 + 8 * chunk));
         }
 #pragma unroll
         for (int i = 0; i < NP8; ++i) {
-            const int piece = tid + 256 * i, c = piece / (8 * KS), mm = mb + (piece % (8 * KS)) * 4;
+            const int piece = tid + 256 * i, c = piece / (8 * TN_KS), mm = mb + (piece % (8 * TN_KS)) * 4;
             t.a[i] = tu32x2{0, 0};
             if (c < 16 * RPB && mm < mend && mm + 4 <= p.etcols) t.a[i] = *reinterpret_cast<const tu32x2*>(p.et + (int64_t)c * p.ldet + mm);
         }
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void lora_tn_kernel(const TnParams p) {
     if constexpr (DROP) seed = p.drop.seed[0];
     auto stage = [&](const Regs& t, int buf, int st) {
 #pragma unroll
-        for (int i = 0; i < KS; ++i) {
+        for (int i = 0; i < TN_KS; ++i) {
             const int piece = tid + 256 * i, row = piece >> 3, chunk = piece & 7;
             tu32x4 xv = t.x[i];
             if constexpr (DROP) xv = drop_piece(xv, seed, mbeg + st * SR + row, n0 + 8 * chunk, p.drop);
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void lora_tn_kernel(const TnParams p) {
         }
 #pragma unroll
         for (int i = 0; i < NP8; ++i) {
-            const int piece = tid + 256 * i, c = piece / (8 * KS), mo = (piece % (8 * KS)) * 4;
+            const int piece = tid + 256 * i, c = piece / (8 * TN_KS), mo = (piece % (8 * TN_KS)) * 4;
             if (c < 16 * RPB) *reinterpret_cast<tu32x2*>(smem + 2 * SB + buf * AB + c * RSA + mo * 2) = t.a[i];
         }
     };
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void lora_tn_kernel(const TnParams p) {
         const int buf = st & 1;
         if (st + 2 < nst) fetch(st + 2, free);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
+        for (int ks = 0; ks < TN_KS; ++ks) {
             const bf16x8 b = ld_tr8<64>(smem, buf * SB, 32 * ks, 16 * wave, lane);
 #pragma unroll
             for (int cb = 0; cb < RPB; ++cb) {
@@ -282,16 +282,10 @@ __global__ __launch_bounds__(256) void lora_tn_reduce_kernel(const float* part, 
     else reinterpret_cast<float*>(out)[o] = s;
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static int tn_ks() { static const int ks = env_int("FASTMAX_LORA_TN_KS", 2) == 4 ? 4 : 2; return ks; }
-
+// about 1024 workgroups: the 64-column slabs times the row ranges
 static void tn_plan(int M, int ncols, int& S, int& rps) {
-    static const int target = env_int("FASTMAX_LORA_TN_TARGET", 1024);
-    const int slabs = ncols / 64, sr = 32 * tn_ks();
-    int want = (target + slabs - 1) / slabs;
+    const int slabs = ncols / 64, sr = 32 * TN_KS;
+    int want = (1024 + slabs - 1) / slabs;
     const int maxs = (M + sr - 1) / sr;
     if (want > maxs) want = maxs;
     if (want < 1) want = 1;
@@ -312,6 +306,8 @@ struct UpParams {
     DropParams drop;               // DROP: y[m][n] += keep(m, n) / (1 - p) * (e bn^T)[m][n]   (dx of the dropped-out LoRA input)
 };
 
+constexpr int UP_RU = 4;   // rows per block of lora_up_kernel
+
 template <int NPL> struct UpVec;
 template <> struct UpVec<8> { typedef tu32x4 type; };
 template <> struct UpVec<4> { typedef tu32x2 type; };
@@ -319,13 +315,13 @@ template <> struct UpVec<4> { typedef tu32x2 type; };
 __device__ __forceinline__ float bf_lo(unsigned int w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned int w) { return __uint_as_float(w & 0xffff0000u); }
 
-// Each wave keeps one slab of 64 NPL columns (its Bn rows stay in registers) and walks row blocks of RU rows with a stride
+// Each wave keeps one slab of 64 NPL columns (its Bn rows stay in registers) and walks row blocks of UP_RU rows with a stride
 // of `groups` blocks, two blocks in flight: the loads of block i+1 are issued before block i is finished.  The block's
-// RU x R coefficients are fetched with one dword per lane and broadcast with v_readlane.
-template <int R, int NPL, int RU, bool DROP = false>
+// UP_RU x R coefficients are fetched with one dword per lane and broadcast with v_readlane.
+template <int R, int NPL, bool DROP = false>
 __global__ __launch_bounds__(256) void lora_up_kernel(const UpParams p) {
     typedef typename UpVec<NPL>::type vec_t;
-    static_assert(RU * R / 2 <= 64, "one dword of E per lane");
+    static_assert(UP_RU * R / 2 <= 64, "one dword of E per lane");
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int w = blockIdx.x * 4 + wave;
@@ -334,7 +330,7 @@ __global__ __launch_bounds__(256) void lora_up_kernel(const UpParams p) {
     const int n = slab * 64 * NPL + lane * NPL;
     const bool act = n < p.N;
     const int nn = act ? n : 0;                                              // idle lanes read column 0 and store nothing
-    const int nblk = (p.M + RU - 1) / RU;
+    const int nblk = (p.M + UP_RU - 1) / UP_RU;
     float b[NPL][R], bias[NPL];
 #pragma unroll
     for (int j = 0; j < NPL; ++j) bias[j] = p.bias ? p.bias[nn + j] : 0.f;
@@ -362,24 +358,24 @@ __global__ __launch_bounds__(256) void lora_up_kernel(const UpParams p) {
             }
         }
     }
-    struct Blk { vec_t y[RU]; unsigned int e; };
+    struct Blk { vec_t y[UP_RU]; unsigned int e; };
     unsigned int seed = 0;
     if constexpr (DROP) seed = p.drop.seed[0];
     const int eu = lane / (R / 2), ec = lane % (R / 2);                      // this lane's dword of the block's coefficients
     auto fetch = [&](int bi, Blk& t) {
-        const int m = bi * RU;
+        const int m = bi * UP_RU;
 #pragma unroll
-        for (int u = 0; u < RU; ++u) {
+        for (int u = 0; u < UP_RU; ++u) {
             t.y[u] = vec_t{};
             if (act && m + u < p.M) t.y[u] = THIN_STREAM_LOAD(reinterpret_cast<const vec_t*>(p.y + (int64_t)(m + u) * p.ldy + n));
         }
         t.e = 0;
-        if (eu < RU && m + eu < p.M) t.e = *reinterpret_cast<const unsigned int*>(p.e + (int64_t)(m + eu) * p.lde + 2 * ec);
+        if (eu < UP_RU && m + eu < p.M) t.e = *reinterpret_cast<const unsigned int*>(p.e + (int64_t)(m + eu) * p.lde + 2 * ec);
     };
     auto finish = [&](int bi, const Blk& t) {
-        const int m = bi * RU;
+        const int m = bi * UP_RU;
 #pragma unroll
-        for (int u = 0; u < RU; ++u) {
+        for (int u = 0; u < UP_RU; ++u) {
             float o[NPL], d[NPL];
 #pragma unroll
             for (int j = 0; j < NPL; j += 2) {
@@ -425,24 +421,24 @@ __global__ __launch_bounds__(256) void lora_up_kernel(const UpParams p) {
     }
 }
 
-template <int R, int NPL, int RU> static int up_launch(UpParams p, hipStream_t stream) {
+template <int R, int NPL> static int up_launch(UpParams p, hipStream_t stream) {
     static int resident = 0;                          // waves of this kernel the device holds at once
     if (!resident) {
         int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lora_up_kernel<R, NPL, RU, false>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lora_up_kernel<R, NPL, false>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        resident = per_cu * cus * 4 * env_int("FASTMAX_LORA_UP_OVERSUB", 1);
+        resident = per_cu * cus * 4;
     }
     p.nslab = (p.N + 64 * NPL - 1) / (64 * NPL);
-    const int nblk = (p.M + RU - 1) / RU;
+    const int nblk = (p.M + UP_RU - 1) / UP_RU;
     int groups = resident / p.nslab;
     if (groups < 1) groups = 1;
     if (groups > nblk) groups = nblk;
     p.groups = groups;
     const int64_t waves = (int64_t)p.nslab * groups;
-    if (p.drop.seed) hipLaunchKernelGGL((lora_up_kernel<R, NPL, RU, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((lora_up_kernel<R, NPL, RU, false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
+    if (p.drop.seed) hipLaunchKernelGGL((lora_up_kernel<R, NPL, true>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((lora_up_kernel<R, NPL, false>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
     return (int)hipGetLastError();
 }
 
@@ -548,18 +544,13 @@ static int lora_tn_impl(const void* et, int64_t ldet, const void* x, int64_t ldx
                M, ncols, rps, make_drop(seed, p_drop, ncols)};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(ncols / 64, S);
-#define TN_LAUNCH(RPB, KS)                                                                                      \
+#define TN_LAUNCH(RPB)                                                                                          \
     do {                                                                                                        \
-        if (p.drop.seed) hipLaunchKernelGGL((lora_tn_kernel<RPB, KS, true>), grid, dim3(256), 0, s, p);         \
-        else hipLaunchKernelGGL((lora_tn_kernel<RPB, KS, false>), grid, dim3(256), 0, s, p);                    \
+        if (p.drop.seed) hipLaunchKernelGGL((lora_tn_kernel<RPB, true>), grid, dim3(256), 0, s, p);             \
+        else hipLaunchKernelGGL((lora_tn_kernel<RPB, false>), grid, dim3(256), 0, s, p);                        \
     } while (0)
-    if (tn_ks() == 4) {
-        if (RP == 16) TN_LAUNCH(1, 4);
-        else TN_LAUNCH(2, 4);
-    } else {
-        if (RP == 16) TN_LAUNCH(1, 2);
-        else TN_LAUNCH(2, 2);
-    }
+    if (RP == 16) TN_LAUNCH(1);
+    else TN_LAUNCH(2);
 #undef TN_LAUNCH
     const int64_t n = (int64_t)R * ncols;
     hipLaunchKernelGGL(lora_tn_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), out, S,
@@ -583,18 +574,11 @@ static int lora_up_impl(void* y, int64_t ldy, const void* e, int64_t lde, const 
     UpParams p{reinterpret_cast<__bf16*>(y), ldy, reinterpret_cast<const __bf16*>(e), lde, reinterpret_cast<const __bf16*>(bn), ldb, bias, bn_transposed ? 1 : 0, M, N, 0, 0,
                make_drop(seed, p_drop, N)};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    static const int variant = env_int("FASTMAX_LORA_UP_VARIANT", 0);
     switch (R) {
-        case 8: return variant & 1 ? up_launch<8, 8, 8>(p, s) : up_launch<8, 8, 4>(p, s);
-        case 16:
-            switch (variant) {
-                case 1: return up_launch<16, 4, 8>(p, s);
-                case 2: return up_launch<16, 4, 4>(p, s);
-                case 3: return up_launch<16, 8, 8>(p, s);
-                default: return up_launch<16, 8, 4>(p, s);
-            }
-        case 24: return up_launch<24, 4, 4>(p, s);
-        case 32: return up_launch<32, 4, 4>(p, s);
+        case 8: return up_launch<8, 8>(p, s);
+        case 16: return up_launch<16, 8>(p, s);
+        case 24: return up_launch<24, 4>(p, s);
+        case 32: return up_launch<32, 4>(p, s);
     }
     return FASTMAX_E_BAD_SHAPE;
 }

@@ -56,7 +56,7 @@ enum fastmax_path {
 
 /* Run-time tuning knob for A/B runs and ablations (no reference counterpart).  The FASTMAX_* environment variables are read
  * once, at the first call into the library; afterwards a knob changes only through this call.  Keys: "mfma_variant" (headline
- * forward kernel generation / schedule), "bf16_kernel" (1 = all-MFMA bf16 scan, 0 = generic).  Host-only, not stream-ordered:
+ * forward kernel: 200, or an ablation number below), "bf16_kernel" (1 = all-MFMA bf16 scan, 0 = generic).  Host-only, not stream-ordered:
  * call it between launches.  Returns 0, or FASTMAX_E_BAD_SHAPE for an unknown key. */
 int fastmax_hip_tune(const char* name, int value);
 /* Current value of a tuning key (so that a benchmark line can record the state it was measured in); INT_MIN for an unknown

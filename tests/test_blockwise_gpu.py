@@ -6,7 +6,7 @@ the per-tensor metric does not).
 
 Tolerances (per block; forward / backward).  The result's own rounding is 2^-8 = 3.9e-3 of an element in bf16 and
 2^-11 = 4.9e-4 in fp16, never more than that of its block's max; the kernels add the bf16 operands of their matrix products
-(q, k, P = 1 + a s and the single-part state image, fastmax_mfma_bf16.hip:29-31: 2^-9 relative each, averaged over D-term
+(q, k, P = 1 + a s and the single-part state image, fastmax_mfma_bf16.hip:27-31: 2^-9 relative each, averaged over D-term
 sums) or split-bf16 operands (~2^-16 per product) in fp32 accumulation for fp32.  Measured worst blocks sit at the result's
 rounding (bf16 3.6e-3 .. 5.8e-3, fp16 4.4e-4 .. 4.8e-4, fp32 <= 2.4e-5), so:
   bf16  8e-3 / 1e-2    -- 2x / 2.5x the result's rounding.
@@ -89,7 +89,8 @@ def test_config5_linearmax_16k_blockwise():
 # p = 1 masked through fastmax(); families from the *_supported predicates (fwd -> bwd):
 #   bf16, D <= 128             mfma_bf16_supported  -> fastmax_mfma_bf16.hip    | lin_bwd_supported -> fastmax_mfma_bwd_lin.hip
 #   fp16, D <= 64              mfma_gen_supported   -> fastmax_mfma_gen.hip     | lin_bwd_supported -> fastmax_mfma_bwd_lin.hip
-#   fp32, D == 64              mfma_p1_supported    -> fastmax_mfma.hip         | lin_bwd_supported -> fastmax_mfma_bwd_lin.hip
+#   fp32, D == 64              mfma_p1_supported    -> fastmax_mfma_v2.hip      | lin_bwd_supported -> fastmax_mfma_bwd_lin.hip
+#                              (a head whose byte span reaches 2 GiB -> fastmax_mfma_gen.hip, test_p1_f32_head_span_2gib_blockwise)
 #   fp32 / fp16, 64 < D <= 128 mfma_d128_2p_supported -> fastmax_mfma_d128_2p.hip | scan_bwd_supported -> fastmax_scan_d128_2p.hip
 # split: split_plan (fastmax_mfma_split.hip) cuts the sequence when B*H is far below the target; (16,32,4096,64) is not cut
 P1_CASES = [
@@ -126,6 +127,31 @@ def test_p1_masked_scans_blockwise(shape, dt, heads, split):
         _check(case, f"o h{bh}", _np(o[b, h]), ro, tf)
         for t, r, n in zip((qq, kk, vv), bw.p1_causal_bwd(qh, kh, vh, gh, nt), ("dq", "dk", "dv")):
             _check(case, f"{n} h{bh}", _np(t.grad[b, h]), r, tb)
+
+
+def test_p1_f32_head_span_2gib_blockwise():
+    """fp32, D = 64 heads whose byte span reaches 2 GiB do not fit the 31-bit buffer offsets of the headline kernel
+    (launch_fwd_mfma_p1, fastmax_mfma_v2.hip) and take the generic kernel (fastmax_mfma_gen.hip, 64-bit addresses), here
+    with the sequence split of a lone head.  q, k, v are column views of (N, W) buffers, which ops._prep passes through."""
+    from attention_mechanisms.fastmax import fastmax
+    from fastmax_experiments_amd import ops
+    N, W, D = 4096, 131072, 64
+    q, k, v, _ = _inputs((1, 1, N, D), torch.float32, N + D + 1)
+    nt = orc.effective_normalize_term(D)
+    views = []
+    for t in (q, k, v):
+        buf = torch.zeros(N, W, device="cuda")
+        buf[:, :D] = t[0, 0].cuda()
+        views.append(buf[:, :D][None, None])
+    for t in views:
+        assert ops._prep(t, t.device) is t                               # no copy: the kernel sees the W-float row stride
+        assert (N * t.stride(2)) * t.element_size() >= 2 ** 31           # past the 31-bit offsets of the headline kernel
+    qv, kv, vv = views
+    assert _split_ran(qv, kv, vv, nt)
+    with torch.no_grad():
+        o = fastmax(qv, kv, vv, mask=True, p=1)
+    ro, _ = bw.p1_causal_fwd(_np(q[0, 0]), _np(k[0, 0]), _np(v[0, 0]), nt)
+    _check(f"p1_span2GiB_1x1x{N}x{D}_float32", "o h0", _np(o[0, 0]), ro, TOL[torch.float32][0])
 
 
 # p = 2 masked: quad32_supported -> fastmax_quad32_mfma.hip, quad32_bwd_supported -> fastmax_quad32_bwd.hip (32-wide tiles);
