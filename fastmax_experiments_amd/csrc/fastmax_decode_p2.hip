@@ -1,0 +1,388 @@
+// Decode-time state cache for SECOND-order fastmax (opt-in, the p = 2 partner of fastmax_decode.hip).
+//
+// With a = 1/nt and f(x) = 1 + x + x^2/2 = ((1 + x)^2 + 1) / 2, masked p = 2 fastmax at the last position of a sequence is
+//     o = sum_n f(a q.k_n) v_n / sum_n f(a q.k_n).
+// Write k~ = [1, k] (D+1 entries), v' = [v, 1] and q~ = [1, a q].  Then (1 + a q.k)^2 = sum_{m,l} q~_m q~_l k~_m k~_l, so the
+// per-(b, kv-head) carried state is the symmetric third-order tensor
+//     S~[(m,l)][j] = sum_n k~_m k~_l v'_j        (m <= l over the D+1 indices of k~; j over the D+1 of v')
+// and a new token is read out as
+//     F_j = sum_{m<=l} w q~_m q~_l S~[(m,l)][j] + S~[(0,0)][j]     (w = 2 off the diagonal, 1 on it)
+//     o   = F_{:D} / F_D                                           (F is twice the numerator / denominator; the 2 cancels).
+// S~ holds the count (S~[(0,0)][D]), S1 = sum v, ksum, S2 = sum k v^T, K2 = sum k k^T and the third-order sum: everything
+// the p = 2 polynomial needs.  The count is an fp32 sum of ones: exact up to 2^24 tokens per sequence.
+//
+// State layout (float32), per (b, kv-head), P = (D+1)(D+2)/2 pair rows of DV = round_up(D+1, 4) floats (16-byte rows):
+//     row(m,l) = m (D+1) - m (m-1) / 2 + (l - m),   row[j] = S~[(m,l)][j] for j <= D, 0 for D < j < DV.
+// After the B*Hkv records sits the step's reduction scratch: STEP_SLOTS rows of DV floats per (b, kv-head).
+// Sizes per kv head: D = 64 -> 2145 x 68 floats (0.58 MB), D = 128 -> 8385 x 132 (4.4 MB).
+//
+// The state depends on k and v only, so it is kept per KV head: grouped-query attention (H = q_per_kv * Hkv query heads,
+// query head h reads kv head h / q_per_kv) reads each pair row once for all q_per_kv query heads of the group.
+//
+// Kernels
+//   p2_prefill_state_kernel   S~ of a whole prompt as one GEMM per (b, kv-head): (pair rows x tokens) . (tokens x (D+1)),
+//                             the pair products k~_m k~_l formed on the fly from an LDS image of k~, on the matrix cores
+//                             (16x16x32 bf16, fp32 accumulation).  The pair product is split into bf16 hi + lo (exact for
+//                             bf16 / f16 inputs), and so is v' for f32 / f16 inputs (bf16 v' is exact as it is).  Each
+//                             workgroup owns 128 (D <= 64) or 256 pair rows over ALL tokens, so no cross-workgroup sum is
+//                             needed: the pair dimension alone gives 17 (D = 64) to 33 (D = 128) workgroups per head.
+//   p2_decode_step_kernel     one token: every pair row read once (16-byte loads), updated by k~_m k~_l v'_j, written back,
+//                             and its contribution to F accumulated for the group's query heads; G workgroups per
+//                             (b, kv-head) each write their partial F to the scratch slab.
+//   p2_decode_finalize_kernel per (b, query head): S~[(0,0)] + the G partials in a fixed order, divide, store o in out_dtype.
+// No float atomics and no data handed between workgroups of one launch: bitwise reproducible run to run.
+#include "fastmax_mfma_common.h"
+
+#include <algorithm>
+
+namespace fastmax {
+namespace p2dec {
+
+constexpr int STEP_SLOTS = 256;   // partial-F rows per (b, kv-head) in the scratch slab: G * q_per_kv <= STEP_SLOTS
+constexpr int STEP_RMIN = 32;     // at least this many pair rows per step workgroup
+constexpr int QCMAX = 8;          // query heads accumulated in registers per pass over the rows
+constexpr int PF_KT = 32;         // tokens per MFMA k-step
+
+__host__ __device__ __forceinline__ int ncols(int D) { return (D + 4) & ~3; }               // round_up(D + 1, 4)
+__host__ __device__ __forceinline__ int npairs(int D) { return (D + 1) * (D + 2) / 2; }
+__device__ __forceinline__ int row_start(int m, int D1) { return m * D1 - m * (m - 1) / 2; }
+
+// pair row r -> (m, l)
+__device__ __forceinline__ void decode_row(int r, int D, int& m, int& l) {
+    const int D1 = D + 1;
+    m = 0;
+    while (m < D && row_start(m + 1, D1) <= r) ++m;
+    l = m + (r - row_start(m, D1));
+}
+
+template <typename T> __device__ __forceinline__ float ld(const void* base, int64_t idx) {
+    return to_float(reinterpret_cast<const T*>(base)[idx]);
+}
+
+// ---- prefill: S~ over the whole prompt ------------------------------------------------------------------------------
+// grid (ceil(P / (64 RT)), B * Hkv), 256 threads; each wave owns RT 16-row tiles of pair rows.  JT = MFMA column tiles
+// (16 JT > D + 1, so column 16 JT - 1 is always 0).  With `vec` (rows of whole 16-byte pieces, 16-byte aligned) the next
+// k-step's K and V pieces are loaded into registers while the matrix cores work on this one; otherwise element loads.
+template <typename T, int JT, int RT>
+__global__ __launch_bounds__(256) void p2_prefill_state_kernel(const void* k, const void* v, Strides3 ks, Strides3 vs,
+                                                               float* state, int Hkv, int N, int D, int vec) {
+    constexpr int DVJ = 16 * JT;
+    constexpr int KS = PF_KT + 4;                                 // fp32 row stride of the transposed k~ image
+    constexpr int VS = PF_KT + 8;                                 // bf16 row stride of the transposed v' images (80 bytes)
+    constexpr int NPV = std::is_same<T, bf16_t>::value ? 1 : 2;   // v' parts: bf16 is exact, f32 / f16 are split
+    constexpr int EPC = InTraits<T>::EPL;                         // elements per 16-byte piece
+    constexpr int NS = (PF_KT * ((DVJ - 16) / EPC) + 255) / 256;  // pieces per thread and tensor at the largest D
+    __shared__ __attribute__((aligned(16))) float kt[DVJ][KS];    // kt[c][t] = k~_c of token t
+    __shared__ __attribute__((aligned(16))) __bf16 vt[NPV][DVJ][VS];   // vt[p][j][t] = part p of v'_j of token t
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bkv = blockIdx.y, b = bkv / Hkv, h = bkv % Hkv;
+    const int P = npairs(D), DV = ncols(D), CPR = D / EPC;
+    const T* kb = row_ptr<T>(k, ks.sb, ks.sh, ks.sn, b, h, 0);
+    const T* vb = row_ptr<T>(v, vs.sb, vs.sh, vs.sn, b, h, 0);
+
+    // columns past D stay zero for the whole kernel
+    for (int idx = tid; idx < (DVJ - D - 1) * PF_KT; idx += 256) {
+        const int c = D + 1 + idx / PF_KT, t = idx % PF_KT;
+        kt[c][t] = 0.f;
+#pragma unroll
+        for (int p = 0; p < NPV; ++p) vt[p][c][t] = (__bf16)0.f;
+    }
+    // this lane's A rows: pair (m, l) of row tile rt; rows past P read the all-zero column DVJ - 1
+    int am[RT], al[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int r = blockIdx.x * (64 * RT) + wave * (16 * RT) + rt * 16 + (lane & 15);
+        if (r < P) decode_row(r, D, am[rt], al[rt]);
+        else am[rt] = al[rt] = DVJ - 1;
+    }
+    const int q8 = 8 * (lane >> 4);
+    f32x4 acc[RT][JT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) acc[rt][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    u32x4 rk[NS], rv[NS];
+    auto fetch = [&](int t0) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int idx = tid + 256 * s, t = idx / CPR, c = idx - t * CPR;
+            const bool ok = t < PF_KT && t0 + t < N;
+            rk[s] = ok ? *reinterpret_cast<const u32x4*>(kb + (int64_t)(t0 + t) * ks.sn + c * EPC) : u32x4{0, 0, 0, 0};
+            rv[s] = ok ? *reinterpret_cast<const u32x4*>(vb + (int64_t)(t0 + t) * vs.sn + c * EPC) : u32x4{0, 0, 0, 0};
+        }
+    };
+    if (vec) fetch(0);
+    for (int t0 = 0; t0 < N; t0 += PF_KT) {
+        __syncthreads();                                          // the previous step's fragments are read
+        if (vec) {
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int idx = tid + 256 * s, t = idx / CPR, c = idx - t * CPR;
+                if (t < PF_KT) {
+                    float xk[EPC], xv[EPC];
+                    piece_to_float<T>(rk[s], xk);
+                    piece_to_float<T>(rv[s], xv);
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) {
+                        kt[c * EPC + e + 1][t] = xk[e];
+                        const __bf16 hi = (__bf16)xv[e];
+                        vt[0][c * EPC + e][t] = hi;
+                        if constexpr (NPV == 2) vt[1][c * EPC + e][t] = (__bf16)(xv[e] - (float)hi);
+                    }
+                }
+            }
+            if (t0 + PF_KT < N) fetch(t0 + PF_KT);                // in flight during this step's matrix work
+        } else {
+            for (int idx = tid; idx < PF_KT * D; idx += 256) {
+                const int t = idx / D, d = idx - t * D;
+                const bool ok = t0 + t < N;
+                const float kx = ok ? ld<T>(kb, (int64_t)(t0 + t) * ks.sn + d) : 0.f;
+                const float vx = ok ? ld<T>(vb, (int64_t)(t0 + t) * vs.sn + d) : 0.f;
+                kt[d + 1][t] = kx;
+                const __bf16 hi = (__bf16)vx;
+                vt[0][d][t] = hi;
+                if constexpr (NPV == 2) vt[1][d][t] = (__bf16)(vx - (float)hi);
+            }
+        }
+        if (tid < PF_KT) {
+            const float one = t0 + tid < N ? 1.f : 0.f;
+            kt[0][tid] = one;
+            vt[0][D][tid] = (__bf16)one;
+            if constexpr (NPV == 2) vt[1][D][tid] = (__bf16)0.f;
+        }
+        __syncthreads();
+        Frag<2> A[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const f32x4 m0 = *reinterpret_cast<const f32x4*>(&kt[am[rt]][q8]), m1 = *reinterpret_cast<const f32x4*>(&kt[am[rt]][q8 + 4]);
+            const f32x4 l0 = *reinterpret_cast<const f32x4*>(&kt[al[rt]][q8]), l1 = *reinterpret_cast<const f32x4*>(&kt[al[rt]][q8 + 4]);
+            bf16x4 h0, lo0, h1, lo1;
+            split4(m0 * l0, h0, lo0);
+            split4(m1 * l1, h1, lo1);
+            A[rt].p[0] = cat4(h0, h1);
+            A[rt].p[1] = cat4(lo0, lo1);
+        }
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            Frag<NPV> Bf;
+#pragma unroll
+            for (int p = 0; p < NPV; ++p) Bf.p[p] = *reinterpret_cast<const bf16x8*>(&vt[p][jt * 16 + (lane & 15)][q8]);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) acc[rt][jt] = mfma_parts<2, NPV>(A[rt], Bf, acc[rt][jt]);
+        }
+    }
+    // C[row 4 (lane >> 4) + e][column lane & 15] of each 16 x 16 tile
+    float* rec = state + (int64_t)bkv * P * DV;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        const int rbase = blockIdx.x * (64 * RT) + wave * (16 * RT) + rt * 16 + 4 * (lane >> 4);
+#pragma unroll
+        for (int jt = 0; jt < JT; ++jt) {
+            const int j = jt * 16 + (lane & 15);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (rbase + e < P && j < DV) rec[(int64_t)(rbase + e) * DV + j] = acc[rt][jt][e];
+        }
+    }
+}
+
+// ---- step: update every pair row with the new token and accumulate the group's partial F -----------------------------
+// grid (G, B * Hkv), 256 threads.  Thread (rs, j4) = (tid / J4, tid % J4) handles columns 4 j4 .. 4 j4 + 3 of the rows
+// r0 + rs, r0 + rs + RP, ... of this workgroup's range [r0, r1).
+template <typename T, int QC>
+__global__ __launch_bounds__(256) void p2_decode_step_kernel(const void* q, const void* k, const void* v, Strides3 qs, Strides3 ks,
+                                                             Strides3 vs, float* state, float* part, int Hkv, int qpk, int D,
+                                                             int G, float a) {
+    __shared__ __attribute__((aligned(16))) float kt[132], vq[132], qt[QCMAX][132], red[16][132];
+    const int tid = threadIdx.x, g = blockIdx.x, bkv = blockIdx.y, b = bkv / Hkv, hk = bkv % Hkv;
+    const int P = npairs(D), DV = ncols(D), J4 = DV / 4;
+    const int RP = min(256 / J4, 16), rs = tid / J4, j4 = tid - rs * J4;
+    const bool active = rs < RP;
+    const int r0 = (int)((int64_t)P * g / G), r1 = (int)((int64_t)P * (g + 1) / G);
+    float* rec = state + (int64_t)bkv * P * DV;
+    if (tid < DV) {
+        kt[tid] = tid == 0 ? 1.f : (tid <= D ? to_float(row_ptr<T>(k, ks.sb, ks.sh, ks.sn, b, hk, 0)[tid - 1]) : 0.f);
+        vq[tid] = tid < D ? to_float(row_ptr<T>(v, vs.sb, vs.sh, vs.sn, b, hk, 0)[tid]) : (tid == D ? 1.f : 0.f);
+    }
+    int m0 = 0, l0 = 0;
+    if (active && r0 + rs < r1) decode_row(r0 + rs, D, m0, l0);
+    for (int c0 = 0; c0 < qpk; c0 += QC) {
+        __syncthreads();
+        for (int idx = tid; idx < QC * DV; idx += 256) {
+            const int hh = idx / DV, c = idx - hh * DV;
+            float x = 0.f;
+            if (c0 + hh < qpk) {
+                if (c == 0) x = 1.f;
+                else if (c <= D) x = a * to_float(row_ptr<T>(q, qs.sb, qs.sh, qs.sn, b, hk * qpk + c0 + hh, 0)[c - 1]);
+            }
+            qt[hh][c] = x;
+        }
+        __syncthreads();
+        f32x4 acc[QC];
+#pragma unroll
+        for (int hh = 0; hh < QC; ++hh) acc[hh] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (active) {
+            const f32x4 vv = *reinterpret_cast<const f32x4*>(&vq[4 * j4]);
+            int m = m0, l = l0;
+            for (int r = r0 + rs; r < r1; r += RP) {
+                f32x4* rowp = reinterpret_cast<f32x4*>(rec + (int64_t)r * DV) + j4;
+                f32x4 s = *rowp;
+                if (c0 == 0) {
+                    const float kk = kt[m] * kt[l];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[e] = fmaf(kk, vv[e], s[e]);
+                    *rowp = s;
+                }
+                const float w = m == l ? 1.f : 2.f;
+#pragma unroll
+                for (int hh = 0; hh < QC; ++hh) {
+                    const float c = w * qt[hh][m] * qt[hh][l];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[hh][e] = fmaf(c, s[e], acc[hh][e]);
+                }
+                if (r + RP >= r1) break;                          // (past the last row m would run beyond D)
+                l += RP;
+                while (l > D) { ++m; l = l - (D + 1) + m; }      // (m, D + 1 + x) is (m + 1, m + 1 + x)
+            }
+        }
+        // fixed-order sum over the RP row groups, one query head at a time
+        const int nq = min(QC, qpk - c0);
+#pragma unroll
+        for (int hh = 0; hh < QC; ++hh) {
+            if (hh >= nq) break;
+            if (active) *reinterpret_cast<f32x4*>(&red[rs][4 * j4]) = acc[hh];
+            __syncthreads();
+            if (tid < DV) {
+                float f = 0.f;
+                for (int i = 0; i < RP; ++i) f += red[i][tid];
+                part[(((int64_t)bkv * G + g) * qpk + c0 + hh) * DV + tid] = f;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// grid (B * H), 256 threads
+__global__ __launch_bounds__(256) void p2_decode_finalize_kernel(const float* state, const float* part, void* o, int out_dtype,
+                                                                 int H, int Hkv, int qpk, int D, int G) {
+    __shared__ float den;
+    const int tid = threadIdx.x, bh = blockIdx.x, b = bh / H, h = bh % H, bkv = b * Hkv + h / qpk, i = h % qpk;
+    const int P = npairs(D), DV = ncols(D);
+    float f = 0.f;
+    if (tid <= D) {
+        f = state[(int64_t)bkv * P * DV + tid];                    // S~[(0,0)][j]
+        const float* pp = part + ((int64_t)bkv * G * qpk + i) * DV + tid;
+        const int64_t sg = (int64_t)qpk * DV;
+        int gg = 0;
+        for (; gg + 8 <= G; gg += 8) {                              // 8 loads in flight, then the adds in order
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = pp[(gg + u) * sg];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) f += x[u];
+        }
+        for (; gg < G; ++gg) f += pp[gg * sg];
+        if (tid == D) den = f;
+    }
+    __syncthreads();
+    if (tid < D) {
+        const float val = f / den;
+        const int64_t idx = (int64_t)bh * D + tid;
+        if (out_dtype == FASTMAX_F32) reinterpret_cast<float*>(o)[idx] = val;
+        else if (out_dtype == FASTMAX_BF16) reinterpret_cast<uint16_t*>(o)[idx] = f32_to_bf16_bits(val);
+        else reinterpret_cast<_Float16*>(o)[idx] = (_Float16)val;
+    }
+}
+
+// step workgroups per (b, kv-head): as many as the slab holds for this group size, at least STEP_RMIN rows each
+static int step_groups(int D, int qpk) {
+    const int by_rows = (npairs(D) + STEP_RMIN - 1) / STEP_RMIN;
+    return std::max(1, std::min(STEP_SLOTS / qpk, by_rows));
+}
+
+template <typename T>
+static int launch_prefill_t(const void* k, const void* v, Strides3 ks, Strides3 vs, float* state, int B, int Hkv, int N, int D,
+                            hipStream_t stream) {
+    const int es = (int)sizeof(T);
+    const int vec = (D * es) % 16 == 0 && (reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 == 0 &&
+                    (ks.sb * es | ks.sh * es | ks.sn * es | vs.sb * es | vs.sh * es | vs.sn * es) % 16 == 0;
+    const int P = npairs(D);
+    if (D <= 64)
+        hipLaunchKernelGGL((p2_prefill_state_kernel<T, 5, 2>), dim3((P + 127) / 128, B * Hkv), dim3(256), 0, stream, k, v, ks, vs,
+                           state, Hkv, N, D, vec);
+    else
+        hipLaunchKernelGGL((p2_prefill_state_kernel<T, 9, 4>), dim3((P + 255) / 256, B * Hkv), dim3(256), 0, stream, k, v, ks, vs,
+                           state, Hkv, N, D, vec);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_step_t(const void* q, const void* k, const void* v, Strides3 qs, Strides3 ks, Strides3 vs, float* state,
+                         void* o, int out_dtype, int B, int H, int Hkv, int D, float a, hipStream_t stream) {
+    const int qpk = H / Hkv, G = step_groups(D, qpk);
+    float* part = state + (size_t)B * Hkv * npairs(D) * ncols(D);
+    const dim3 grid(G, B * Hkv);
+    if (qpk == 1)
+        hipLaunchKernelGGL((p2_decode_step_kernel<T, 1>), grid, dim3(256), 0, stream, q, k, v, qs, ks, vs, state, part, Hkv, qpk, D, G, a);
+    else if (qpk == 2)
+        hipLaunchKernelGGL((p2_decode_step_kernel<T, 2>), grid, dim3(256), 0, stream, q, k, v, qs, ks, vs, state, part, Hkv, qpk, D, G, a);
+    else if (qpk <= 4)
+        hipLaunchKernelGGL((p2_decode_step_kernel<T, 4>), grid, dim3(256), 0, stream, q, k, v, qs, ks, vs, state, part, Hkv, qpk, D, G, a);
+    else
+        hipLaunchKernelGGL((p2_decode_step_kernel<T, QCMAX>), grid, dim3(256), 0, stream, q, k, v, qs, ks, vs, state, part, Hkv, qpk,
+                           D, G, a);
+    hipLaunchKernelGGL(p2_decode_finalize_kernel, dim3(B * H), dim3(256), 0, stream, state, part, o, out_dtype, H, Hkv, qpk, D, G);
+    return (int)hipGetLastError();
+}
+
+}  // namespace p2dec
+}  // namespace fastmax
+
+using namespace fastmax;
+using namespace fastmax::p2dec;
+
+extern "C" {
+
+size_t fastmax_hip_p2_decode_state_bytes(int B, int Hkv, int D) {
+    if (B <= 0 || Hkv <= 0 || D <= 0 || D > 128) return 0;
+    return sizeof(float) * (size_t)B * Hkv * ((size_t)npairs(D) + STEP_SLOTS) * ncols(D);
+}
+
+int fastmax_hip_p2_prefill_state(const fastmax_problem* prob, const void* k, const int64_t* k_strides, const void* v,
+                                 const int64_t* v_strides, float* state, void* stream) {
+    if (!prob || !k || !v || !state || !k_strides || !v_strides) return FASTMAX_E_NULL;
+    if (prob->p != 2 || !prob->causal) return FASTMAX_E_BAD_P;
+    if (prob->B <= 0 || prob->H <= 0 || prob->Nk <= 0 || prob->Nq != prob->Nk || prob->D <= 0 || prob->D > 128 ||
+        (int64_t)prob->B * prob->H > 65535)
+        return FASTMAX_E_BAD_SHAPE;
+    const Strides3 ks{k_strides[0], k_strides[1], k_strides[2]}, vs{v_strides[0], v_strides[1], v_strides[2]};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (prob->in_dtype) {
+        case FASTMAX_F32: return launch_prefill_t<float>(k, v, ks, vs, state, prob->B, prob->H, prob->Nk, prob->D, st);
+        case FASTMAX_BF16: return launch_prefill_t<bf16_t>(k, v, ks, vs, state, prob->B, prob->H, prob->Nk, prob->D, st);
+        case FASTMAX_F16: return launch_prefill_t<f16_t>(k, v, ks, vs, state, prob->B, prob->H, prob->Nk, prob->D, st);
+    }
+    return FASTMAX_E_BAD_DTYPE;
+}
+
+int fastmax_hip_p2_decode_step(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                               const int64_t* v_strides, float* state, void* o, int B, int H, int Hkv, int D, int in_dtype,
+                               int out_dtype, float a, void* stream) {
+    if (!q || !k || !v || !state || !o || !q_strides || !k_strides || !v_strides) return FASTMAX_E_NULL;
+    if (B <= 0 || H <= 0 || Hkv <= 0 || D <= 0 || D > 128 || H % Hkv != 0 || H / Hkv > STEP_SLOTS ||
+        (int64_t)B * Hkv > 65535 || (int64_t)B * H > (int64_t)0x7fffffff)
+        return FASTMAX_E_BAD_SHAPE;
+    if (out_dtype < FASTMAX_F32 || out_dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
+    const Strides3 qs{q_strides[0], q_strides[1], q_strides[2]}, ks{k_strides[0], k_strides[1], k_strides[2]},
+        vs{v_strides[0], v_strides[1], v_strides[2]};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (in_dtype) {
+        case FASTMAX_F32: return launch_step_t<float>(q, k, v, qs, ks, vs, state, o, out_dtype, B, H, Hkv, D, a, st);
+        case FASTMAX_BF16: return launch_step_t<bf16_t>(q, k, v, qs, ks, vs, state, o, out_dtype, B, H, Hkv, D, a, st);
+        case FASTMAX_F16: return launch_step_t<f16_t>(q, k, v, qs, ks, vs, state, o, out_dtype, B, H, Hkv, D, a, st);
+    }
+    return FASTMAX_E_BAD_DTYPE;
+}
+
+}  // extern "C"

@@ -1,11 +1,18 @@
-"""Opt-in decode-time state cache for first-order fastmax.
+"""Opt-in decode-time state caches for fastmax: first order (p=1) and second order (p=2).
 
 The reference generates with a zero-padded KV cache and re-runs UNMASKED attention over the whole cache for every
 new token (lit_gpt/model.py:427-430, 464-466; generate/base.py:85-92): O(N D) per token and, by quirk Q4, not the
-same function as masked attention over the real sequence.  Here the carried state (S2 = sum k v^T, S1 = sum v,
-ksum = sum k, count) lives in HBM: `prefill` builds it from the prompt, `step` costs O(D^2) per token and returns
-masked p=1 fastmax at the new last position.  Because it changes the decode semantics it is a separate class, not
-a silent replacement of `fastmax(mask=False)`.
+same function as masked attention over the real sequence.  Here a carried state lives in HBM: `prefill` builds it from
+the prompt and `step` returns masked fastmax at the new last position for a fixed cost per token.  Because it changes
+the decode semantics it is a separate class, not a silent replacement of `fastmax(mask=False)`.
+
+  p=1  state (S2 = sum k v^T, S1 = sum v, ksum = sum k, count) per head; O(D^2) per token (csrc/fastmax_decode.hip).
+  p=2  the model's `fastmax(q, k, v, p=2)` (attention_block.py).  With k~ = [1, k] and v' = [v, 1] the state is
+       S~[(m,l)][j] = sum_n k~_m k~_l v'_j over the pairs m <= l, (D+1)(D+2)/2 rows of D+1 floats (0.58 MB per head at
+       D = 64, 4.4 MB at D = 128); O(D^3) per token (csrc/fastmax_decode_p2.hip).  It depends on K and V only, so it
+       is kept per KV head: with grouped-query attention (`n_query_groups` < H) one pass over a group's state serves
+       its H / n_query_groups query heads.  The token count inside the state is an fp32 sum of ones: exact up to 2^24
+       tokens.  The prompt's own outputs come from the masked p=2 forward (`fastmax(..., mask=True, p=2)`).
 """
 import ctypes
 import math
@@ -17,7 +24,15 @@ from .attention_mechanisms.fastmax import fastmax
 
 
 class FastmaxDecodeState:
-    def __init__(self, B, H, D, device, normalize_term=8, tensors_normalized=False):
+    def __init__(self, B, H, D, device, normalize_term=8, tensors_normalized=False, p=1, n_query_groups=None):
+        if p not in (1, 2):
+            raise ValueError(f"p should be 1 or 2, got p={p}")
+        if p == 2:
+            self._init_p2(B, H, D, device, normalize_term, tensors_normalized, n_query_groups)
+            return
+        if n_query_groups not in (None, H):
+            raise ValueError("the first-order decode state has one record per head: n_query_groups must be None or H")
+        self.p = 1
         self.B, self.H, self.D = B, H, D
         self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
         self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
@@ -27,8 +42,25 @@ class FastmaxDecodeState:
         self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
         self.count = 0
 
+    def _init_p2(self, B, H, D, device, normalize_term, tensors_normalized, n_query_groups):
+        Hkv = H if n_query_groups is None else n_query_groups
+        if Hkv <= 0 or H % Hkv != 0:
+            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+        self.p = 2
+        self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
+        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
+        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
+        nbytes = _lib.lib().fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
+        if nbytes == 0:
+            raise NotImplementedError(f"head size {D} not supported")
+        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+        self.count = 0
+
     def prefill(self, q, k, v):
-        """Masked p=1 forward over the prompt; also captures the end-of-prompt state.  Returns o (B,H,N,D)."""
+        """Masked forward over the prompt; also captures the end-of-prompt state.  Returns o (B,H,N,D).
+        p=2: q (B,H,N,D), k and v (B,n_query_groups,N,D)."""
+        if self.p == 2:
+            return self._prefill_p2(q, k, v)
         assert self.count == 0, "prefill starts a sequence"
         L = _lib.lib()
         o = fastmax(q, k, v, mask=True, p=1, **self._kw)
@@ -42,7 +74,10 @@ class FastmaxDecodeState:
         return o
 
     def step(self, q, k, v):
-        """q,k,v: (B,H,1,D) of the new token -> o (B,H,1,D); O(D^2) per head."""
+        """q,k,v: (B,H,1,D) of the new token -> o (B,H,1,D); O(D^2) per head.
+        p=2: k and v are (B,n_query_groups,1,D); O(D^3) per KV head."""
+        if self.p == 2:
+            return self._step_p2(q, k, v)
         L = _lib.lib()
         qd, kd, vd = (ops._prep(t, t.device) for t in (q, k, v))
         self.count += 1
@@ -53,4 +88,46 @@ class FastmaxDecodeState:
                                               ops._strides(vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.D,
                                               dt, dt, 1.0 / self.nt, self.count, ops._stream(q.device))
         _lib.check(rc, "fastmax_hip_p1_decode_step")
+        return o
+
+    def _check_p2_shapes(self, q, k, n):
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        if tuple(q.shape) != (B, H, n, D) or tuple(k.shape) != (B, Hkv, n, D):
+            raise ValueError(f"expected q {(B, H, n, D)} and k, v {(B, Hkv, n, D)}, got {tuple(q.shape)} and {tuple(k.shape)}")
+
+    def _prefill_p2(self, q, k, v):
+        assert self.count == 0, "prefill starts a sequence"
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        T = q.shape[2]
+        self._check_p2_shapes(q, k, T)
+        if Hkv == H:
+            o = fastmax(q, k, v, mask=True, p=2, **self._kw)
+        else:
+            # each group's query heads as the heads of one batch entry, its K and V as stride-0 views over them
+            r = H // Hkv
+            qg = q.reshape(B * Hkv, r, T, D)
+            kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
+            o = fastmax(qg, kg, vg, mask=True, p=2, **self._kw).reshape(B, H, T, D)
+        L = _lib.lib()
+        kd, vd = ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device)
+        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, 2, True, self.nt, 0.0)
+        with torch.cuda.device(kd.device):
+            rc = L.fastmax_hip_p2_prefill_state(ctypes.byref(prob), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
+                                                ops._strides(vd), self.state.data_ptr(), ops._stream(kd.device))
+        _lib.check(rc, "fastmax_hip_p2_prefill_state")
+        self.count = T
+        return o
+
+    def _step_p2(self, q, k, v):
+        self._check_p2_shapes(q, k, 1)
+        L = _lib.lib()
+        qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
+        o = torch.empty((self.B, self.H, 1, self.D), dtype=q.dtype, device=q.device)
+        dt = ops._DT[q.dtype]
+        with torch.cuda.device(q.device):
+            rc = L.fastmax_hip_p2_decode_step(qd.data_ptr(), ops._strides(qd), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
+                                              ops._strides(vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.Hkv,
+                                              self.D, dt, dt, 1.0 / self.nt, ops._stream(q.device))
+        _lib.check(rc, "fastmax_hip_p2_decode_step")
+        self.count += 1
         return o

@@ -274,6 +274,27 @@ int fastmax_hip_p1_decode_step(const void* q, const int64_t* q_strides, const vo
                                int B, int H, int D, int in_dtype, int out_dtype, float a, int64_t count_after,
                                void* stream);
 
+/* ---- second-order (p = 2) decode state cache (opt-in, csrc/fastmax_decode_p2.hip): a fixed-size state and a fixed cost per
+ *      generated token for the model's `fastmax(q, k, v, p=2)` instead of the unmasked recompute over the whole KV cache.
+ *      With k~ = [1, k], v' = [v, 1], the state of each (b, KV head) is S~[(m,l)][j] = sum_n k~_m k~_l v'_j over the pairs
+ *      m <= l of the D+1 indices of k~, float32, (D+1)(D+2)/2 rows of round_up(D+1, 4) floats (D = 64: 0.58 MB,
+ *      D = 128: 4.4 MB per KV head), followed by the step's reduction scratch.  The count S~[(0,0)][D] is an fp32 sum of ones:
+ *      exact up to 2^24 tokens.
+ *      p2_decode_state_bytes: bytes of the whole buffer (state + scratch) for B x Hkv KV heads; 0 when D <= 0, D > 128,
+ *                     B <= 0 or Hkv <= 0.
+ *      p2_prefill_state: the state of a whole prompt (k, v: (B,Hkv,N,D)); prob->p = 2, prob->causal = 1, prob->H = Hkv,
+ *                     Nq = Nk = N.  Overwrites the state.
+ *      p2_decode_step: q (B,H,1,D), k, v (B,Hkv,1,D) of ONE new token; H % Hkv == 0 (query head h reads KV head
+ *                     h / (H / Hkv)), H / Hkv <= 256.  Updates the state in place and writes o (B,H,1,D) in out_dtype =
+ *                     masked second-order fastmax at the new last position (a = 1/nt).  Not the reference's decode arithmetic
+ *                     (quirk Q4).  Bitwise reproducible: no float atomics. */
+size_t fastmax_hip_p2_decode_state_bytes(int B, int Hkv, int D);
+int fastmax_hip_p2_prefill_state(const fastmax_problem* prob, const void* k, const int64_t* k_strides,
+                                 const void* v, const int64_t* v_strides, float* state, void* stream);
+int fastmax_hip_p2_decode_step(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides,
+                               const void* v, const int64_t* v_strides, float* state, void* o,
+                               int B, int H, int Hkv, int D, int in_dtype, int out_dtype, float a, void* stream);
+
 /* ---- QLoRA linear: frozen NF4 base weight + LoRA branch, fused (csrc/nf4_lora.hip).
  *      Replaces the bitsandbytes Linear4bit matmul + the low-rank branch of
  *      lit_gpt/lora.py:170-177 (LoRALinear.forward) and :398-433 (LoRAQKVLinear.forward):

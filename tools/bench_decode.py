@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generation-time shapes: N_q new tokens against N_k cached keys (unmasked, lit_gpt/model.py:464-466), and the opt-in
-decode state cache.  Markdown to stdout."""
+decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-order rows only."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,6 +21,65 @@ def timeit(fn, iters=20, rounds=5):
     return statistics.median(ts)
 
 
+import ctypes
+from fastmax_experiments_amd import _lib, ops
+
+
+def bench_p2():
+    """Second-order decode state cache (FastmaxDecodeState(p=2)): step time rotating over enough independent states (one per
+    layer of a 22-layer model, more when that is under 512 MiB) that the step streams HBM and not the 256 MiB Infinity Cache,
+    beside the unmasked p=2 call over a 4096-token KV cache it replaces; prefill-state kernel beside the masked p=2 forward.
+    Event times include the host side of each call: take kernel times from a rocprofv3 --kernel-trace --stats run."""
+    print("| p=2 case | (B,H,Hkv,D) | states | state MB | bytes/step MB | ms/step | TB/s |")
+    print("|---|---|---|---|---|---|---|")
+    for B, H, Hkv, D in ((1, 32, 32, 64), (1, 32, 32, 128), (8, 32, 32, 64), (1, 32, 4, 64)):
+        L = _lib.lib()
+        sb = B * Hkv * (D + 1) * (D + 2) // 2 * ((D + 4) // 4 * 4) * 4           # the state proper (scratch excluded)
+        full = L.fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
+        n = max(22, -(-(512 << 20) // full))
+        states = [FastmaxDecodeState(B, H, D, device="cuda", p=2, n_query_groups=Hkv) for _ in range(n)]
+        q, k, v = (torch.randn(B, h, 64, D, device="cuda").to(torch.bfloat16) for h in (H, Hkv, Hkv))
+        for st in states:
+            st.prefill(q, k, v)
+        q1 = torch.randn(B, H, 1, D, device="cuda").to(torch.bfloat16)
+        k1, v1 = (torch.randn(B, Hkv, 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+
+        def steps():
+            for st in states:
+                st.step(q1, k1, v1)
+        with torch.no_grad():
+            ms = timeit(steps, iters=2, rounds=5) / n
+        print(f"| decode state cache step | ({B},{H},{Hkv},{D}) | {n} | {sb / 1e6:.2f} | {2 * sb / 1e6:.2f} | {ms:.4f} | "
+              f"{2 * sb / (ms * 1e-3) / 1e12:.2f} |", flush=True)
+        del states
+        qc = torch.randn(B, H, 1, D, device="cuda").to(torch.bfloat16)
+        kc, vc = (torch.randn(B, H, 4096, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+        with torch.no_grad():
+            ms = timeit(lambda: fastmax(qc, kc, vc, mask=False, p=2))
+        print(f"| unmasked over a 4096-token KV cache | ({B},{H},{H},{D}) | | | | {ms:.4f} | |", flush=True)
+    print()
+    print("| p=2 prefill | (B,H,N,D) | ms |")
+    print("|---|---|---|")
+    for B, H, N, D in ((1, 32, 4096, 64), (1, 32, 4096, 128)):
+        q, k, v = (torch.randn(B, H, N, D, device="cuda").to(torch.bfloat16) for _ in range(3))
+        st = FastmaxDecodeState(B, H, D, device="cuda", p=2)
+        prob = ops._problem(k, k, k.dtype, k.dtype, 2, True, st.nt, 0.0)
+        L = _lib.lib()
+
+        def prefill_state():
+            _lib.check(L.fastmax_hip_p2_prefill_state(ctypes.byref(prob), k.data_ptr(), ops._strides(k), v.data_ptr(),
+                                                      ops._strides(v), st.state.data_ptr(), ops._stream(k.device)), "prefill")
+        with torch.no_grad():
+            ms_s = timeit(prefill_state)
+            ms_f = timeit(lambda: fastmax(q, k, v, mask=True, p=2))
+        print(f"| prefill-state kernel | ({B},{H},{N},{D}) | {ms_s:.4f} |", flush=True)
+        print(f"| masked p=2 forward | ({B},{H},{N},{D}) | {ms_f:.4f} |", flush=True)
+
+
+if "--p2" in sys.argv:          # the second-order rows only (for a profiler run)
+    bench_p2()
+    sys.exit(0)
+
 print("| case | (B,H,Nq,Nk,D) | dtype | p | ms |")
 print("|---|---|---|---|---|")
 for B, H, Nq, Nk, D, dt, p in ((1, 32, 1, 4096, 64, torch.bfloat16, 2), (1, 32, 1, 4096, 128, torch.bfloat16, 2), (8, 32, 1, 4096, 64, torch.bfloat16, 2),
@@ -38,6 +97,10 @@ for B, H, T, D in ((1, 32, 4096, 64), (1, 32, 16384, 128), (8, 32, 4096, 64)):
     with torch.no_grad():
         ms = timeit(lambda: st.step(q1, k1, v1))
     print(f"| decode state cache step (p=1, opt-in) | ({B},{H},1,{T},{D}) | bfloat16 | 1 | {ms:.4f} |", flush=True)
+
+print()
+bench_p2()
+print()
 
 # the frozen 4-bit linear at generation-size row counts (merged weights: no LoRA branch), eager and as a HIP graph replay
 from fastmax_experiments_amd import lora
