@@ -22,6 +22,7 @@ SYMBOLS = ["fastmax_hip_forward_workspace", "fastmax_hip_forward", "fastmax_hip_
            "fastmax_hip_abi_version", "fastmax_hip_select_path", "fastmax_hip_error_string",
            "fastmax_hip_decode_state_bytes", "fastmax_hip_p1_prefill_state", "fastmax_hip_p1_decode_step",
            "fastmax_hip_p2_decode_state_bytes", "fastmax_hip_p2_prefill_state", "fastmax_hip_p2_decode_step",
+           "fastmax_hip_p2_extend_workspace", "fastmax_hip_p2_extend",
            "fastmax_hip_normalize_stats", "fastmax_hip_normalize_cast", "fastmax_hip_normalize_backward_workspace",
            "fastmax_hip_normalize_backward", "fastmax_hip_rope_qkv_split", "fastmax_hip_rope_qkv_split_backward", "fastmax_hip_cross_entropy_forward", "fastmax_hip_cross_entropy_backward",
            "fastmax_hip_linearmax_forward", "fastmax_hip_linearmax_forward_auto", "fastmax_hip_linearmax_forward_auto_workspace",
@@ -128,6 +129,10 @@ def lib():
     L.fastmax_hip_p2_prefill_state.restype = ci
     L.fastmax_hip_p2_decode_step.argtypes = [vp, i64p, vp, i64p, vp, i64p, fp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
     L.fastmax_hip_p2_decode_step.restype = ci
+    L.fastmax_hip_p2_extend_workspace.argtypes = [ci, ci, ci, ci, ci]
+    L.fastmax_hip_p2_extend_workspace.restype = sz
+    L.fastmax_hip_p2_extend.argtypes = [pp, ci, vp, i64p, vp, i64p, vp, i64p, fp, vp, vp, sz, vp]
+    L.fastmax_hip_p2_extend.restype = ci
     L.fastmax_hip_nf4_linear_forward.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
     L.fastmax_hip_nf4_linear_forward.restype = ci
     L.fastmax_hip_nf4_linear_backward_input.argtypes = [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]

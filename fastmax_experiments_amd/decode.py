@@ -13,6 +13,11 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
        is kept per KV head: with grouped-query attention (`n_query_groups` < H) one pass over a group's state serves
        its H / n_query_groups query heads.  The token count inside the state is an fp32 sum of ones: exact up to 2^24
        tokens.  The prompt's own outputs come from the masked p=2 forward (`fastmax(..., mask=True, p=2)`).
+       `extend` continues a state of any length by T >= 1 tokens at once (a second turn, a block of draft tokens, a long
+       prompt in pieces): the cached tokens are read out of the state for all T queries in one matrix-core pass, the
+       chunk's own masked part comes from the p=2 tile kernels, and the state is then advanced by the T tokens: about
+       three passes over the state instead of the 2 T of T single steps.  `prefill(..., chunk=C)` feeds a prompt as
+       `extend` calls of C tokens: masked p=2 attention in time linear in N (forward only).
 """
 import ctypes
 import math
@@ -56,9 +61,21 @@ class FastmaxDecodeState:
         self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
         self.count = 0
 
-    def prefill(self, q, k, v):
+    def prefill(self, q, k, v, chunk=None):
         """Masked forward over the prompt; also captures the end-of-prompt state.  Returns o (B,H,N,D).
-        p=2: q (B,H,N,D), k and v (B,n_query_groups,N,D)."""
+        p=2: q (B,H,N,D), k and v (B,n_query_groups,N,D).  With `chunk=C` (p=2) the prompt is fed as `extend` calls of C
+        tokens, the last one shorter: linear in N, where the default runs the quadratic tile kernels over the whole prompt."""
+        if chunk is not None:
+            if chunk <= 0:
+                raise ValueError(f"chunk should be a positive number of tokens, got chunk={chunk}")
+            if self.p != 2:
+                raise NotImplementedError("chunked prefill needs the second-order state cache (p=2)")
+            assert self.count == 0, "prefill starts a sequence"
+            self._check_p2_shapes(q, k, q.shape[2])
+            o = torch.empty((self.B, self.H, q.shape[2], self.D), dtype=q.dtype, device=q.device)
+            for s in range(0, q.shape[2], chunk):
+                o[:, :, s:s + chunk] = self.extend(q[:, :, s:s + chunk], k[:, :, s:s + chunk], v[:, :, s:s + chunk])
+            return o
         if self.p == 2:
             return self._prefill_p2(q, k, v)
         assert self.count == 0, "prefill starts a sequence"
@@ -88,6 +105,31 @@ class FastmaxDecodeState:
                                               ops._strides(vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.D,
                                               dt, dt, 1.0 / self.nt, self.count, ops._stream(q.device))
         _lib.check(rc, "fastmax_hip_p1_decode_step")
+        return o
+
+    def extend(self, q, k, v):
+        """p=2: T >= 1 new tokens after the `count` cached ones (any count, 0 included).  q (B,H,T,D), k and v
+        (B,n_query_groups,T,D) -> o (B,H,T,D) in q's dtype = masked p=2 fastmax at the T new positions over the cached and
+        the new tokens; the state advances by T tokens."""
+        if self.p != 2:
+            raise NotImplementedError("extend needs the second-order state cache (p=2): linearmax normalises q and k over the "
+                                      "whole sequence, which a carried first-order state cannot follow")
+        T = q.shape[2] if q.dim() == 4 else 0
+        if T < 1:
+            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        self._check_p2_shapes(q, k, T)
+        L = _lib.lib()
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
+        o = torch.empty((B, H, T, D), dtype=q.dtype, device=q.device)
+        prob = ops._problem(qd, kd, qd.dtype, qd.dtype, 2, True, self.nt, 0.0)
+        wsb, wsp = ops._ws(L.fastmax_hip_p2_extend_workspace(B, H, Hkv, T, D), q.device)
+        with torch.cuda.device(q.device):
+            rc = L.fastmax_hip_p2_extend(ctypes.byref(prob), Hkv, qd.data_ptr(), ops._strides(qd), kd.data_ptr(), ops._strides(kd),
+                                         vd.data_ptr(), ops._strides(vd), self.state.data_ptr(), o.data_ptr(), wsp,
+                                         wsb.numel() if wsb is not None else 0, ops._stream(q.device))
+        _lib.check(rc, "fastmax_hip_p2_extend")
+        self.count += T
         return o
 
     def _check_p2_shapes(self, q, k, n):

@@ -287,13 +287,32 @@ int fastmax_hip_p1_decode_step(const void* q, const int64_t* q_strides, const vo
  *      p2_decode_step: q (B,H,1,D), k, v (B,Hkv,1,D) of ONE new token; H % Hkv == 0 (query head h reads KV head
  *                     h / (H / Hkv)), H / Hkv <= 256.  Updates the state in place and writes o (B,H,1,D) in out_dtype =
  *                     masked second-order fastmax at the new last position (a = 1/nt).  Not the reference's decode arithmetic
- *                     (quirk Q4).  Bitwise reproducible: no float atomics. */
+ *                     (quirk Q4).  Bitwise reproducible: no float atomics.
+ *      p2_extend:     T >= 1 new tokens at once onto a state that holds any number (0 included: a zeroed state is an empty
+ *                     sequence) of cached tokens: chunked prefill, a second turn, a block of draft tokens.  prob: p = 2,
+ *                     causal = 1, B, H = QUERY heads, Nq = Nk = T, D <= 128, a = 1/nt, b = a^2/2, in / out dtypes; q (B,H,T,D),
+ *                     k, v (B,Hkv,T,D), H % Hkv == 0.  Writes o (B,H,T,D, contiguous) in out_dtype = masked second-order
+ *                     fastmax at the T new positions over the cached + the new tokens (one rounding: the chunk's own sums
+ *                     stay fp32 until the divide), then adds the T tokens to the state (S~ +=, fixed order).  The cached
+ *                     part is a (query rows x pair rows) . (pair rows x D+1) product on the matrix cores with the pair
+ *                     products w q~_m q~_l formed on the fly; all H / Hkv query heads of a group are rows of one product,
+ *                     and when B Hkv ceil(rows / 128) is small the pair dimension is split over workgroups whose partials
+ *                     are summed in a fixed order.  Bitwise reproducible: no float atomics.
+ *                     FASTMAX_E_BAD_P for p != 2 or causal = 0, FASTMAX_E_WORKSPACE when workspace is NULL or smaller than
+ *                     p2_extend_workspace says; every rejection happens before anything is launched.
+ *      p2_extend_workspace: bytes p2_extend needs (the chunk's fp32 sums, the read-out partials, the tile forward's own workspace);
+ *                     non-decreasing in T; 0 for arguments p2_extend rejects (B, H, Hkv, T <= 0, D <= 0, D > 128,
+ *                     H % Hkv != 0). */
 size_t fastmax_hip_p2_decode_state_bytes(int B, int Hkv, int D);
 int fastmax_hip_p2_prefill_state(const fastmax_problem* prob, const void* k, const int64_t* k_strides,
                                  const void* v, const int64_t* v_strides, float* state, void* stream);
 int fastmax_hip_p2_decode_step(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides,
                                const void* v, const int64_t* v_strides, float* state, void* o,
                                int B, int H, int Hkv, int D, int in_dtype, int out_dtype, float a, void* stream);
+size_t fastmax_hip_p2_extend_workspace(int B, int H, int Hkv, int T, int D);
+int fastmax_hip_p2_extend(const fastmax_problem* prob, int Hkv, const void* q, const int64_t* q_strides, const void* k,
+                          const int64_t* k_strides, const void* v, const int64_t* v_strides, float* state, void* o,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- QLoRA linear: frozen NF4 base weight + LoRA branch, fused (csrc/nf4_lora.hip).
  *      Replaces the bitsandbytes Linear4bit matmul + the low-rank branch of

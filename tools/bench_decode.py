@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Generation-time shapes: N_q new tokens against N_k cached keys (unmasked, lit_gpt/model.py:464-466), and the opt-in
-decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-order rows only."""
+decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-order rows only.
+`--extend`: multi-token continuation of the second-order cache (`extend`, `prefill(chunk=C)`), all rows, event times.
+`--extend-case B,H,Hkv,D,T` and `--prefill-case B,H,N,D,C` (C = 0: the one-shot prefill) run ONE row, for a
+`rocprofv3 --kernel-trace --stats` run whose per-kernel totals then belong to that row alone."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -76,6 +79,100 @@ def bench_p2():
         print(f"| masked p=2 forward | ({B},{H},{N},{D}) | {ms_f:.4f} |", flush=True)
 
 
+EXTEND_SHAPES = ((1, 32, 32, 64), (1, 32, 32, 128), (8, 32, 32, 64), (1, 32, 4, 64))
+PREFILL_CASES = ((1, 32, 4096, 64), (1, 32, 16384, 64), (1, 32, 32768, 64), (1, 32, 65536, 64), (1, 32, 4096, 128), (1, 32, 32768, 128))
+
+
+def _rotating_states(B, H, Hkv, D, cached=4096):
+    """enough independent states to exceed the Infinity Cache (as bench_p2), each holding `cached` tokens.  The state is
+    written by fastmax_hip_p2_prefill_state alone, so the setup launches none of the kernels that `extend` or `step` use."""
+    L = _lib.lib()
+    full = L.fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
+    n = max(22, -(-(512 << 20) // full))
+    k, v = (torch.randn(B, Hkv, cached, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+    first = FastmaxDecodeState(B, H, D, device="cuda", p=2, n_query_groups=Hkv)
+    prob = ops._problem(k, k, k.dtype, k.dtype, 2, True, first.nt, 0.0)
+    _lib.check(L.fastmax_hip_p2_prefill_state(ctypes.byref(prob), k.data_ptr(), ops._strides(k), v.data_ptr(), ops._strides(v),
+                                              first.state.data_ptr(), ops._stream(k.device)), "prefill")
+    states = [first]
+    for _ in range(n - 1):
+        st = FastmaxDecodeState(B, H, D, device="cuda", p=2, n_query_groups=Hkv)
+        st.state.copy_(first.state)
+        states.append(st)
+    for st in states:
+        st.count = cached
+    return states
+
+
+def extend_case(B, H, Hkv, D, T, rounds=3):
+    """-> (ms per extend(T), ms per T single steps, states, extend calls, step sequences); both rotate over the states"""
+    states = _rotating_states(B, H, Hkv, D)
+    n = len(states)
+    q = torch.randn(B, H, T, D, device="cuda").to(torch.bfloat16)
+    k, v = (torch.randn(B, Hkv, T, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+    q1, k1, v1 = q[:, :, :1].contiguous(), k[:, :, :1].contiguous(), v[:, :, :1].contiguous()
+
+    def extends():
+        for st in states:
+            st.extend(q, k, v)
+
+    def steps():
+        for i in range(T):
+            states[i % n].step(q1, k1, v1)
+    with torch.no_grad():
+        ms_e = timeit(extends, iters=1, rounds=rounds) / n
+        ms_s = timeit(steps, iters=1, rounds=rounds)
+    return ms_e, ms_s, n, n * (rounds + 1), rounds + 1
+
+
+def prefill_case(B, H, N, D, C, rounds=3):
+    """-> (ms per prefill, calls): C = 0 is the one-shot prefill (masked tiles + prefill-state kernel), else prefill(chunk=C)"""
+    q, k, v = (torch.randn(B, H, N, D, device="cuda").to(torch.bfloat16) for _ in range(3))
+    st = FastmaxDecodeState(B, H, D, device="cuda", p=2)
+
+    def run():
+        st.count = 0
+        st.state.zero_()
+        st.prefill(q, k, v, chunk=C or None)
+    with torch.no_grad():
+        return timeit(run, iters=1, rounds=rounds), rounds + 1
+
+
+def bench_extend():
+    """extend(T) onto 4096 cached tokens next to T single steps, then prefill(chunk=C) next to the one-shot prefill.
+    Event times (they include the host side of each call, and state.zero_() in the prefill rows)."""
+    print("| extend | (B,H,Hkv,D) | T | states | extend(T) ms | T steps ms | steps / extend |")
+    print("|---|---|---|---|---|---|---|")
+    for B, H, Hkv, D in EXTEND_SHAPES:
+        for T in (8, 64, 512):
+            ms_e, ms_s, n, _, _ = extend_case(B, H, Hkv, D, T)
+            print(f"| extend vs steps | ({B},{H},{Hkv},{D}) | {T} | {n} | {ms_e:.4f} | {ms_s:.4f} | {ms_s / ms_e:.1f} |", flush=True)
+    print()
+    print("| p=2 prefill | (B,H,N,D) | one-shot ms | chunk 1024 ms | chunk 2048 ms | chunk 4096 ms |")
+    print("|---|---|---|---|---|---|")
+    for B, H, N, D in PREFILL_CASES:
+        ms = [prefill_case(B, H, N, D, C)[0] for C in (0, 1024, 2048, 4096)]
+        print(f"| one-shot vs chunked | ({B},{H},{N},{D}) | " + " | ".join(f"{x:.3f}" for x in ms) + " |", flush=True)
+
+
+def _case_arg(flag):
+    return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
+
+
+if "--extend-case" in sys.argv:
+    B, H, Hkv, D, T = _case_arg("--extend-case")
+    ms_e, ms_s, n, ne, ns = extend_case(B, H, Hkv, D, T)
+    print(f"extend-case ({B},{H},{Hkv},{D}) T={T}: states={n} extend_calls={ne} step_sequences={ns} "
+          f"event ms: extend {ms_e:.4f}, {T} steps {ms_s:.4f}")
+    sys.exit(0)
+if "--prefill-case" in sys.argv:
+    B, H, N, D, C = _case_arg("--prefill-case")
+    ms, calls = prefill_case(B, H, N, D, C)
+    print(f"prefill-case ({B},{H},{N},{D}) chunk={C}: calls={calls} event ms {ms:.4f}")
+    sys.exit(0)
+if "--extend" in sys.argv:
+    bench_extend()
+    sys.exit(0)
 if "--p2" in sys.argv:          # the second-order rows only (for a profiler run)
     bench_p2()
     sys.exit(0)
