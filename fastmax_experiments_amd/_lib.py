@@ -13,30 +13,8 @@ LIB_PATH = os.environ.get("FASTMAX_LIB_PATH") or os.path.join(HERE, "libfastmax_
 F32, BF16, F16 = 0, 1, 2
 PATH_AUTO, PATH_QUADRATIC, PATH_RECURRENT, PATH_MFMA, PATH_QUADRATIC_MFMA = 0, 1, 2, 3, 4
 PATH_NAMES = {PATH_AUTO: "auto", PATH_QUADRATIC: "quadratic", PATH_RECURRENT: "recurrent", PATH_MFMA: "mfma", PATH_QUADRATIC_MFMA: "quadratic_mfma"}
-E_BAD_P = -1
-E_BAD_SHAPE = -2
-
-# every symbol include/fastmax_hip.h declares
-SYMBOLS = ["fastmax_hip_forward_workspace", "fastmax_hip_forward", "fastmax_hip_backward_workspace",
-           "fastmax_hip_backward", "fastmax_hip_normalize_workspace", "fastmax_hip_normalize",
-           "fastmax_hip_abi_version", "fastmax_hip_select_path", "fastmax_hip_error_string",
-           "fastmax_hip_decode_state_bytes", "fastmax_hip_p1_prefill_state", "fastmax_hip_p1_decode_step",
-           "fastmax_hip_p2_decode_state_bytes", "fastmax_hip_p2_prefill_state", "fastmax_hip_p2_decode_step",
-           "fastmax_hip_p2_extend_workspace", "fastmax_hip_p2_extend",
-           "fastmax_hip_normalize_stats", "fastmax_hip_normalize_cast", "fastmax_hip_normalize_backward_workspace",
-           "fastmax_hip_normalize_backward", "fastmax_hip_rope_qkv_split", "fastmax_hip_rope_qkv_split_backward", "fastmax_hip_cross_entropy_forward", "fastmax_hip_cross_entropy_backward",
-           "fastmax_hip_linearmax_forward", "fastmax_hip_linearmax_forward_auto", "fastmax_hip_linearmax_forward_auto_workspace",
-           "fastmax_hip_linearmax_backward", "fastmax_hip_linearmax_train_supported",
-           "fastmax_hip_nf4_linear_forward", "fastmax_hip_nf4_linear_backward_input", "fastmax_hip_nf4_dequantize",
-           "fastmax_hip_lora_down", "fastmax_hip_lora_tn_workspace", "fastmax_hip_lora_tn", "fastmax_hip_lora_up",
-           "fastmax_hip_forward_state_bytes", "fastmax_hip_backward_with_states",
-           "fastmax_hip_lora_scatter", "fastmax_hip_lora_scatter_backward",
-           "fastmax_hip_normalize_cast_expand", "fastmax_hip_normalize_backward_expand", "fastmax_hip_tune",
-           "fastmax_hip_nf4_linear_forward_s", "fastmax_hip_nf4_linear_backward_input_s", "fastmax_hip_nf4_dequantize_s",
-           "fastmax_hip_qlora_gemm", "fastmax_hip_nf4_dequantize_transposed",
-           "fastmax_hip_qlora_gemm_rope", "fastmax_hip_tune_get", "fastmax_hip_build_flags",
-           "fastmax_hip_normalize_stats2_workspace", "fastmax_hip_normalize_stats2",
-           "fastmax_hip_lora_down_dropout", "fastmax_hip_lora_tn_dropout", "fastmax_hip_lora_up_dropout", "fastmax_hip_lora_dropout_mask"]
+ABI_VERSION = 8
+OK, E_BAD_P, E_BAD_SHAPE, E_BAD_DTYPE, E_WORKSPACE, E_ALIGNMENT, E_NULL = 0, -1, -2, -3, -4, -5, -6      # enum fastmax_error
 
 
 class Problem(ctypes.Structure):
@@ -45,6 +23,75 @@ class Problem(ctypes.Structure):
                 ("causal", ctypes.c_int), ("a", ctypes.c_float), ("b", ctypes.c_float), ("g0", ctypes.c_float),
                 ("path", ctypes.c_int)]
 
+
+vp, sz, ci, i64, cf, cs = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p
+i64p, pp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Problem)
+QKV = [vp, i64p, vp, i64p, vp, i64p]          # q, q_strides, k, k_strides, v, v_strides
+BWD = [pp] + QKV + [vp, vp, vp, i64p]         # ..., o, g, grad_o, go_strides
+NF4 = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
+# every function include/fastmax_hip.h declares, in its order: name -> (restype, argtypes).
+# tests/test_binding_cpu.py checks each row against the prototype.
+ABI = {
+    "fastmax_hip_tune": (ci, [cs, ci]),
+    "fastmax_hip_tune_get": (ci, [cs]),
+    "fastmax_hip_build_flags": (ci, []),
+    "fastmax_hip_forward_workspace": (sz, [pp]),
+    "fastmax_hip_forward": (ci, [pp] + QKV + [vp, vp, vp, sz, vp]),
+    "fastmax_hip_backward_workspace": (sz, [pp]),
+    "fastmax_hip_backward": (ci, BWD + [vp, vp, vp, vp, sz, vp]),
+    "fastmax_hip_forward_state_bytes": (sz, [pp] + QKV + [vp]),
+    "fastmax_hip_backward_with_states": (ci, BWD + [vp, vp, vp, vp, sz, vp, sz, vp]),
+    "fastmax_hip_normalize_workspace": (sz, [ci, ci]),
+    "fastmax_hip_normalize": (ci, [vp, i64p, ci, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_stats": (ci, [vp, i64p, ci, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_stats2_workspace": (sz, [ci, ci, ci]),
+    "fastmax_hip_normalize_stats2": (ci, [vp, i64p, vp, i64p, ci, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_cast": (ci, [vp, i64p, ci, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_backward_workspace": (sz, [ci, ci, ci]),
+    "fastmax_hip_normalize_backward": (ci, [vp, i64p, ci, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_cast_expand": (ci, [vp, i64p, ci, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_normalize_backward_expand": (ci, [vp, i64p, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_linearmax_forward": (ci, [pp] + QKV + [vp, vp, vp, vp, vp, sz, vp]),
+    "fastmax_hip_linearmax_forward_auto_workspace": (sz, [pp]),
+    "fastmax_hip_linearmax_forward_auto": (ci, [pp] + QKV + [vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "fastmax_hip_linearmax_train_supported": (ci, [pp]),
+    "fastmax_hip_linearmax_backward": (ci, BWD + [vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, ci, vp]),
+    "fastmax_hip_rope_qkv_split": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_rope_qkv_split_backward": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_cross_entropy_forward": (ci, [vp, i64, vp, vp, vp, i64, ci, i64, ci, vp]),
+    "fastmax_hip_cross_entropy_backward": (ci, [vp, i64, vp, vp, vp, cf, vp, i64, i64, ci, i64, ci, vp]),
+    "fastmax_hip_decode_state_bytes": (sz, [ci, ci, ci]),
+    "fastmax_hip_p1_prefill_state": (ci, [pp, vp, i64p, vp, i64p, vp, vp]),
+    "fastmax_hip_p1_decode_step": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, cf, i64, vp]),
+    "fastmax_hip_p2_decode_state_bytes": (sz, [ci, ci, ci]),
+    "fastmax_hip_p2_prefill_state": (ci, [pp, vp, i64p, vp, i64p, vp, vp]),
+    "fastmax_hip_p2_decode_step": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
+    "fastmax_hip_p2_extend_workspace": (sz, [ci, ci, ci, ci, ci]),
+    "fastmax_hip_p2_extend": (ci, [pp, ci] + QKV + [vp, vp, vp, sz, vp]),
+    "fastmax_hip_nf4_linear_forward": (ci, NF4),
+    "fastmax_hip_nf4_linear_backward_input": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_nf4_dequantize": (ci, [vp, vp, vp, i64, ci, vp]),
+    "fastmax_hip_nf4_linear_forward_s": (ci, NF4),
+    "fastmax_hip_nf4_linear_backward_input_s": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_nf4_dequantize_s": (ci, [vp, vp, vp, i64, ci, vp]),
+    "fastmax_hip_qlora_gemm": (ci, [vp, i64, vp, ci, vp, vp, vp, vp, ci, vp, i64, ci, ci, ci, vp]),
+    "fastmax_hip_qlora_gemm_rope": (ci, [vp, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_nf4_dequantize_transposed": (ci, [vp, vp, vp, ci, ci, vp]),
+    "fastmax_hip_lora_down": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, vp]),
+    "fastmax_hip_lora_tn_workspace": (i64, [ci, ci, ci]),
+    "fastmax_hip_lora_tn": (ci, [vp, i64, vp, i64, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
+    "fastmax_hip_lora_up": (ci, [vp, i64, vp, i64, vp, i64, ci, vp, ci, ci, ci, vp]),
+    "fastmax_hip_lora_down_dropout": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, vp, cf, vp]),
+    "fastmax_hip_lora_tn_dropout": (ci, [vp, i64, vp, i64, vp, ci, ci, ci, vp, ci, ci, ci, vp, cf, vp]),
+    "fastmax_hip_lora_up_dropout": (ci, [vp, i64, vp, i64, vp, i64, ci, vp, ci, ci, ci, vp, cf, vp]),
+    "fastmax_hip_lora_dropout_mask": (ci, [vp, ci, ci, vp, cf, vp]),
+    "fastmax_hip_lora_scatter": (ci, [vp, ci, ci, vp, ci, cf, vp, i64, ci, ci, vp]),
+    "fastmax_hip_lora_scatter_backward": (ci, [vp, ci, i64, vp, vp, cf, vp, ci, ci, ci, vp]),
+    "fastmax_hip_abi_version": (ci, []),
+    "fastmax_hip_select_path": (ci, [pp]),
+    "fastmax_hip_error_string": (cs, [ci]),
+}
+SYMBOLS = list(ABI)
 
 _lib = None
 
@@ -58,130 +105,12 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(L, s):
-            raise RuntimeError(f"libfastmax_hip.so does not export {s}")
-    vp, i64p, fp, sz, ci = ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    pp = ctypes.POINTER(Problem)
-    L.fastmax_hip_tune.argtypes = [ctypes.c_char_p, ci]
-    L.fastmax_hip_tune.restype = ci
-    L.fastmax_hip_tune_get.argtypes = [ctypes.c_char_p]
-    L.fastmax_hip_tune_get.restype = ci
-    L.fastmax_hip_build_flags.argtypes = []
-    L.fastmax_hip_build_flags.restype = ci
-    L.fastmax_hip_forward_workspace.argtypes = [pp]
-    L.fastmax_hip_forward_workspace.restype = sz
-    L.fastmax_hip_forward.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, vp, fp, vp, sz, vp]
-    L.fastmax_hip_forward.restype = ci
-    L.fastmax_hip_backward_workspace.argtypes = [pp]
-    L.fastmax_hip_backward_workspace.restype = sz
-    L.fastmax_hip_backward.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, vp, fp, vp, i64p, vp, vp, vp, vp, sz, vp]
-    L.fastmax_hip_backward_with_states.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, vp, fp, vp, i64p, vp, vp, vp, vp, sz, vp, sz, vp]
-    L.fastmax_hip_backward_with_states.restype = ci
-    L.fastmax_hip_forward_state_bytes.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, vp]
-    L.fastmax_hip_forward_state_bytes.restype = sz
-    L.fastmax_hip_backward.restype = ci
-    L.fastmax_hip_normalize_workspace.argtypes = [ci, ci]
-    L.fastmax_hip_normalize_workspace.restype = sz
-    L.fastmax_hip_normalize.argtypes = [vp, i64p, ci, fp, fp, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize.restype = ci
-    L.fastmax_hip_normalize_stats.argtypes = [vp, i64p, ci, fp, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_stats.restype = ci
-    L.fastmax_hip_normalize_stats2_workspace.argtypes = [ci, ci, ci]
-    L.fastmax_hip_normalize_stats2_workspace.restype = sz
-    L.fastmax_hip_normalize_stats2.argtypes = [vp, i64p, vp, i64p, ci, fp, fp, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_stats2.restype = ci
-    L.fastmax_hip_normalize_cast.argtypes = [vp, i64p, ci, vp, fp, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_cast.restype = ci
-    L.fastmax_hip_normalize_backward_workspace.argtypes = [ci, ci, ci]
-    L.fastmax_hip_normalize_backward_workspace.restype = sz
-    L.fastmax_hip_normalize_backward.argtypes = [vp, i64p, ci, vp, fp, vp, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_backward.restype = ci
-    L.fastmax_hip_rope_qkv_split.argtypes = [vp, fp, fp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.fastmax_hip_rope_qkv_split.restype = ci
-    L.fastmax_hip_rope_qkv_split_backward.argtypes = [vp, vp, vp, fp, fp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.fastmax_hip_rope_qkv_split_backward.restype = ci
-    i64 = ctypes.c_int64
-    L.fastmax_hip_cross_entropy_forward.argtypes = [vp, i64, vp, fp, fp, i64, ci, i64, ci, vp]
-    L.fastmax_hip_cross_entropy_forward.restype = ci
-    L.fastmax_hip_cross_entropy_backward.argtypes = [vp, i64, vp, fp, fp, ctypes.c_float, vp, i64, i64, ci, i64, ci, vp]
-    L.fastmax_hip_cross_entropy_backward.restype = ci
-    L.fastmax_hip_linearmax_forward.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, fp, fp, vp, fp, vp, sz, vp]
-    L.fastmax_hip_linearmax_forward.restype = ci
-    L.fastmax_hip_linearmax_forward_auto.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, fp, fp, vp, vp, vp, fp, vp, sz, vp]
-    L.fastmax_hip_linearmax_forward_auto.restype = ci
-    L.fastmax_hip_linearmax_forward_auto_workspace.argtypes = [pp]
-    L.fastmax_hip_linearmax_forward_auto_workspace.restype = sz
-    L.fastmax_hip_linearmax_train_supported.argtypes = [pp]
-    L.fastmax_hip_linearmax_train_supported.restype = ci
-    L.fastmax_hip_linearmax_backward.argtypes = [pp, vp, i64p, vp, i64p, vp, i64p, vp, fp, vp, i64p, fp, fp, vp, vp, vp, vp, vp, vp, sz, vp, sz, ci, vp]
-    L.fastmax_hip_linearmax_backward.restype = ci
-    i64 = ctypes.c_int64
-    L.fastmax_hip_decode_state_bytes.argtypes = [ci, ci, ci]
-    L.fastmax_hip_decode_state_bytes.restype = sz
-    L.fastmax_hip_p1_prefill_state.argtypes = [pp, vp, i64p, vp, i64p, fp, vp]
-    L.fastmax_hip_p1_prefill_state.restype = ci
-    L.fastmax_hip_p1_decode_step.argtypes = [vp, i64p, vp, i64p, vp, i64p, fp, vp, ci, ci, ci, ci, ci, ctypes.c_float, i64, vp]
-    L.fastmax_hip_p1_decode_step.restype = ci
-    L.fastmax_hip_p2_decode_state_bytes.argtypes = [ci, ci, ci]
-    L.fastmax_hip_p2_decode_state_bytes.restype = sz
-    L.fastmax_hip_p2_prefill_state.argtypes = [pp, vp, i64p, vp, i64p, fp, vp]
-    L.fastmax_hip_p2_prefill_state.restype = ci
-    L.fastmax_hip_p2_decode_step.argtypes = [vp, i64p, vp, i64p, vp, i64p, fp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
-    L.fastmax_hip_p2_decode_step.restype = ci
-    L.fastmax_hip_p2_extend_workspace.argtypes = [ci, ci, ci, ci, ci]
-    L.fastmax_hip_p2_extend_workspace.restype = sz
-    L.fastmax_hip_p2_extend.argtypes = [pp, ci, vp, i64p, vp, i64p, vp, i64p, fp, vp, vp, sz, vp]
-    L.fastmax_hip_p2_extend.restype = ci
-    L.fastmax_hip_nf4_linear_forward.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
-    L.fastmax_hip_nf4_linear_forward.restype = ci
-    L.fastmax_hip_nf4_linear_backward_input.argtypes = [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]
-    L.fastmax_hip_nf4_linear_backward_input.restype = ci
-    L.fastmax_hip_nf4_dequantize.argtypes = [vp, vp, vp, i64, ci, vp]
-    L.fastmax_hip_nf4_dequantize.restype = ci
-    L.fastmax_hip_nf4_linear_forward_s.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
-    L.fastmax_hip_nf4_linear_forward_s.restype = ci
-    L.fastmax_hip_nf4_linear_backward_input_s.argtypes = [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]
-    L.fastmax_hip_nf4_linear_backward_input_s.restype = ci
-    L.fastmax_hip_nf4_dequantize_s.argtypes = [vp, vp, vp, i64, ci, vp]
-    L.fastmax_hip_nf4_dequantize_s.restype = ci
-    L.fastmax_hip_qlora_gemm.argtypes = [vp, i64, vp, ci, vp, vp, vp, vp, ci, vp, i64, ci, ci, ci, vp]
-    L.fastmax_hip_qlora_gemm.restype = ci
-    L.fastmax_hip_nf4_dequantize_transposed.argtypes = [vp, vp, vp, ci, ci, vp]
-    L.fastmax_hip_nf4_dequantize_transposed.restype = ci
-    L.fastmax_hip_qlora_gemm_rope.argtypes = [vp, i64, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.fastmax_hip_qlora_gemm_rope.restype = ci
-    L.fastmax_hip_lora_down.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, vp]
-    L.fastmax_hip_lora_down.restype = ci
-    L.fastmax_hip_lora_tn_workspace.argtypes = [ci, ci, ci]
-    L.fastmax_hip_lora_tn_workspace.restype = i64
-    L.fastmax_hip_lora_tn.argtypes = [vp, i64, vp, i64, vp, ci, ci, ci, vp, ci, ci, ci, vp]
-    L.fastmax_hip_lora_tn.restype = ci
-    L.fastmax_hip_lora_up.argtypes = [vp, i64, vp, i64, vp, i64, ci, vp, ci, ci, ci, vp]
-    cf = ctypes.c_float
-    L.fastmax_hip_lora_down_dropout.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, vp, cf, vp]
-    L.fastmax_hip_lora_down_dropout.restype = ci
-    L.fastmax_hip_lora_tn_dropout.argtypes = [vp, i64, vp, i64, vp, ci, ci, ci, vp, ci, ci, ci, vp, cf, vp]
-    L.fastmax_hip_lora_tn_dropout.restype = ci
-    L.fastmax_hip_lora_up_dropout.argtypes = [vp, i64, vp, i64, vp, i64, ci, vp, ci, ci, ci, vp, cf, vp]
-    L.fastmax_hip_lora_up_dropout.restype = ci
-    L.fastmax_hip_lora_dropout_mask.argtypes = [vp, ci, ci, vp, cf, vp]
-    L.fastmax_hip_lora_dropout_mask.restype = ci
-    L.fastmax_hip_normalize_cast_expand.argtypes = [vp, i64p, ci, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_cast_expand.restype = ci
-    L.fastmax_hip_normalize_backward_expand.argtypes = [vp, i64p, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, sz, vp]
-    L.fastmax_hip_normalize_backward_expand.restype = ci
-    L.fastmax_hip_lora_scatter.argtypes = [vp, ci, ci, vp, ci, ctypes.c_float, vp, i64, ci, ci, vp]
-    L.fastmax_hip_lora_scatter.restype = ci
-    L.fastmax_hip_lora_scatter_backward.argtypes = [vp, ci, i64, vp, vp, ctypes.c_float, vp, ci, ci, ci, vp]
-    L.fastmax_hip_lora_scatter_backward.restype = ci
-    L.fastmax_hip_lora_up.restype = ci
-    L.fastmax_hip_abi_version.restype = ci
-    L.fastmax_hip_select_path.argtypes = [pp]
-    L.fastmax_hip_select_path.restype = ci
-    L.fastmax_hip_error_string.argtypes = [ci]
-    L.fastmax_hip_error_string.restype = ctypes.c_char_p
-    if L.fastmax_hip_abi_version() != 8:
+    for name, (restype, argtypes) in ABI.items():
+        if not hasattr(L, name):
+            raise RuntimeError(f"libfastmax_hip.so does not export {name}")
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    if L.fastmax_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libfastmax_hip.so ABI version mismatch")
     _lib = L
     return L
@@ -192,7 +121,7 @@ def error_string(code):
 
 
 def check(code, what):
-    if code == 0:
+    if code == OK:
         return
     if code == E_BAD_P:
         raise ValueError(f"{what}: {error_string(code)}")

@@ -52,6 +52,109 @@ bool aligned16(const void* ptr, const int64_t* s, int dtype) {
         if ((s[i] * es) & 15) return false;
     return true;
 }
+// Operand layout of one call: a bit per operand that keeps the 16-byte rule (base address, and for the strided ones every row
+// stride); computed once, read by every decision below.  An operand the entry point does not have leaves its bit clear.
+enum : unsigned {
+    LAY_Q = 1, LAY_K = 2, LAY_V = 4, LAY_GO = 8, LAY_O = 16, LAY_DQ = 32, LAY_DK = 64, LAY_DV = 128,
+    LAY_FWD = LAY_Q | LAY_K | LAY_V | LAY_O,                                          // what the matrix-core forwards read and write
+    // the callers' rules differ and each is kept as it was: the backward tiles do not ask for o, the linear-time backwards do
+    LAY_BWD_TILES = LAY_Q | LAY_K | LAY_V | LAY_GO | LAY_DQ | LAY_DK | LAY_DV,
+    LAY_BWD_ALL = LAY_BWD_TILES | LAY_O,
+};
+bool has(unsigned lay, unsigned need) { return (lay & need) == need; }
+unsigned layout(const fastmax_problem& p, const void* q, const int64_t* qs, const void* k, const int64_t* ks, const void* v,
+                const int64_t* vs, const void* o, const void* go = nullptr, const int64_t* gos = nullptr, const void* dq = nullptr,
+                const void* dk = nullptr, const void* dv = nullptr) {
+    auto base = [](const void* ptr) { return ptr && !(reinterpret_cast<uintptr_t>(ptr) & 15); };
+    return (aligned16(q, qs, p.in_dtype) ? LAY_Q : 0) | (aligned16(k, ks, p.in_dtype) ? LAY_K : 0) | (aligned16(v, vs, p.in_dtype) ? LAY_V : 0) |
+           (go && aligned16(go, gos, p.in_dtype) ? LAY_GO : 0) | (base(o) ? LAY_O : 0) | (base(dq) ? LAY_DQ : 0) | (base(dk) ? LAY_DK : 0) |
+           (base(dv) ? LAY_DV : 0);
+}
+
+// state tile of the sequence split: the scans carry a 64 x 64 or a 128 x 128 state
+int scan_dp(const fastmax_problem& p) { return p.D <= 64 ? 64 : 128; }
+// bytes of prefix states a split scan leaves at the start of its workspace (0: this problem is not split)
+size_t scan_state_bytes(const fastmax_problem& p) { return split_workspace_bytes(p, scan_dp(p)); }
+
+enum FwdKernel {
+    FWD_QUADRATIC, FWD_RECURRENT, FWD_UNMASKED_LIN, FWD_SCAN_V2, FWD_SCAN_D128_2P, FWD_SCAN_BF16, FWD_SCAN_GEN, FWD_QUAD32, FWD_QUAD_MFMA
+};
+// the scan kernel of a p = 1 masked problem whose q, k may carry the linearmax scales (the headline kernel takes none)
+FwdKernel scan_kernel(const fastmax_problem& p) {
+    if (mfma_d128_2p_supported(p)) return FWD_SCAN_D128_2P;
+    return use_bf16_kernel(p) ? FWD_SCAN_BF16 : FWD_SCAN_GEN;
+}
+int launch_fwd_scan(const FwdArgs& a, const float* qscale, const float* kscale) {
+    switch (scan_kernel(a.prob)) {
+        case FWD_SCAN_D128_2P: return launch_fwd_mfma_d128_2p(a, qscale, kscale);
+        case FWD_SCAN_BF16: return launch_fwd_mfma_bf16(a, qscale, kscale);
+        default: return launch_fwd_mfma_gen(a, qscale, kscale);
+    }
+}
+
+// Everything fastmax_hip_forward decides, as a function of (problem, layout): rc < 0 rejects the call; else the family
+// (what fastmax_hip_select_path reports), the kernel, the workspace it needs and how many leading bytes of that workspace
+// hold prefix states afterwards.  The size queries have no operands: they plan with LAY_FWD.
+struct FwdPlan {
+    int rc, path;
+    FwdKernel kernel;
+    size_t workspace, state_bytes;
+};
+FwdPlan fwd_plan(const fastmax_problem& p, unsigned lay) {
+    FwdPlan f{FASTMAX_OK, select(p), FWD_QUADRATIC, 0, 0};
+    if (f.path < 0) {
+        f.rc = f.path;
+        return f;
+    }
+    if ((f.path == FASTMAX_PATH_MFMA || f.path == FASTMAX_PATH_QUADRATIC_MFMA) && !has(lay, LAY_FWD)) {
+        if (p.path == f.path) {          // the caller forced this family
+            f.rc = FASTMAX_E_ALIGNMENT;
+            return f;
+        }
+        f.path = (f.path == FASTMAX_PATH_MFMA && p.causal) ? FASTMAX_PATH_RECURRENT : FASTMAX_PATH_QUADRATIC;
+    }
+    switch (f.path) {
+        case FASTMAX_PATH_MFMA:
+            if (!p.causal) {
+                f.kernel = FWD_UNMASKED_LIN;
+                f.workspace = unmasked_lin_workspace(p);
+            } else {
+                f.kernel = mfma_p1_supported(p) ? FWD_SCAN_V2 : scan_kernel(p);
+                f.workspace = f.state_bytes = scan_state_bytes(p);
+            }
+            break;
+        case FASTMAX_PATH_RECURRENT: f.kernel = FWD_RECURRENT; break;
+        case FASTMAX_PATH_QUADRATIC_MFMA: f.kernel = quad32_supported(p) ? FWD_QUAD32 : FWD_QUAD_MFMA; break;
+        default: break;
+    }
+    return f;
+}
+
+enum BwdKernel { BWD_QUADRATIC, BWD_UNMASKED_LIN, BWD_LIN, BWD_SCAN, BWD_QUAD32, BWD_QUAD_MFMA };
+BwdKernel bwd_select(const fastmax_problem& p, unsigned lay) {
+    // matrix-core tiles unless the caller forces the vector-ALU family or the layout rules it out
+    if (p.path == FASTMAX_PATH_QUADRATIC || !quad_mfma_bwd_supported(p) || !has(lay, LAY_BWD_TILES)) return BWD_QUADRATIC;
+    // the linear-time kernels, unless the caller asks for the tile kernels; they also read o in 16-byte pieces
+    if (p.path != FASTMAX_PATH_QUADRATIC_MFMA && has(lay, LAY_O)) {
+        // p=1 unmasked at sizes where totals + row-wise D x D products beat the O(N_q N_k) tiles
+        if (unmasked_lin_bwd_supported(p)) return BWD_UNMASKED_LIN;
+        // p=1 masked: scans with a carried D x D state
+        if (lin_bwd_supported(p) && p.in_dtype == p.out_dtype) return BWD_LIN;
+        // fp32 / fp16 at 64 < D <= 128: the same scans with two-part operands, one per gradient (fastmax_scan_d128_2p.hip)
+        if (scan_bwd_supported(p)) return BWD_SCAN;
+    }
+    return quad32_bwd_supported(p) ? BWD_QUAD32 : BWD_QUAD_MFMA;
+}
+
+// null / shape / workspace checks of the normalize family, in the order every entry point applies them
+int normalize_check(bool have_ptrs, int B, int H, int rep, int N, int D, const void* workspace, size_t workspace_bytes, size_t need,
+                    int dtype = FASTMAX_F32) {
+    if (!have_ptrs) return FASTMAX_E_NULL;
+    if (B <= 0 || H <= 0 || rep <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
+    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
+    if (!workspace || workspace_bytes < need) return FASTMAX_E_WORKSPACE;
+    return FASTMAX_OK;
+}
 }  // namespace
 
 namespace fastmax {
@@ -139,14 +242,13 @@ const char* fastmax_hip_error_string(int code) {
 int fastmax_hip_select_path(const fastmax_problem* prob) {
     const int rc = validate(prob);
     if (rc) return rc;
-    return select(*prob);
+    const FwdPlan plan = fwd_plan(*prob, LAY_FWD);
+    return plan.rc ? plan.rc : plan.path;
 }
 
 size_t fastmax_hip_forward_workspace(const fastmax_problem* prob) {
     if (validate(prob)) return 0;
-    if (select(*prob) != FASTMAX_PATH_MFMA) return 0;
-    if (!prob->causal) return unmasked_lin_workspace(*prob);
-    return split_workspace_bytes(*prob, prob->D <= 64 ? 64 : 128);
+    return fwd_plan(*prob, LAY_FWD).workspace;
 }
 
 int fastmax_hip_forward(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
@@ -155,28 +257,22 @@ int fastmax_hip_forward(const fastmax_problem* prob, const void* q, const int64_
     int rc = validate(prob);
     if (rc) return rc;
     if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides) return FASTMAX_E_NULL;
-    int path = select(*prob);
-    if (path < 0) return path;
-    if (path == FASTMAX_PATH_MFMA || path == FASTMAX_PATH_QUADRATIC_MFMA) {
-        const bool ok = aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) &&
-                        aligned16(v, v_strides, prob->in_dtype) && !(reinterpret_cast<uintptr_t>(o) & 15);
-        if (!ok) {
-            if (prob->path == path) return FASTMAX_E_ALIGNMENT;          // the caller forced this family
-            path = path == FASTMAX_PATH_MFMA ? (prob->causal ? FASTMAX_PATH_RECURRENT : FASTMAX_PATH_QUADRATIC) : FASTMAX_PATH_QUADRATIC;
-        }
-    }
+    const FwdPlan plan = fwd_plan(*prob, layout(*prob, q, q_strides, k, k_strides, v, v_strides, o));
+    if (plan.rc) return plan.rc;
     FwdArgs a{*prob, q, k, v, st(q_strides), st(k_strides), st(v_strides), o, g, workspace, workspace_bytes,
               reinterpret_cast<hipStream_t>(stream)};
-    switch (path) {
-        case FASTMAX_PATH_MFMA:
-            if (!prob->causal) return launch_fwd_unmasked_p1(a);
-            if (mfma_p1_supported(*prob)) return launch_fwd_mfma_p1(a);
-            if (mfma_d128_2p_supported(*prob)) return launch_fwd_mfma_d128_2p(a, nullptr, nullptr);
-            return use_bf16_kernel(*prob) ? launch_fwd_mfma_bf16(a, nullptr, nullptr) : launch_fwd_mfma_gen(a, nullptr, nullptr);
-        case FASTMAX_PATH_RECURRENT: return launch_fwd_recurrent_p1(a);
-        case FASTMAX_PATH_QUADRATIC_MFMA: return quad32_supported(a.prob) ? launch_fwd_quad32(a) : launch_fwd_quad_mfma(a);
-        default: return launch_fwd_quadratic(a);
+    switch (plan.kernel) {
+        case FWD_UNMASKED_LIN: return launch_fwd_unmasked_p1(a);
+        case FWD_SCAN_V2: return launch_fwd_mfma_p1(a);
+        case FWD_SCAN_D128_2P:
+        case FWD_SCAN_BF16:
+        case FWD_SCAN_GEN: return launch_fwd_scan(a, nullptr, nullptr);
+        case FWD_RECURRENT: return launch_fwd_recurrent_p1(a);
+        case FWD_QUAD32: return launch_fwd_quad32(a);
+        case FWD_QUAD_MFMA: return launch_fwd_quad_mfma(a);
+        case FWD_QUADRATIC: break;
     }
+    return launch_fwd_quadratic(a);
 }
 
 size_t fastmax_hip_backward_workspace(const fastmax_problem* prob) {
@@ -191,13 +287,8 @@ size_t fastmax_hip_backward_workspace(const fastmax_problem* prob) {
 size_t fastmax_hip_forward_state_bytes(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
                                        const int64_t* k_strides, const void* v, const int64_t* v_strides, const void* o) {
     if (validate(prob) || !q || !k || !v || !o || !q_strides || !k_strides || !v_strides) return 0;
-    if (select(*prob) != FASTMAX_PATH_MFMA || !prob->causal) return 0;
-    // the same layout rule as fastmax_hip_forward: anything else takes a kernel without a sequence split
-    if (!(aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) && aligned16(v, v_strides, prob->in_dtype) &&
-          !(reinterpret_cast<uintptr_t>(o) & 15)))
-        return 0;
-    if (split_plan(*prob).nseg <= 1) return 0;
-    return split_workspace_bytes(*prob, prob->D <= 64 ? 64 : 128);
+    const FwdPlan plan = fwd_plan(*prob, layout(*prob, q, q_strides, k, k_strides, v, v_strides, o));
+    return plan.rc ? 0 : plan.state_bytes;
 }
 
 int fastmax_hip_backward_with_states(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
@@ -211,27 +302,20 @@ int fastmax_hip_backward_with_states(const fastmax_problem* prob, const void* q,
         return FASTMAX_E_NULL;
     BwdArgs a{*prob, q, k, v, o, grad_o, g, st(q_strides), st(k_strides), st(v_strides), st(go_strides), dq, dk, dv,
               workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)};
-    if (fwd_states && fwd_state_bytes >= fastmax_hip_forward_state_bytes(prob, q, q_strides, k, k_strides, v, v_strides, o) && fwd_state_bytes > 0 &&
-        !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
+    const unsigned lay = layout(*prob, q, q_strides, k, k_strides, v, v_strides, o, grad_o, go_strides, dq, dk, dv);
+    // the caller's records are taken when they cover what this forward leaves (a rejected or unsplit forward leaves none)
+    const FwdPlan fwd = fwd_plan(*prob, lay);
+    if (fwd_states && fwd_state_bytes > 0 && fwd_state_bytes >= (fwd.rc ? 0 : fwd.state_bytes) && !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
         a.fwd_states = reinterpret_cast<const float*>(fwd_states);
-    // matrix-core tiles unless the caller forces the vector-ALU family or the layout rules it out
-    const bool mfma_ok = prob->path != FASTMAX_PATH_QUADRATIC && quad_mfma_bwd_supported(*prob) &&
-                         aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) &&
-                         aligned16(v, v_strides, prob->in_dtype) && aligned16(grad_o, go_strides, prob->in_dtype) &&
-                         !((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) |
-                            reinterpret_cast<uintptr_t>(dv)) & 15);
-    if (!mfma_ok) return launch_bwd_quadratic(a);
-    // p=1 unmasked at sizes where totals + row-wise D x D products beat the O(N_q N_k) tiles
-    if (prob->path != FASTMAX_PATH_QUADRATIC_MFMA && unmasked_lin_bwd_supported(*prob) && !(reinterpret_cast<uintptr_t>(o) & 15))
-        return launch_bwd_unmasked_p1(a);
-    // p=1 masked: linear-time scans (carried D x D state) unless the caller asks for the tile kernels
-    const bool lin = prob->path != FASTMAX_PATH_QUADRATIC_MFMA && lin_bwd_supported(*prob) && prob->in_dtype == prob->out_dtype &&
-                     !(reinterpret_cast<uintptr_t>(o) & 15);
-    if (lin) return launch_bwd_lin(a);
-    // fp32 / fp16 at 64 < D <= 128: the same scans with two-part operands, one per gradient (fastmax_scan_d128_2p.hip)
-    if (prob->path != FASTMAX_PATH_QUADRATIC_MFMA && scan_bwd_supported(*prob) && !(reinterpret_cast<uintptr_t>(o) & 15))
-        return launch_bwd_scan(a);
-    return quad32_bwd_supported(*prob) ? launch_bwd_quad32(a) : launch_bwd_quad_mfma(a);
+    switch (bwd_select(*prob, lay)) {
+        case BWD_UNMASKED_LIN: return launch_bwd_unmasked_p1(a);
+        case BWD_LIN: return launch_bwd_lin(a);
+        case BWD_SCAN: return launch_bwd_scan(a);
+        case BWD_QUAD32: return launch_bwd_quad32(a);
+        case BWD_QUAD_MFMA: return launch_bwd_quad_mfma(a);
+        case BWD_QUADRATIC: break;
+    }
+    return launch_bwd_quadratic(a);
 }
 
 int fastmax_hip_backward(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
@@ -246,18 +330,16 @@ size_t fastmax_hip_normalize_workspace(int B, int H) { return sizeof(unsigned in
 
 int fastmax_hip_normalize(const void* x, const int64_t* x_strides, int dtype, float* y, float* inv_norm, int B, int H,
                           int N, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !x_strides || !y) return FASTMAX_E_NULL;
-    if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < fastmax_hip_normalize_workspace(B, H)) return FASTMAX_E_WORKSPACE;
+    const int rc = normalize_check(x && x_strides && y, B, H, 1, N, D, workspace, workspace_bytes, fastmax_hip_normalize_workspace(B, H));
+    if (rc) return rc;
     return launch_normalize(x, st(x_strides), dtype, y, inv_norm, B, H, N, D, workspace,
                             reinterpret_cast<hipStream_t>(stream));
 }
 
 int fastmax_hip_normalize_stats(const void* x, const int64_t* x_strides, int dtype, float* inv_norm, int B, int H, int N,
                                 int D, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !x_strides || !inv_norm) return FASTMAX_E_NULL;
-    if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < fastmax_hip_normalize_workspace(B, H)) return FASTMAX_E_WORKSPACE;
+    const int rc = normalize_check(x && x_strides && inv_norm, B, H, 1, N, D, workspace, workspace_bytes, fastmax_hip_normalize_workspace(B, H));
+    if (rc) return rc;
     return launch_normalize_stats(x, st(x_strides), dtype, inv_norm, B, H, N, D, workspace,
                                   reinterpret_cast<hipStream_t>(stream));
 }
@@ -269,31 +351,29 @@ size_t fastmax_hip_normalize_stats2_workspace(int B, int H, int N) {
 int fastmax_hip_normalize_stats2(const void* x0, const int64_t* x0_strides, const void* x1, const int64_t* x1_strides, int dtype,
                                  float* inv_norm0, float* inv_norm1, int B, int H, int N, int D, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-    if (!x0 || !x1 || !x0_strides || !x1_strides || !inv_norm0 || !inv_norm1) return FASTMAX_E_NULL;
-    if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D || (int64_t)B * H > 65535) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < fastmax_hip_normalize_stats2_workspace(B, H, N)) return FASTMAX_E_WORKSPACE;
+    const bool have = x0 && x1 && x0_strides && x1_strides && inv_norm0 && inv_norm1;
+    if (have && (int64_t)B * H > 65535) return FASTMAX_E_BAD_SHAPE;          // (b,h) rides on gridDim.y
+    const int rc = normalize_check(have, B, H, 1, N, D, workspace, workspace_bytes, fastmax_hip_normalize_stats2_workspace(B, H, N));
+    if (rc) return rc;
     return launch_normalize_stats2(x0, st(x0_strides), x1, st(x1_strides), dtype, inv_norm0, inv_norm1, B, H, N, D, workspace,
                                    reinterpret_cast<hipStream_t>(stream));
 }
 
 int fastmax_hip_normalize_cast(const void* x, const int64_t* x_strides, int dtype, void* y, float* inv_norm, int B, int H,
                                int N, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !x_strides || !y || !inv_norm) return FASTMAX_E_NULL;
-    if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < fastmax_hip_normalize_workspace(B, H)) return FASTMAX_E_WORKSPACE;
-    const int es = dtype == FASTMAX_F32 ? 4 : 2;
-    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
-    if (D * es > 1024) return FASTMAX_E_BAD_SHAPE;
+    int rc = normalize_check(x && x_strides && y && inv_norm, B, H, 1, N, D, workspace, workspace_bytes, fastmax_hip_normalize_workspace(B, H));
+    if (rc) return rc;
+    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;          // after the workspace check here, before it in _cast_expand
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int npart = (N + 255) / 256;
     if (workspace_bytes >= sizeof(unsigned int) * (size_t)B * H * npart) {
         // two launches: per-block maxima, then the row pass combines them (no zeroing pass, no atomics, no finish pass)
         unsigned int* partials = reinterpret_cast<unsigned int*>(workspace);
-        int rc = launch_normalize_partial_max(x, st(x_strides), dtype, partials, B, H, N, D, s);
+        rc = launch_normalize_partial_max(x, st(x_strides), dtype, partials, B, H, N, D, s);
         if (rc) return rc;
         return launch_normalize_cast(x, st(x_strides), dtype, y, nullptr, B, H, N, D, s, partials, npart, inv_norm);
     }
-    int rc = launch_normalize_stats(x, st(x_strides), dtype, inv_norm, B, H, N, D, workspace, s);
+    rc = launch_normalize_stats(x, st(x_strides), dtype, inv_norm, B, H, N, D, workspace, s);
     if (rc) return rc;
     return launch_normalize_cast(x, st(x_strides), dtype, y, inv_norm, B, H, N, D, s);
 }
@@ -303,9 +383,9 @@ size_t fastmax_hip_normalize_backward_workspace(int B, int H, int N) { return no
 int fastmax_hip_normalize_backward(const void* x, const int64_t* x_strides, int dtype, const void* grad_y, const float* inv_norm,
                                    void* grad_x, int B, int H, int N, int D, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    if (!x || !x_strides || !grad_y || !inv_norm || !grad_x) return FASTMAX_E_NULL;
-    if (B <= 0 || H <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < normalize_backward_workspace(B, H, N)) return FASTMAX_E_WORKSPACE;
+    const int rc = normalize_check(x && x_strides && grad_y && inv_norm && grad_x, B, H, 1, N, D, workspace, workspace_bytes,
+                                   normalize_backward_workspace(B, H, N));
+    if (rc) return rc;
     return launch_normalize_backward(x, st(x_strides), dtype, grad_y, inv_norm, grad_x, B, H, N, D, workspace,
                                      reinterpret_cast<hipStream_t>(stream));
 }
@@ -315,16 +395,13 @@ int fastmax_hip_normalize_backward(const void* x, const int64_t* x_strides, int 
 // and the sum over a group's heads fused into its backward
 int fastmax_hip_normalize_cast_expand(const void* x, const int64_t* x_strides, int dtype, void* y, float* inv_norm, int B, int G,
                                       int rep, int N, int D, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !x_strides || !y || !inv_norm) return FASTMAX_E_NULL;
-    if (B <= 0 || G <= 0 || rep <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
-    const int es = dtype == FASTMAX_F32 ? 4 : 2;
-    if (D * es > 1024) return FASTMAX_E_BAD_SHAPE;
     const int npart = (N + 255) / 256;
-    if (!workspace || workspace_bytes < sizeof(unsigned int) * (size_t)B * G * npart) return FASTMAX_E_WORKSPACE;
+    int rc = normalize_check(x && x_strides && y && inv_norm, B, G, rep, N, D, workspace, workspace_bytes,
+                             sizeof(unsigned int) * (size_t)B * G * npart, dtype);
+    if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     unsigned int* partials = reinterpret_cast<unsigned int*>(workspace);
-    const int rc = launch_normalize_partial_max(x, st(x_strides), dtype, partials, B, G, N, D, s);
+    rc = launch_normalize_partial_max(x, st(x_strides), dtype, partials, B, G, N, D, s);
     if (rc) return rc;
     return launch_normalize_cast(x, st(x_strides), dtype, y, nullptr, B, G, N, D, s, partials, npart, inv_norm, rep);
 }
@@ -332,65 +409,64 @@ int fastmax_hip_normalize_cast_expand(const void* x, const int64_t* x_strides, i
 int fastmax_hip_normalize_backward_expand(const void* x, const int64_t* x_strides, int dtype, const void* grad_y,
                                           const float* inv_norm, void* grad_x, int B, int G, int rep, int N, int D, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-    if (!x || !x_strides || !grad_y || !inv_norm || !grad_x) return FASTMAX_E_NULL;
-    if (B <= 0 || G <= 0 || rep <= 0 || N <= 0 || D <= 0 || D > FASTMAX_MAX_D) return FASTMAX_E_BAD_SHAPE;
-    if (!workspace || workspace_bytes < normalize_backward_workspace_grouped(B, G, rep, N)) return FASTMAX_E_WORKSPACE;
+    const int rc = normalize_check(x && x_strides && grad_y && inv_norm && grad_x, B, G, rep, N, D, workspace, workspace_bytes,
+                                   normalize_backward_workspace_grouped(B, G, rep, N));
+    if (rc) return rc;
     return launch_normalize_backward(x, st(x_strides), dtype, grad_y, inv_norm, grad_x, B, G, N, D, workspace,
                                      reinterpret_cast<hipStream_t>(stream), rep);
+}
+
+// what the two fused linearmax forwards ask of a call before they launch a scan that applies q's and k's scales
+static int linearmax_fwd_check(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
+                               const int64_t* k_strides, const void* v, const int64_t* v_strides, const float* q_inv_norm,
+                               const float* k_inv_norm, const void* o) {
+    const int rc = validate(prob);
+    if (rc) return rc;
+    if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !q_inv_norm || !k_inv_norm) return FASTMAX_E_NULL;
+    if (!mfma_gen_supported(*prob, true) && !mfma_d128_2p_supported(*prob)) return FASTMAX_E_BAD_SHAPE;
+    return has(layout(*prob, q, q_strides, k, k_strides, v, v_strides, o), LAY_FWD) ? FASTMAX_OK : FASTMAX_E_ALIGNMENT;
 }
 
 int fastmax_hip_linearmax_forward(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
                                   const int64_t* k_strides, const void* v, const int64_t* v_strides,
                                   const float* q_inv_norm, const float* k_inv_norm, void* o, float* g, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    int rc = validate(prob);
+    const int rc = linearmax_fwd_check(prob, q, q_strides, k, k_strides, v, v_strides, q_inv_norm, k_inv_norm, o);
     if (rc) return rc;
-    if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !q_inv_norm || !k_inv_norm) return FASTMAX_E_NULL;
-    if (!mfma_gen_supported(*prob, true) && !mfma_d128_2p_supported(*prob)) return FASTMAX_E_BAD_SHAPE;
-    if (!(aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) &&
-          aligned16(v, v_strides, prob->in_dtype)) || (reinterpret_cast<uintptr_t>(o) & 15))
-        return FASTMAX_E_ALIGNMENT;
     FwdArgs a{*prob, q, k, v, st(q_strides), st(k_strides), st(v_strides), o, g, workspace, workspace_bytes,
               reinterpret_cast<hipStream_t>(stream)};
-    if (mfma_d128_2p_supported(*prob)) return launch_fwd_mfma_d128_2p(a, q_inv_norm, k_inv_norm);
-    return use_bf16_kernel(*prob) ? launch_fwd_mfma_bf16(a, q_inv_norm, k_inv_norm) : launch_fwd_mfma_gen(a, q_inv_norm, k_inv_norm);
+    return launch_fwd_scan(a, q_inv_norm, k_inv_norm);
 }
 
 // fastmax_hack.py:36-60 (masked branch) in ONE call: statistics + scan.  With the sequence split the statistics ride on the
 // split's state pass (K is read there anyway, the state is linear in K's scale; Q's words come from extra blocks of the same
 // launch); otherwise they are the paired statistics pass.  q_inv_norm / k_inv_norm (B*H floats each) are OUTPUTS here.
-// workspace = [forward workspace | statistic words].
+// workspace = [forward workspace | statistic words]; the first part is the plan's, so a forced prob->path sizes it as it
+// sizes fastmax_hip_forward's.
 static size_t linearmax_stats_bytes(int B, int H, int N) {
     const size_t per_head = (size_t)((N + 255) / 256) + 32;          // statistics-only blocks of 256 rows + one key per segment
     return sizeof(unsigned long long) * 2 * (size_t)B * H * per_head;
 }
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static size_t linearmax_fwd_bytes(const fastmax_problem& p) { return (fwd_plan(p, LAY_FWD).workspace + 255) & ~(size_t)255; }
 
 size_t fastmax_hip_linearmax_forward_auto_workspace(const fastmax_problem* prob) {
     if (validate(prob)) return 0;
-    return align256(fastmax_hip_forward_workspace(prob)) + linearmax_stats_bytes(prob->B, prob->H, prob->Nq);
+    return linearmax_fwd_bytes(*prob) + linearmax_stats_bytes(prob->B, prob->H, prob->Nq);
 }
 
 int fastmax_hip_linearmax_forward_auto(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
                                        const int64_t* k_strides, const void* v, const int64_t* v_strides, float* q_inv_norm,
                                        float* k_inv_norm, int* q_nstar, int* k_nstar, void* o, float* g, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    int rc = validate(prob);
+    const int rc = linearmax_fwd_check(prob, q, q_strides, k, k_strides, v, v_strides, q_inv_norm, k_inv_norm, o);
     if (rc) return rc;
-    if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !q_inv_norm || !k_inv_norm) return FASTMAX_E_NULL;
-    if (!mfma_gen_supported(*prob, true) && !mfma_d128_2p_supported(*prob)) return FASTMAX_E_BAD_SHAPE;
-    if ((int64_t)prob->B * prob->H > 65535) return FASTMAX_E_BAD_SHAPE;
-    if (!(aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) &&
-          aligned16(v, v_strides, prob->in_dtype)) || (reinterpret_cast<uintptr_t>(o) & 15))
-        return FASTMAX_E_ALIGNMENT;
-    const size_t fwd_bytes = align256(fastmax_hip_forward_workspace(prob));
+    const size_t fwd_bytes = linearmax_fwd_bytes(*prob);
     if (!workspace || workspace_bytes < fwd_bytes + linearmax_stats_bytes(prob->B, prob->H, prob->Nq)) return FASTMAX_E_WORKSPACE;
     const LinearmaxStats stats{q_inv_norm, k_inv_norm, reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + fwd_bytes),
                                q_nstar, k_nstar};
     FwdArgs a{*prob, q, k, v, st(q_strides), st(k_strides), st(v_strides), o, g, workspace, fwd_bytes,
               reinterpret_cast<hipStream_t>(stream), &stats};
-    if (mfma_d128_2p_supported(*prob)) return launch_fwd_mfma_d128_2p(a, q_inv_norm, k_inv_norm);
-    return use_bf16_kernel(*prob) ? launch_fwd_mfma_bf16(a, q_inv_norm, k_inv_norm) : launch_fwd_mfma_gen(a, q_inv_norm, k_inv_norm);
+    return launch_fwd_scan(a, q_inv_norm, k_inv_norm);
 }
 
 // Training route of the same branch: the backward of fastmax_hip_linearmax_forward_auto.  q, k are the RAW tensors and
@@ -416,10 +492,7 @@ int fastmax_hip_linearmax_backward(const fastmax_problem* prob, const void* q, c
         !q_inv_norm || !k_inv_norm)
         return FASTMAX_E_NULL;
     if (!fastmax_hip_linearmax_train_supported(prob)) return FASTMAX_E_BAD_SHAPE;
-    if (!(aligned16(q, q_strides, prob->in_dtype) && aligned16(k, k_strides, prob->in_dtype) && aligned16(v, v_strides, prob->in_dtype) &&
-          aligned16(grad_o, go_strides, prob->in_dtype)) ||
-        ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dk) | reinterpret_cast<uintptr_t>(dv) | reinterpret_cast<uintptr_t>(o)) & 15))
-        return FASTMAX_E_ALIGNMENT;
+    if (!has(layout(*prob, q, q_strides, k, k_strides, v, v_strides, o, grad_o, go_strides, dq, dk, dv), LAY_BWD_ALL)) return FASTMAX_E_ALIGNMENT;
     BwdArgs a{*prob, q, k, v, o, grad_o, g, st(q_strides), st(k_strides), st(v_strides), st(go_strides), dq, dk, dv,
               workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)};
     a.qscale = q_inv_norm;
@@ -427,9 +500,9 @@ int fastmax_hip_linearmax_backward(const fastmax_problem* prob, const void* q, c
     a.fuse_prologue = ((flags & 1) && k_nstar ? 1 : 0) | ((flags & 2) && q_nstar ? 2 : 0);
     a.k_nstar = k_nstar;
     a.q_nstar = q_nstar;
-    const SplitPlan plan = split_plan(*prob);
-    if (fwd_states && plan.nseg > 1 && fwd_state_bytes >= split_workspace_bytes(*prob, prob->D <= 64 ? 64 : 128) &&
-        !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
+    // the fused forward ran a scan whatever prob->path says: its states are there iff the sequence was split
+    const size_t state_bytes = scan_state_bytes(*prob);
+    if (fwd_states && state_bytes > 0 && fwd_state_bytes >= state_bytes && !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
         a.fwd_states = reinterpret_cast<const float*>(fwd_states);
     return launch_bwd_lin(a);
 }

@@ -32,30 +32,19 @@ class FastmaxDecodeState:
     def __init__(self, B, H, D, device, normalize_term=8, tensors_normalized=False, p=1, n_query_groups=None):
         if p not in (1, 2):
             raise ValueError(f"p should be 1 or 2, got p={p}")
-        if p == 2:
-            self._init_p2(B, H, D, device, normalize_term, tensors_normalized, n_query_groups)
-            return
-        if n_query_groups not in (None, H):
-            raise ValueError("the first-order decode state has one record per head: n_query_groups must be None or H")
-        self.p = 1
-        self.B, self.H, self.D = B, H, D
-        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
-        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
-        nbytes = _lib.lib().fastmax_hip_decode_state_bytes(B, H, D)
-        if nbytes == 0:
-            raise NotImplementedError(f"head size {D} not supported")
-        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-        self.count = 0
-
-    def _init_p2(self, B, H, D, device, normalize_term, tensors_normalized, n_query_groups):
         Hkv = H if n_query_groups is None else n_query_groups
-        if Hkv <= 0 or H % Hkv != 0:
+        if p == 1 and Hkv != H:
+            raise ValueError("the first-order decode state has one record per head: n_query_groups must be None or H")
+        if p == 2 and (Hkv <= 0 or H % Hkv != 0):
             raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
-        self.p = 2
-        self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
+        self.p = p
+        self.B, self.H, self.D = B, H, D
+        if p == 2:
+            self.Hkv = Hkv          # the second-order state is kept per KV head
         self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
         self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
-        nbytes = _lib.lib().fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
+        L = _lib.lib()
+        nbytes = L.fastmax_hip_decode_state_bytes(B, H, D) if p == 1 else L.fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
         if nbytes == 0:
             raise NotImplementedError(f"head size {D} not supported")
         self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
@@ -79,15 +68,8 @@ class FastmaxDecodeState:
         if self.p == 2:
             return self._prefill_p2(q, k, v)
         assert self.count == 0, "prefill starts a sequence"
-        L = _lib.lib()
         o = fastmax(q, k, v, mask=True, p=1, **self._kw)
-        kd, vd = ops._prep(k, k.device), ops._prep(v, v.device)
-        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, 1, True, self.nt, 0.0)
-        with torch.cuda.device(kd.device):
-            rc = L.fastmax_hip_p1_prefill_state(ctypes.byref(prob), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
-                                                ops._strides(vd), self.state.data_ptr(), ops._stream(kd.device))
-        _lib.check(rc, "fastmax_hip_p1_prefill_state")
-        self.count = k.shape[2]
+        self._prefill_state(ops._prep(k, k.device), ops._prep(v, v.device))
         return o
 
     def step(self, q, k, v):
@@ -95,16 +77,12 @@ class FastmaxDecodeState:
         p=2: k and v are (B,n_query_groups,1,D); O(D^3) per KV head."""
         if self.p == 2:
             return self._step_p2(q, k, v)
-        L = _lib.lib()
         qd, kd, vd = (ops._prep(t, t.device) for t in (q, k, v))
         self.count += 1
         o = torch.empty((self.B, self.H, 1, self.D), dtype=q.dtype, device=q.device)
         dt = ops._DT[q.dtype]
-        with torch.cuda.device(q.device):
-            rc = L.fastmax_hip_p1_decode_step(qd.data_ptr(), ops._strides(qd), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
-                                              ops._strides(vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.D,
-                                              dt, dt, 1.0 / self.nt, self.count, ops._stream(q.device))
-        _lib.check(rc, "fastmax_hip_p1_decode_step")
+        ops._call("fastmax_hip_p1_decode_step", q.device,
+                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.D, dt, dt, 1.0 / self.nt, self.count))
         return o
 
     def extend(self, q, k, v):
@@ -118,17 +96,12 @@ class FastmaxDecodeState:
         if T < 1:
             raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
         self._check_p2_shapes(q, k, T)
-        L = _lib.lib()
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
         o = torch.empty((B, H, T, D), dtype=q.dtype, device=q.device)
         prob = ops._problem(qd, kd, qd.dtype, qd.dtype, 2, True, self.nt, 0.0)
-        wsb, wsp = ops._ws(L.fastmax_hip_p2_extend_workspace(B, H, Hkv, T, D), q.device)
-        with torch.cuda.device(q.device):
-            rc = L.fastmax_hip_p2_extend(ctypes.byref(prob), Hkv, qd.data_ptr(), ops._strides(qd), kd.data_ptr(), ops._strides(kd),
-                                         vd.data_ptr(), ops._strides(vd), self.state.data_ptr(), o.data_ptr(), wsp,
-                                         wsb.numel() if wsb is not None else 0, ops._stream(q.device))
-        _lib.check(rc, "fastmax_hip_p2_extend")
+        ops._call("fastmax_hip_p2_extend", q.device, (ctypes.byref(prob), Hkv, *ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr()),
+                  ws=_lib.lib().fastmax_hip_p2_extend_workspace(B, H, Hkv, T, D))
         self.count += T
         return o
 
@@ -150,26 +123,21 @@ class FastmaxDecodeState:
             qg = q.reshape(B * Hkv, r, T, D)
             kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
             o = fastmax(qg, kg, vg, mask=True, p=2, **self._kw).reshape(B, H, T, D)
-        L = _lib.lib()
-        kd, vd = ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device)
-        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, 2, True, self.nt, 0.0)
-        with torch.cuda.device(kd.device):
-            rc = L.fastmax_hip_p2_prefill_state(ctypes.byref(prob), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
-                                                ops._strides(vd), self.state.data_ptr(), ops._stream(kd.device))
-        _lib.check(rc, "fastmax_hip_p2_prefill_state")
-        self.count = T
+        self._prefill_state(ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device))
         return o
+
+    def _prefill_state(self, kd, vd):
+        """the state of the whole prompt from its prepared k, v"""
+        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, self.p, True, self.nt, 0.0)
+        ops._call(f"fastmax_hip_p{self.p}_prefill_state", kd.device, (ctypes.byref(prob), *ops._qkv(kd, vd), self.state.data_ptr()))
+        self.count = kd.shape[2]
 
     def _step_p2(self, q, k, v):
         self._check_p2_shapes(q, k, 1)
-        L = _lib.lib()
         qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
         o = torch.empty((self.B, self.H, 1, self.D), dtype=q.dtype, device=q.device)
         dt = ops._DT[q.dtype]
-        with torch.cuda.device(q.device):
-            rc = L.fastmax_hip_p2_decode_step(qd.data_ptr(), ops._strides(qd), kd.data_ptr(), ops._strides(kd), vd.data_ptr(),
-                                              ops._strides(vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.Hkv,
-                                              self.D, dt, dt, 1.0 / self.nt, ops._stream(q.device))
-        _lib.check(rc, "fastmax_hip_p2_decode_step")
+        ops._call("fastmax_hip_p2_decode_step", q.device,
+                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.Hkv, self.D, dt, dt, 1.0 / self.nt))
         self.count += 1
         return o

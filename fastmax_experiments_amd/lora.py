@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .ops import _DT, _stream
 
 NF4_CODE = torch.tensor([-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
                          -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
@@ -61,7 +62,7 @@ def nf4_dequantize(packed: torch.Tensor, absmax, shape, dtype=torch.float32) -> 
         with torch.cuda.device(packed.device):
             rc = _lib.lib().fastmax_hip_nf4_dequantize_s(packed.data_ptr(), sc.ref, out.data_ptr(), n,
                                                          _lib.F32 if dtype == torch.float32 else _lib.BF16,
-                                                         ctypes.c_void_p(torch.cuda.current_stream(packed.device).cuda_stream))
+                                                         _stream(packed.device))
         _lib.check(rc, "fastmax_hip_nf4_dequantize_s")
         return out.view(shape)
     code = NF4_CODE.to(packed.device)
@@ -288,8 +289,6 @@ def _announce_once(key: str, msg: str) -> None:
 # ---------------------------------------------------------------------------------------------
 # the fused op
 # ---------------------------------------------------------------------------------------------
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 # Above this many rows of x the frozen weight is decoded ONCE into dense bf16 (HIP kernel; kept resident across passes within
@@ -493,7 +492,7 @@ def lora_up_(y: torch.Tensor, e: torch.Tensor, bn: torch.Tensor, bias=None, tran
     return y
 
 
-_KDT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+_KDT = {t: _DT[t] for t in (torch.float32, torch.bfloat16)}          # the scatter kernels take these two
 
 
 class _ScatterRowsFn(torch.autograd.Function):

@@ -51,6 +51,31 @@ def _ws(nbytes, dev):
     return buf, ctypes.c_void_p(buf.data_ptr())
 
 
+def _qkv(*tensors):
+    """(address, strides) of each tensor, flat: the way the C ABI takes q, k, v and grad_o"""
+    return tuple(a for t in tensors for a in (t.data_ptr(), _strides(t)))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _call(name, dev, args, ws=None, tail=(), not_covered=()):
+    """``name(*args[, workspace, its size], *tail, stream)`` on ``dev``'s current stream, with ``ws`` bytes of fresh workspace
+    when a size is given.  -> (True, the workspace tensor or None), or (False, None) when the library answers with one of the
+    codes in ``not_covered``; any other code but 0 raises."""
+    wsb, wsargs = None, ()
+    if ws is not None:
+        wsb, wsp = _ws(ws, dev)
+        wsargs = (wsp, ws)
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*args, *wsargs, *tail, _stream(dev))
+    if rc in not_covered:
+        return False, None
+    _lib.check(rc, name)
+    return True, wsb
+
+
 def _problem(q, k, in_dt, out_dt, p, causal, nt, g0):
     B, H, Nq, D = q.shape
     return _lib.Problem(B, H, Nq, k.shape[2], D, _DT[in_dt], _DT[out_dt], int(p), int(causal), 1.0 / nt,
@@ -84,19 +109,17 @@ def forward(q, k, v, p, causal, nt, g0, out_dtype, need_g=True, keep_states=Fals
     prob = _problem(q, k, q.dtype, out_dtype, p, causal, nt, g0)
     o = torch.empty((B, H, Nq, D), dtype=out_dtype, device=dev)
     g = torch.empty((B, H, Nq), dtype=torch.float32, device=dev) if need_g else None
-    wsb, wsp = _ws(L.fastmax_hip_forward_workspace(ctypes.byref(prob)), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_forward(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                   v.data_ptr(), _strides(v), o.data_ptr(), g.data_ptr() if need_g else None,
-                                   wsp, wsb.numel() if wsb is not None else 0, _stream(dev))
-    _lib.check(rc, "fastmax_hip_forward")
-    if keep_states:
-        nb = 0
-        if KEEP_STATES and wsb is not None:
-            nb = L.fastmax_hip_forward_state_bytes(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                                   v.data_ptr(), _strides(v), o.data_ptr())
-        return o, g, (wsb if 0 < nb <= wsb.numel() else None)
-    return o, g
+    _, wsb = _call("fastmax_hip_forward", dev, (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), _ptr(g)),
+                   ws=L.fastmax_hip_forward_workspace(ctypes.byref(prob)))
+    return (o, g, _kept_states(prob, q, k, v, o, wsb)) if keep_states else (o, g)
+
+
+def _kept_states(prob, q, k, v, o, wsb):
+    """the forward's workspace when it holds the sequence split's prefix states for this call, else None"""
+    if not KEEP_STATES or wsb is None:
+        return None
+    nb = _lib.lib().fastmax_hip_forward_state_bytes(ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr())
+    return wsb if 0 < nb <= wsb.numel() else None
 
 
 def backward(q, k, v, o, g, grad_o, p, causal, nt, states=None):
@@ -106,15 +129,9 @@ def backward(q, k, v, o, g, grad_o, p, causal, nt, states=None):
     dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
     dk = torch.empty(k.shape, dtype=q.dtype, device=dev)
     dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_backward_workspace(ctypes.byref(prob)), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_backward_with_states(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                                v.data_ptr(), _strides(v), o.data_ptr(), g.data_ptr(), grad_o.data_ptr(),
-                                                _strides(grad_o), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), wsp,
-                                                wsb.numel() if wsb is not None else 0,
-                                                None if states is None else states.data_ptr(),
-                                                0 if states is None else states.numel(), _stream(dev))
-    _lib.check(rc, "fastmax_hip_backward_with_states")
+    _call("fastmax_hip_backward_with_states", dev,
+          (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), g.data_ptr(), *_qkv(grad_o), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()),
+          ws=L.fastmax_hip_backward_workspace(ctypes.byref(prob)), tail=(_ptr(states), 0 if states is None else states.numel()))
     return dq, dk, dv
 
 
@@ -127,11 +144,8 @@ def normalize(x):
         raise NotImplementedError(f"head size {D} > {MAX_HEAD_SIZE} is not supported by the HIP kernels")
     y = torch.empty((B, H, N, D), dtype=torch.float32, device=dev)
     inv = torch.empty((B, H), dtype=torch.float32, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_normalize_workspace(B, H), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_normalize(x.data_ptr(), _strides(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H, N,
-                                     D, wsp, wsb.numel(), _stream(dev))
-    _lib.check(rc, "fastmax_hip_normalize")
+    _call("fastmax_hip_normalize", dev, (*_qkv(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H, N, D),
+          ws=L.fastmax_hip_normalize_workspace(B, H))
     return y, inv
 
 
@@ -145,18 +159,13 @@ def normalize_cast(x, rep=1):
     y = torch.empty((B, H * rep, N, D), dtype=x.dtype, device=dev)
     inv = torch.empty((B, H), dtype=torch.float32, device=dev)
     # room for one word per 256-token block of every head: the two-launch form (see include/fastmax_hip.h)
-    wsb, wsp = _ws(max(L.fastmax_hip_normalize_workspace(B, H), 4 * B * H * ((N + 255) // 256)), dev)
-    with torch.cuda.device(dev):
-        if rep == 1:
-            rc = L.fastmax_hip_normalize_cast(x.data_ptr(), _strides(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H, N, D,
-                                              wsp, wsb.numel(), _stream(dev))
-        else:
-            rc = L.fastmax_hip_normalize_cast_expand(x.data_ptr(), _strides(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H,
-                                                     rep, N, D, wsp, wsb.numel(), _stream(dev))
-    if rc == _lib.E_BAD_SHAPE:
-        return None
-    _lib.check(rc, "fastmax_hip_normalize_cast")
-    return y, inv
+    ws = max(L.fastmax_hip_normalize_workspace(B, H), 4 * B * H * ((N + 255) // 256))
+    args = (*_qkv(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H)
+    if rep == 1:
+        ok, _ = _call("fastmax_hip_normalize_cast", dev, args + (N, D), ws=ws, not_covered=(_lib.E_BAD_SHAPE,))
+    else:
+        ok, _ = _call("fastmax_hip_normalize_cast_expand", dev, args + (rep, N, D), ws=ws, not_covered=(_lib.E_BAD_SHAPE,))
+    return (y, inv) if ok else None
 
 
 def normalize_backward(x, gy, inv, rep=1):
@@ -166,15 +175,12 @@ def normalize_backward(x, gy, inv, rep=1):
     B, H, N, D = x.shape
     gy = gy.to(x.dtype).contiguous()
     gx = torch.empty((B, H, N, D), dtype=x.dtype, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_normalize_backward_workspace(B, H * rep, N), dev)
-    with torch.cuda.device(dev):
-        if rep == 1:
-            rc = L.fastmax_hip_normalize_backward(x.data_ptr(), _strides(x), _DT[x.dtype], gy.data_ptr(), inv.data_ptr(),
-                                                  gx.data_ptr(), B, H, N, D, wsp, wsb.numel(), _stream(dev))
-        else:
-            rc = L.fastmax_hip_normalize_backward_expand(x.data_ptr(), _strides(x), _DT[x.dtype], gy.data_ptr(), inv.data_ptr(),
-                                                         gx.data_ptr(), B, H, rep, N, D, wsp, wsb.numel(), _stream(dev))
-    _lib.check(rc, "fastmax_hip_normalize_backward")
+    ws = L.fastmax_hip_normalize_backward_workspace(B, H * rep, N)
+    args = (*_qkv(x), _DT[x.dtype], gy.data_ptr(), inv.data_ptr(), gx.data_ptr(), B, H)
+    if rep == 1:
+        _call("fastmax_hip_normalize_backward", dev, args + (N, D), ws=ws)
+    else:
+        _call("fastmax_hip_normalize_backward_expand", dev, args + (rep, N, D), ws=ws)
     return gx
 
 
@@ -184,11 +190,7 @@ def normalize_stats(x):
     dev = x.device
     B, H, N, D = x.shape
     inv = torch.empty((B, H), dtype=torch.float32, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_normalize_workspace(B, H), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_normalize_stats(x.data_ptr(), _strides(x), _DT[x.dtype], inv.data_ptr(), B, H, N, D, wsp,
-                                           wsb.numel(), _stream(dev))
-    _lib.check(rc, "fastmax_hip_normalize_stats")
+    _call("fastmax_hip_normalize_stats", dev, (*_qkv(x), _DT[x.dtype], inv.data_ptr(), B, H, N, D), ws=L.fastmax_hip_normalize_workspace(B, H))
     return inv
 
 
@@ -201,11 +203,8 @@ def normalize_stats_pair(q, k):
     B, H, N, D = q.shape
     qi = torch.empty((B, H), dtype=torch.float32, device=dev)
     ki = torch.empty((B, H), dtype=torch.float32, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_normalize_stats2_workspace(B, H, N), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_normalize_stats2(q.data_ptr(), _strides(q), k.data_ptr(), _strides(k), _DT[q.dtype], qi.data_ptr(),
-                                            ki.data_ptr(), B, H, N, D, wsp, wsb.numel(), _stream(dev))
-    _lib.check(rc, "fastmax_hip_normalize_stats2")
+    _call("fastmax_hip_normalize_stats2", dev, (*_qkv(q, k), _DT[q.dtype], qi.data_ptr(), ki.data_ptr(), B, H, N, D),
+          ws=L.fastmax_hip_normalize_stats2_workspace(B, H, N))
     return qi, ki
 
 
@@ -229,22 +228,15 @@ def linearmax_forward_fused(q, k, v, return_stats=False, train=False):
     nstar = torch.full((2, B * H), -1, dtype=torch.int32, device=dev) if train else None
     o = torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
     g = torch.empty((B, H, N), dtype=torch.float32, device=dev) if train else None
-    wsb, wsp = _ws(L.fastmax_hip_linearmax_forward_auto_workspace(ctypes.byref(prob)), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_linearmax_forward_auto(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                                  v.data_ptr(), _strides(v), stats[0].data_ptr(), stats[1].data_ptr(),
-                                                  nstar[0].data_ptr() if train else None, nstar[1].data_ptr() if train else None,
-                                                  o.data_ptr(), g.data_ptr() if train else None, wsp,
-                                                  wsb.numel() if wsb is not None else 0, _stream(dev))
-    if rc in (-2, -5):          # FASTMAX_E_BAD_SHAPE / _ALIGNMENT: not covered by the fused kernel
+    nq, nk = (nstar[0].data_ptr(), nstar[1].data_ptr()) if train else (None, None)
+    ok, wsb = _call("fastmax_hip_linearmax_forward_auto", dev,
+                    (ctypes.byref(prob), *_qkv(q, k, v), stats[0].data_ptr(), stats[1].data_ptr(), nq, nk, o.data_ptr(), _ptr(g)),
+                    ws=L.fastmax_hip_linearmax_forward_auto_workspace(ctypes.byref(prob)),
+                    not_covered=(_lib.E_BAD_SHAPE, _lib.E_ALIGNMENT))          # not covered by the fused kernel
+    if not ok:
         return None
-    _lib.check(rc, "fastmax_hip_linearmax_forward_auto")
     if train:
-        nb = 0
-        if KEEP_STATES and wsb is not None:
-            nb = L.fastmax_hip_forward_state_bytes(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                                   v.data_ptr(), _strides(v), o.data_ptr())
-        return o, g, stats[0], stats[1], (wsb if 0 < nb <= wsb.numel() else None), nstar
+        return o, g, stats[0], stats[1], _kept_states(prob, q, k, v, o, wsb), nstar
     return (o, stats[0], stats[1]) if return_stats else o
 
 
@@ -259,17 +251,12 @@ def linearmax_backward(q, k, v, o, g, grad_o, inv_q, inv_k, states=None, nstar=N
     dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
     dk = torch.empty(q.shape, dtype=q.dtype, device=dev)
     dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
-    wsb, wsp = _ws(L.fastmax_hip_backward_workspace(ctypes.byref(prob)), dev)
-    with torch.cuda.device(dev):
-        rc = L.fastmax_hip_linearmax_backward(ctypes.byref(prob), q.data_ptr(), _strides(q), k.data_ptr(), _strides(k),
-                                              v.data_ptr(), _strides(v), o.data_ptr(), g.data_ptr(), grad_o.data_ptr(),
-                                              _strides(grad_o), inv_q.data_ptr(), inv_k.data_ptr(),
-                                              None if nstar is None else nstar[0].data_ptr(),
-                                              None if nstar is None else nstar[1].data_ptr(), dq.data_ptr(), dk.data_ptr(),
-                                              dv.data_ptr(), wsp, wsb.numel() if wsb is not None else 0,
-                                              None if states is None else states.data_ptr(),
-                                              0 if states is None else states.numel(), 0 if nstar is None else fuse, _stream(dev))
-    _lib.check(rc, "fastmax_hip_linearmax_backward")
+    nq, nk = (None, None) if nstar is None else (nstar[0].data_ptr(), nstar[1].data_ptr())
+    _call("fastmax_hip_linearmax_backward", dev,
+          (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), g.data_ptr(), *_qkv(grad_o), inv_q.data_ptr(), inv_k.data_ptr(), nq, nk,
+           dq.data_ptr(), dk.data_ptr(), dv.data_ptr()),
+          ws=L.fastmax_hip_backward_workspace(ctypes.byref(prob)),
+          tail=(_ptr(states), 0 if states is None else states.numel(), 0 if nstar is None else fuse))
     return dq, dk, dv
 
 
@@ -309,11 +296,9 @@ def rope_qkv_backward(gq, gk, gv, cos32, sin32, B, T, G, qpk, hs, rope_n, kern_e
     kern_expand 1 / 2: k, v (or v) arrive per query head and are summed over their group while they are read)"""
     gq, gk, gv = gq.contiguous(), gk.contiguous(), gv.contiguous()
     gqkv = torch.empty((B, T, G, qpk + 2, hs), dtype=gq.dtype, device=gq.device)
-    with torch.cuda.device(gq.device):
-        rc = _lib.lib().fastmax_hip_rope_qkv_split_backward(gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), cos32.data_ptr(),
-                                                            sin32.data_ptr(), gqkv.data_ptr(), B, T, G, qpk, hs, rope_n, kern_expand,
-                                                            _DT[gq.dtype], _stream(gq.device))
-    _lib.check(rc, "fastmax_hip_rope_qkv_split_backward")
+    _call("fastmax_hip_rope_qkv_split_backward", gq.device,
+          (gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), cos32.data_ptr(), sin32.data_ptr(), gqkv.data_ptr(), B, T, G, qpk, hs, rope_n,
+           kern_expand, _DT[gq.dtype]))
     return gqkv
 
 
@@ -332,7 +317,6 @@ class RopeQKVSplit(torch.autograd.Function):
              group indexing, so every query head of a group reads the same K, V rows; the gradients then arrive per
              query head and the backward pass sums them over the group while it reads them
           4  k stays (B,G,T,hs) (for the linearmax prologue, which normalises per key head), q and v as in 3"""
-        L = _lib.lib()
         B, T, G, total, hs = qkv.shape
         qpk = total - 2
         qkv = qkv.contiguous()
@@ -345,11 +329,9 @@ class RopeQKVSplit(torch.autograd.Function):
         q = torch.empty((B, G * qpk, T, hs), dtype=qkv.dtype, device=qkv.device)
         k = torch.empty((B, G * qpk if k_copies else G, T, hs), dtype=qkv.dtype, device=qkv.device)
         v = torch.empty((B, G * qpk if v_copies else G, T, hs), dtype=qkv.dtype, device=qkv.device)
-        with torch.cuda.device(qkv.device):
-            rc = L.fastmax_hip_rope_qkv_split(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), q.data_ptr(), k.data_ptr(),
-                                              v.data_ptr(), B, T, G, qpk, hs, rope_n_elem, kern_expand | tables16, _DT[qkv.dtype],
-                                              _stream(qkv.device))
-        _lib.check(rc, "fastmax_hip_rope_qkv_split")
+        _call("fastmax_hip_rope_qkv_split", qkv.device,
+              (qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), B, T, G, qpk, hs, rope_n_elem,
+               kern_expand | tables16, _DT[qkv.dtype]))
         ctx.save_for_backward(cos, sin)
         ctx.dims = (B, T, G, qpk, hs, rope_n_elem, int(expand))
         if expand in (3, 4):
@@ -360,17 +342,10 @@ class RopeQKVSplit(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gq, gk, gv):
-        L = _lib.lib()
         cos, sin = ctx.saved_tensors
         B, T, G, qpk, hs, rope_n_elem, expand = ctx.dims
         # modes 3 / 4: gradients of the stride-0 views arrive dense, one per query head, laid out (B*G, qpk, T, hs) =
         # (B, H, T, hs): exactly what the kernel's group-summing read expects for copied heads
         kern_expand = {0: 0, 1: 1, 2: 2, 3: 1, 4: 2}[expand]
-        gq, gk, gv = gq.contiguous(), gk.contiguous(), gv.contiguous()
-        gqkv = torch.empty((B, T, G, qpk + 2, hs), dtype=gq.dtype, device=gq.device)
-        with torch.cuda.device(gq.device):
-            rc = L.fastmax_hip_rope_qkv_split_backward(gq.data_ptr(), gk.data_ptr(), gv.data_ptr(), cos.data_ptr(), sin.data_ptr(),
-                                                       gqkv.data_ptr(), B, T, G, qpk, hs, rope_n_elem, kern_expand, _DT[gq.dtype],
-                                                       _stream(gq.device))
-        _lib.check(rc, "fastmax_hip_rope_qkv_split_backward")
+        gqkv = rope_qkv_backward(gq, gk, gv, cos, sin, B, T, G, qpk, hs, rope_n_elem, kern_expand)
         return gqkv, None, None, None, None
