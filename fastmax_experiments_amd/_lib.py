@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("FASTMAX_LIB_PATH") or os.path.join(HERE, "libfastmax_
 F32, BF16, F16 = 0, 1, 2
 PATH_AUTO, PATH_QUADRATIC, PATH_RECURRENT, PATH_MFMA, PATH_QUADRATIC_MFMA = 0, 1, 2, 3, 4
 PATH_NAMES = {PATH_AUTO: "auto", PATH_QUADRATIC: "quadratic", PATH_RECURRENT: "recurrent", PATH_MFMA: "mfma", PATH_QUADRATIC_MFMA: "quadratic_mfma"}
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK, E_BAD_P, E_BAD_SHAPE, E_BAD_DTYPE, E_WORKSPACE, E_ALIGNMENT, E_NULL = 0, -1, -2, -3, -4, -5, -6      # enum fastmax_error
 
 
@@ -24,8 +24,19 @@ class Problem(ctypes.Structure):
                 ("path", ctypes.c_int)]
 
 
+class Plan(ctypes.Structure):
+    """struct fastmax_plan: what fastmax_hip_plan reports"""
+    _fields_ = [("rc", ctypes.c_int), ("path", ctypes.c_int), ("fwd_kernel", ctypes.c_int), ("bwd_kernel", ctypes.c_int),
+                ("nseg", ctypes.c_int), ("state_bytes", ctypes.c_size_t)]
+
+
+# enum fastmax_fwd_kernel / fastmax_bwd_kernel, by number
+FWD_KERNELS = ["FWD_QUADRATIC", "FWD_RECURRENT", "FWD_UNMASKED_LIN", "FWD_SCAN_V2", "FWD_SCAN_D128_2P", "FWD_SCAN_BF16", "FWD_SCAN_GEN",
+               "FWD_QUAD32", "FWD_QUAD_MFMA"]
+BWD_KERNELS = ["BWD_QUADRATIC", "BWD_UNMASKED_LIN", "BWD_LIN", "BWD_SCAN", "BWD_QUAD32", "BWD_QUAD_MFMA"]
+
 vp, sz, ci, i64, cf, cs = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p
-i64p, pp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Problem)
+i64p, pp, planp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Problem), ctypes.POINTER(Plan)
 QKV = [vp, i64p, vp, i64p, vp, i64p]          # q, q_strides, k, k_strides, v, v_strides
 BWD = [pp] + QKV + [vp, vp, vp, i64p]         # ..., o, g, grad_o, go_strides
 NF4 = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
@@ -41,6 +52,7 @@ ABI = {
     "fastmax_hip_backward": (ci, BWD + [vp, vp, vp, vp, sz, vp]),
     "fastmax_hip_forward_state_bytes": (sz, [pp] + QKV + [vp]),
     "fastmax_hip_backward_with_states": (ci, BWD + [vp, vp, vp, vp, sz, vp, sz, vp]),
+    "fastmax_hip_plan": (ci, [pp] + QKV + [vp, vp, i64p, vp, vp, vp, planp]),
     "fastmax_hip_normalize_workspace": (sz, [ci, ci]),
     "fastmax_hip_normalize": (ci, [vp, i64p, ci, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
     "fastmax_hip_normalize_stats": (ci, [vp, i64p, ci, vp, ci, ci, ci, ci, vp, sz, vp]),

@@ -76,18 +76,16 @@ int scan_dp(const fastmax_problem& p) { return p.D <= 64 ? 64 : 128; }
 // bytes of prefix states a split scan leaves at the start of its workspace (0: this problem is not split)
 size_t scan_state_bytes(const fastmax_problem& p) { return split_workspace_bytes(p, scan_dp(p)); }
 
-enum FwdKernel {
-    FWD_QUADRATIC, FWD_RECURRENT, FWD_UNMASKED_LIN, FWD_SCAN_V2, FWD_SCAN_D128_2P, FWD_SCAN_BF16, FWD_SCAN_GEN, FWD_QUAD32, FWD_QUAD_MFMA
-};
+using FwdKernel = fastmax_fwd_kernel;          // numbered in include/fastmax_hip.h: fastmax_hip_plan reports them
 // the scan kernel of a p = 1 masked problem whose q, k may carry the linearmax scales (the headline kernel takes none)
 FwdKernel scan_kernel(const fastmax_problem& p) {
-    if (mfma_d128_2p_supported(p)) return FWD_SCAN_D128_2P;
-    return use_bf16_kernel(p) ? FWD_SCAN_BF16 : FWD_SCAN_GEN;
+    if (mfma_d128_2p_supported(p)) return FASTMAX_FWD_SCAN_D128_2P;
+    return use_bf16_kernel(p) ? FASTMAX_FWD_SCAN_BF16 : FASTMAX_FWD_SCAN_GEN;
 }
 int launch_fwd_scan(const FwdArgs& a, const float* qscale, const float* kscale) {
     switch (scan_kernel(a.prob)) {
-        case FWD_SCAN_D128_2P: return launch_fwd_mfma_d128_2p(a, qscale, kscale);
-        case FWD_SCAN_BF16: return launch_fwd_mfma_bf16(a, qscale, kscale);
+        case FASTMAX_FWD_SCAN_D128_2P: return launch_fwd_mfma_d128_2p(a, qscale, kscale);
+        case FASTMAX_FWD_SCAN_BF16: return launch_fwd_mfma_bf16(a, qscale, kscale);
         default: return launch_fwd_mfma_gen(a, qscale, kscale);
     }
 }
@@ -101,7 +99,7 @@ struct FwdPlan {
     size_t workspace, state_bytes;
 };
 FwdPlan fwd_plan(const fastmax_problem& p, unsigned lay) {
-    FwdPlan f{FASTMAX_OK, select(p), FWD_QUADRATIC, 0, 0};
+    FwdPlan f{FASTMAX_OK, select(p), FASTMAX_FWD_QUADRATIC, 0, 0};
     if (f.path < 0) {
         f.rc = f.path;
         return f;
@@ -116,34 +114,34 @@ FwdPlan fwd_plan(const fastmax_problem& p, unsigned lay) {
     switch (f.path) {
         case FASTMAX_PATH_MFMA:
             if (!p.causal) {
-                f.kernel = FWD_UNMASKED_LIN;
+                f.kernel = FASTMAX_FWD_UNMASKED_LIN;
                 f.workspace = unmasked_lin_workspace(p);
             } else {
-                f.kernel = mfma_p1_supported(p) ? FWD_SCAN_V2 : scan_kernel(p);
+                f.kernel = mfma_p1_supported(p) ? FASTMAX_FWD_SCAN_V2 : scan_kernel(p);
                 f.workspace = f.state_bytes = scan_state_bytes(p);
             }
             break;
-        case FASTMAX_PATH_RECURRENT: f.kernel = FWD_RECURRENT; break;
-        case FASTMAX_PATH_QUADRATIC_MFMA: f.kernel = quad32_supported(p) ? FWD_QUAD32 : FWD_QUAD_MFMA; break;
+        case FASTMAX_PATH_RECURRENT: f.kernel = FASTMAX_FWD_RECURRENT; break;
+        case FASTMAX_PATH_QUADRATIC_MFMA: f.kernel = quad32_supported(p) ? FASTMAX_FWD_QUAD32 : FASTMAX_FWD_QUAD_MFMA; break;
         default: break;
     }
     return f;
 }
 
-enum BwdKernel { BWD_QUADRATIC, BWD_UNMASKED_LIN, BWD_LIN, BWD_SCAN, BWD_QUAD32, BWD_QUAD_MFMA };
+using BwdKernel = fastmax_bwd_kernel;
 BwdKernel bwd_select(const fastmax_problem& p, unsigned lay) {
     // matrix-core tiles unless the caller forces the vector-ALU family or the layout rules it out
-    if (p.path == FASTMAX_PATH_QUADRATIC || !quad_mfma_bwd_supported(p) || !has(lay, LAY_BWD_TILES)) return BWD_QUADRATIC;
+    if (p.path == FASTMAX_PATH_QUADRATIC || !quad_mfma_bwd_supported(p) || !has(lay, LAY_BWD_TILES)) return FASTMAX_BWD_QUADRATIC;
     // the linear-time kernels, unless the caller asks for the tile kernels; they also read o in 16-byte pieces
     if (p.path != FASTMAX_PATH_QUADRATIC_MFMA && has(lay, LAY_O)) {
         // p=1 unmasked at sizes where totals + row-wise D x D products beat the O(N_q N_k) tiles
-        if (unmasked_lin_bwd_supported(p)) return BWD_UNMASKED_LIN;
+        if (unmasked_lin_bwd_supported(p)) return FASTMAX_BWD_UNMASKED_LIN;
         // p=1 masked: scans with a carried D x D state
-        if (lin_bwd_supported(p) && p.in_dtype == p.out_dtype) return BWD_LIN;
+        if (lin_bwd_supported(p) && p.in_dtype == p.out_dtype) return FASTMAX_BWD_LIN;
         // fp32 / fp16 at 64 < D <= 128: the same scans with two-part operands, one per gradient (fastmax_scan_d128_2p.hip)
-        if (scan_bwd_supported(p)) return BWD_SCAN;
+        if (scan_bwd_supported(p)) return FASTMAX_BWD_SCAN;
     }
-    return quad32_bwd_supported(p) ? BWD_QUAD32 : BWD_QUAD_MFMA;
+    return quad32_bwd_supported(p) ? FASTMAX_BWD_QUAD32 : FASTMAX_BWD_QUAD_MFMA;
 }
 
 // null / shape / workspace checks of the normalize family, in the order every entry point applies them
@@ -262,15 +260,15 @@ int fastmax_hip_forward(const fastmax_problem* prob, const void* q, const int64_
     FwdArgs a{*prob, q, k, v, st(q_strides), st(k_strides), st(v_strides), o, g, workspace, workspace_bytes,
               reinterpret_cast<hipStream_t>(stream)};
     switch (plan.kernel) {
-        case FWD_UNMASKED_LIN: return launch_fwd_unmasked_p1(a);
-        case FWD_SCAN_V2: return launch_fwd_mfma_p1(a);
-        case FWD_SCAN_D128_2P:
-        case FWD_SCAN_BF16:
-        case FWD_SCAN_GEN: return launch_fwd_scan(a, nullptr, nullptr);
-        case FWD_RECURRENT: return launch_fwd_recurrent_p1(a);
-        case FWD_QUAD32: return launch_fwd_quad32(a);
-        case FWD_QUAD_MFMA: return launch_fwd_quad_mfma(a);
-        case FWD_QUADRATIC: break;
+        case FASTMAX_FWD_UNMASKED_LIN: return launch_fwd_unmasked_p1(a);
+        case FASTMAX_FWD_SCAN_V2: return launch_fwd_mfma_p1(a);
+        case FASTMAX_FWD_SCAN_D128_2P:
+        case FASTMAX_FWD_SCAN_BF16:
+        case FASTMAX_FWD_SCAN_GEN: return launch_fwd_scan(a, nullptr, nullptr);
+        case FASTMAX_FWD_RECURRENT: return launch_fwd_recurrent_p1(a);
+        case FASTMAX_FWD_QUAD32: return launch_fwd_quad32(a);
+        case FASTMAX_FWD_QUAD_MFMA: return launch_fwd_quad_mfma(a);
+        case FASTMAX_FWD_QUADRATIC: break;
     }
     return launch_fwd_quadratic(a);
 }
@@ -308,12 +306,12 @@ int fastmax_hip_backward_with_states(const fastmax_problem* prob, const void* q,
     if (fwd_states && fwd_state_bytes > 0 && fwd_state_bytes >= (fwd.rc ? 0 : fwd.state_bytes) && !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
         a.fwd_states = reinterpret_cast<const float*>(fwd_states);
     switch (bwd_select(*prob, lay)) {
-        case BWD_UNMASKED_LIN: return launch_bwd_unmasked_p1(a);
-        case BWD_LIN: return launch_bwd_lin(a);
-        case BWD_SCAN: return launch_bwd_scan(a);
-        case BWD_QUAD32: return launch_bwd_quad32(a);
-        case BWD_QUAD_MFMA: return launch_bwd_quad_mfma(a);
-        case BWD_QUADRATIC: break;
+        case FASTMAX_BWD_UNMASKED_LIN: return launch_bwd_unmasked_p1(a);
+        case FASTMAX_BWD_LIN: return launch_bwd_lin(a);
+        case FASTMAX_BWD_SCAN: return launch_bwd_scan(a);
+        case FASTMAX_BWD_QUAD32: return launch_bwd_quad32(a);
+        case FASTMAX_BWD_QUAD_MFMA: return launch_bwd_quad_mfma(a);
+        case FASTMAX_BWD_QUADRATIC: break;
     }
     return launch_bwd_quadratic(a);
 }
@@ -324,6 +322,38 @@ int fastmax_hip_backward(const fastmax_problem* prob, const void* q, const int64
                          void* workspace, size_t workspace_bytes, void* stream) {
     return fastmax_hip_backward_with_states(prob, q, q_strides, k, k_strides, v, v_strides, o, g, grad_o, go_strides, dq, dk, dv, workspace,
                                             workspace_bytes, nullptr, 0, stream);
+}
+
+// what fastmax_hip_forward and fastmax_hip_backward_with_states would decide for these operands, from the functions they
+// call themselves; addresses and strides are only looked at, nothing is read through them and nothing is launched
+int fastmax_hip_plan(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides,
+                     const void* v, const int64_t* v_strides, const void* o, const void* grad_o, const int64_t* go_strides,
+                     const void* dq, const void* dk, const void* dv, fastmax_plan* out) {
+    if (!out) return FASTMAX_E_NULL;
+    *out = fastmax_plan{FASTMAX_OK, -1, -1, -1, 1, 0};
+    const bool with_bwd = grad_o || go_strides || dq || dk || dv;
+    out->rc = validate(prob);
+    if (!out->rc && (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides ||
+                     (with_bwd && (!grad_o || !go_strides || !dq || !dk || !dv))))
+        out->rc = FASTMAX_E_NULL;
+    if (out->rc) return out->rc;
+    const unsigned lay = with_bwd ? layout(*prob, q, q_strides, k, k_strides, v, v_strides, o, grad_o, go_strides, dq, dk, dv)
+                                  : layout(*prob, q, q_strides, k, k_strides, v, v_strides, o);
+    const FwdPlan fwd = fwd_plan(*prob, lay);
+    out->rc = fwd.rc;
+    bool split = false;
+    if (!fwd.rc) {
+        out->path = fwd.path;
+        out->fwd_kernel = fwd.kernel;
+        out->state_bytes = fwd.state_bytes;
+        split = fwd.path == FASTMAX_PATH_MFMA && prob->causal;
+    }
+    if (with_bwd) {          // the backward does not ask whether the forward was accepted
+        out->bwd_kernel = bwd_select(*prob, lay);
+        split = split || out->bwd_kernel == FASTMAX_BWD_LIN;
+    }
+    if (split) out->nseg = split_plan(*prob).nseg;
+    return out->rc;
 }
 
 size_t fastmax_hip_normalize_workspace(int B, int H) { return sizeof(unsigned int) * (size_t)B * H; }

@@ -89,6 +89,28 @@ def selected_path(q, k, p, causal, nt=1.0):
     return _lib.lib().fastmax_hip_select_path(ctypes.byref(prob))
 
 
+def planned_kernels(q, k, v, p, causal, o=None, grad_o=None, nt=1.0):
+    """What forward() -- and with ``grad_o`` also backward() -- would launch for these tensors (fastmax_hip_plan; nothing runs).
+    -> dict(rc, path, fwd_kernel, bwd_kernel, nseg, state_bytes) with the kernels by name (``_lib.FWD_KERNELS`` /
+    ``BWD_KERNELS``; None: rejected, or no backward asked for).  Tensors are taken as forward() takes them; o and the
+    gradients, which forward() and backward() allocate themselves, count as aligned unless ``o`` is given."""
+    dev = q.device
+    in_dt = q.dtype if q.dtype in _DT else torch.float32
+    out_dt = o.dtype if o is not None else (in_dt if causal else torch.float32)          # dtype rule Q1
+    q, k, v = (_prep(t, dev) for t in (q, k, v))
+    prob = _problem(q, k, in_dt, out_dt, p, causal, nt, float(q.shape[2]))
+    fresh = 256          # stands for a fresh allocation: only the alignment of an address is looked at
+    bwd = (None,) * 5 if grad_o is None else (*_qkv(_prep(grad_o, dev)), fresh, fresh, fresh)
+    plan = _lib.Plan()
+    _lib.lib().fastmax_hip_plan(ctypes.byref(prob), *_qkv(q, k, v), fresh if o is None else o.data_ptr(), *bwd, ctypes.byref(plan))
+
+    def name(names, i):
+        return names[i] if i >= 0 else None
+
+    return dict(rc=plan.rc, path=plan.path, fwd_kernel=name(_lib.FWD_KERNELS, plan.fwd_kernel),
+                bwd_kernel=name(_lib.BWD_KERNELS, plan.bwd_kernel), nseg=plan.nseg, state_bytes=plan.state_bytes)
+
+
 KEEP_STATES = os.environ.get("FASTMAX_KEEP_STATES", "1") != "0"
 
 

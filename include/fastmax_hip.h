@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FASTMAX_ABI_VERSION 8   /* 8: the lmhead_ce_* and debug_gemm_stamps entry points are gone: the head's two products are plain library GEMMs by decision, see DESIGN.md, and the losing GEMM loop variants were removed; + fastmax_hip_tune_get, fastmax_hip_build_flags, fastmax_hip_normalize_stats2(_workspace), fastmax_hip_lora_{down,tn,up}_dropout, fastmax_hip_lora_dropout_mask, fastmax_hip_linearmax_forward_auto(_workspace), fastmax_hip_linearmax_backward, fastmax_hip_linearmax_train_supported; 7: + qlora_gemm_rope; 6: + qlora_gemm, nf4_dequantize_transposed, lmhead_ce_*; 5: + nf4 *_s entry points (double-quantised block scales); 4: + fastmax_hip_tune; 2: + normalize_cast/backward, rope_qkv_split(_backward), cross_entropy_forward/backward; 3: + lora_down/tn/up/scatter, normalize_*_expand, forward_state_bytes, backward_with_states */
+#define FASTMAX_ABI_VERSION 9   /* 9: + fastmax_hip_plan (enum fastmax_fwd_kernel, enum fastmax_bwd_kernel, struct fastmax_plan); 8: the lmhead_ce_* and debug_gemm_stamps entry points are gone: the head's two products are plain library GEMMs by decision, see DESIGN.md, and the losing GEMM loop variants were removed; + fastmax_hip_tune_get, fastmax_hip_build_flags, fastmax_hip_normalize_stats2(_workspace), fastmax_hip_lora_{down,tn,up}_dropout, fastmax_hip_lora_dropout_mask, fastmax_hip_linearmax_forward_auto(_workspace), fastmax_hip_linearmax_backward, fastmax_hip_linearmax_train_supported; 7: + qlora_gemm_rope; 6: + qlora_gemm, nf4_dequantize_transposed, lmhead_ce_*; 5: + nf4 *_s entry points (double-quantised block scales); 4: + fastmax_hip_tune; 2: + normalize_cast/backward, rope_qkv_split(_backward), cross_entropy_forward/backward; 3: + lora_down/tn/up/scatter, normalize_*_expand, forward_state_bytes, backward_with_states */
 
 enum fastmax_dtype { FASTMAX_F32 = 0, FASTMAX_BF16 = 1, FASTMAX_F16 = 2 };
 
@@ -123,6 +123,49 @@ int fastmax_hip_backward_with_states(const fastmax_problem* prob,
                                      void* dq, void* dk, void* dv,
                                      void* workspace, size_t workspace_bytes,
                                      const void* fwd_states, size_t fwd_state_bytes, void* stream);
+
+/* ---- plan query: which kernel a call would launch.  Host arithmetic only: the operands are looked at as addresses and
+ *      strides, nothing is read through them and nothing is launched, so tests may pass made-up addresses.
+ *      The numbers are stable: new kernels are appended.                                                                  */
+enum fastmax_fwd_kernel {
+    FASTMAX_FWD_QUADRATIC = 0,     /* f(QK^T)V tiles on the vector ALU (fastmax_generic.hip): any p, mask, layout            */
+    FASTMAX_FWD_RECURRENT = 1,     /* p=1 masked, carried K^T V' state on the vector ALU (fastmax_generic.hip)                */
+    FASTMAX_FWD_UNMASKED_LIN = 2,  /* p=1 unmasked from totals: one pass over K, V + a D x D product per query row            */
+    FASTMAX_FWD_SCAN_V2 = 3,       /* p=1 masked chunked scan, fp32 D = 64: the headline kernel (fastmax_mfma_v2.hip)         */
+    FASTMAX_FWD_SCAN_D128_2P = 4,  /* p=1 masked scan, fp32 / fp16 at 64 < D <= 128, two-part operands                        */
+    FASTMAX_FWD_SCAN_BF16 = 5,     /* p=1 masked scan, bf16 D <= 128, all matrix-core (fastmax_mfma_bf16.hip)                 */
+    FASTMAX_FWD_SCAN_GEN = 6,      /* p=1 masked scan, generic: padded head sizes, fp16, fp32 D < 64 (fastmax_mfma_gen.hip)   */
+    FASTMAX_FWD_QUAD32 = 7,        /* matrix-core tiles, 32 x 32 x 16, N_q >= 256 (fastmax_quad32_mfma.hip)                   */
+    FASTMAX_FWD_QUAD_MFMA = 8      /* matrix-core tiles, 16 query rows per wave, D <= 256 (fastmax_quad_mfma.hip)             */
+};
+enum fastmax_bwd_kernel {
+    FASTMAX_BWD_QUADRATIC = 0,     /* vector-ALU tiles: forced, not covered by the matrix cores, or a misaligned operand      */
+    FASTMAX_BWD_UNMASKED_LIN = 1,  /* p=1 unmasked from totals and row-wise D x D products                                    */
+    FASTMAX_BWD_LIN = 2,           /* p=1 masked forward / reverse scans with a carried state (fastmax_mfma_bwd_lin.hip)      */
+    FASTMAX_BWD_SCAN = 3,          /* the same for fp32 / fp16 at 64 < D <= 128: one scan per gradient (fastmax_scan_d128_2p.hip) */
+    FASTMAX_BWD_QUAD32 = 4,        /* matrix-core tiles, 32 x 32 x 16, N_q, N_k >= 256 (fastmax_quad32_bwd.hip)               */
+    FASTMAX_BWD_QUAD_MFMA = 5      /* matrix-core tiles, 16 rows per wave (fastmax_quad_mfma_bwd.hip)                         */
+};
+typedef struct fastmax_plan {
+    int rc;              /* what the forward answers before it launches: 0, or the FASTMAX_E_* code it rejects the call with */
+    int path;            /* enum fastmax_path of the forward after the layout rules; -1 when rc != 0                         */
+    int fwd_kernel;      /* enum fastmax_fwd_kernel; -1 when rc != 0                                                         */
+    int bwd_kernel;      /* enum fastmax_bwd_kernel; -1 for a forward-only query                                             */
+    int nseg;            /* segments of the sequence split when fwd_kernel is one of the scans or bwd_kernel is
+                            FASTMAX_BWD_LIN (1: not split); FASTMAX_BWD_SCAN cuts the sequence by a rule of its own          */
+    size_t state_bytes;  /* what fastmax_hip_forward_state_bytes answers for these operands                                  */
+} fastmax_plan;
+/*      Operands as for fastmax_hip_forward (q .. o) and fastmax_hip_backward_with_states (grad_o .. dv); grad_o, go_strides, dq,
+ *      dk, dv all NULL asks about the forward only.  Fills *out and returns out->rc; a bad problem or a missing operand answers
+ *      with its code and leaves the kernels at -1.  The backward is planned whatever the forward answers, as the backward entry
+ *      points do.  The plan names the kernel the entry point hands the call to; two launchers then still step aside for slabs
+ *      beyond 31-bit offsets (the bf16 scan to the generic scan, the 32 x 32 backward tiles to the 16-row ones): not reported. */
+int fastmax_hip_plan(const fastmax_problem* prob,
+                     const void* q, const int64_t* q_strides,
+                     const void* k, const int64_t* k_strides,
+                     const void* v, const int64_t* v_strides, const void* o,
+                     const void* grad_o, const int64_t* go_strides,
+                     const void* dq, const void* dk, const void* dv, fastmax_plan* out);
 
 /* ---- linearmax prologue: replaces fastattention_einops.normalize (fastmax.py:326-334)
  *      == the inline copy at fastmax_hack.py:38-43 / 10-15: per token subtract the mean

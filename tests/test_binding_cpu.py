@@ -43,7 +43,7 @@ def header_prototypes():
 
 def test_parser_reads_the_header():
     protos = dict((n, (r, k)) for n, r, k in header_prototypes())
-    assert len(protos) == 58
+    assert len(protos) == 59
     assert protos["fastmax_hip_error_string"] == ("const char*", ["int"])
     assert protos["fastmax_hip_tune"] == ("int", ["const char*", "int"])
     assert protos["fastmax_hip_build_flags"] == ("int", [])

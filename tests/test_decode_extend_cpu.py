@@ -28,8 +28,8 @@ def test_symbols_exported_and_declared(lib):
     declared = set(re.findall(r"\b(fastmax_hip_[a-z0-9_]+)\s*\(", hdr))
     for s in NEW:
         assert s in declared and s in _lib.SYMBOLS and hasattr(lib, s), s
-    assert lib.fastmax_hip_abi_version() == 8
-    assert "#define FASTMAX_ABI_VERSION 8" in hdr
+    assert lib.fastmax_hip_abi_version() == 9
+    assert "#define FASTMAX_ABI_VERSION 9" in hdr
 
 
 def test_workspace_bytes(lib):

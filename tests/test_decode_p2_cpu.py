@@ -27,7 +27,7 @@ def test_symbols_exported_and_declared(lib):
     declared = set(re.findall(r"\b(fastmax_hip_[a-z0-9_]+)\s*\(", hdr))
     for s in P2:
         assert s in declared and s in _lib.SYMBOLS and hasattr(lib, s), s
-    assert lib.fastmax_hip_abi_version() == 8
+    assert lib.fastmax_hip_abi_version() == 9
 
 
 def test_state_bytes(lib):

@@ -317,6 +317,12 @@ def test_head_sizes_above_128(shape, p, mask, dt, tolf, tolb):
     for path in ("auto", "quadratic"):
         _force(path)
         qq, kk, vv = (t.cuda().requires_grad_(True) for t in (q, k, v))
+        plan = ops.planned_kernels(qq, kk, vv, p, mask, grad_o=go.cuda())
+        if path == "auto":
+            assert plan["fwd_kernel"] == "FWD_QUAD_MFMA"
+            assert plan["bwd_kernel"] == ("BWD_QUAD_MFMA" if dt == torch.bfloat16 else "BWD_QUADRATIC")
+        else:
+            assert (plan["fwd_kernel"], plan["bwd_kernel"]) == ("FWD_QUADRATIC", "BWD_QUADRATIC")
         o = fastmax(qq, kk, vv, mask=mask, p=p)
         assert rel_err(o.detach().float().cpu().numpy(), ro) < tolf, path
         o.backward(go.cuda().to(o.dtype))
@@ -340,6 +346,14 @@ def test_linear_time_matrix_core_kernel_dtypes_and_head_sizes(shape, dt, tol):
     # D <= 64: generic / bf16 kernels; 64 < D <= 128: the eight-wave kernels (bf16, and fp32 / fp16 with two-part operands)
     want = _lib.PATH_MFMA
     assert ops.selected_path(qq, kk, 1, True) == want
+    D = shape[3]
+    if dt == torch.bfloat16:
+        kernel = "FWD_SCAN_BF16"
+    elif D > 64:
+        kernel = "FWD_SCAN_D128_2P"
+    else:
+        kernel = "FWD_SCAN_V2" if (dt == torch.float32 and D == 64) else "FWD_SCAN_GEN"
+    assert ops.planned_kernels(qq, kk, vv, 1, True)["fwd_kernel"] == kernel
     o = fastmax(qq, kk, vv)
     assert o.dtype == dt
     ro, _ = c_oracle.fwd(q.float().numpy(), k.float().numpy(), v.float().numpy())
@@ -391,9 +405,12 @@ def test_sequence_split_for_few_heads(shape, dt, tol):
     """few heads -> the sequence is cut into segments (state kernel + prefix + main kernel): same result"""
     from attention_mechanisms.fastmax import fastmax
     from attention_mechanisms.fastmax_hack import fastmax_hack
+    from fastmax_experiments_amd import ops
     from oracle import fastmax_oracle as orc
     g = torch.Generator().manual_seed(shape[2])
     q, k, v = (torch.randn(shape, generator=g).to(dt) for _ in range(3))
+    plan = ops.planned_kernels(q.cuda(), k.cuda(), v.cuda(), 1, True)
+    assert plan["nseg"] > 1 and plan["state_bytes"] > 0 and plan["fwd_kernel"].startswith("FWD_SCAN_")
     o = fastmax(q.cuda(), k.cuda(), v.cuda())
     with torch.no_grad():
         oh = fastmax_hack(q.cuda(), k.cuda(), v.cuda())
@@ -435,6 +452,7 @@ def test_linearmax_statistics_ride_on_the_state_pass(shape, dt, tol):
 def test_linear_time_backward(shape, dt, tol):
     """p=1 masked backward by forward / reverse scans with carried state vs the float64 scans (block by block) and vs the tile kernels"""
     from attention_mechanisms.fastmax import fastmax
+    from fastmax_experiments_amd import ops
     from oracle import fastmax_oracle as orc
     g = torch.Generator().manual_seed(shape[2])
     q, k, v, go = (torch.randn(shape, generator=g).to(dt) for _ in range(4))
@@ -446,6 +464,8 @@ def test_linear_time_backward(shape, dt, tol):
     for path in ("auto", "quadratic_mfma"):
         _force(path)
         qq, kk, vv = (t.cuda().requires_grad_(True) for t in (q, k, v))
+        scans = "BWD_LIN" if (shape[3] <= 64 or dt == torch.bfloat16) else "BWD_SCAN"          # two-part operands: one scan per gradient
+        assert ops.planned_kernels(qq, kk, vv, 1, True, grad_o=go.cuda())["bwd_kernel"] == (scans if path == "auto" else "BWD_QUAD32")
         o = fastmax(qq, kk, vv)
         o.backward(go.cuda())
         grads[path] = [t.grad.float().cpu().numpy() for t in (qq, kk, vv)]
@@ -684,6 +704,7 @@ def test_wide_tile_kernels_forward_backward(shape, p, mask, dt, tf, tb):
     """quadratic family forced, sizes that route to fastmax_quad32_mfma.hip / fastmax_quad32_bwd.hip: ragged lengths,
     padded head sizes, head counts that are / are not a multiple of the 8 XCDs, N_q != N_k (unmasked)"""
     from attention_mechanisms.fastmax import fastmax
+    from fastmax_experiments_amd import ops
     from oracle import c_oracle
     B, H, Nq, Nk, D = shape
     g = torch.Generator().manual_seed(Nq + Nk + D + p)
@@ -691,6 +712,11 @@ def test_wide_tile_kernels_forward_backward(shape, p, mask, dt, tf, tb):
     k, v = (torch.randn(B, H, Nk, D, generator=g).to(dt) for _ in range(2))
     _force("quadratic_mfma")
     qq, kk, vv = (t.cuda().requires_grad_(True) for t in (q, k, v))
+    # the 32 x 32 tiles up to D = 128 (forward: two-part fp32 / fp16 operands only up to D = 64), the 16-row tiles beyond
+    plan = ops.planned_kernels(qq, kk, vv, p, mask, grad_o=go.cuda())
+    wide_fwd = D <= 128 and (D <= 64 or dt == torch.bfloat16)
+    assert plan["fwd_kernel"] == ("FWD_QUAD32" if wide_fwd else "FWD_QUAD_MFMA")
+    assert plan["bwd_kernel"] == ("BWD_QUAD32" if D <= 128 else "BWD_QUAD_MFMA" if dt == torch.bfloat16 else "BWD_QUADRATIC")
     o = fastmax(qq, kk, vv, mask=mask, p=p)
     ro, _ = c_oracle.fwd(q.float().numpy(), k.float().numpy(), v.float().numpy(), mask=mask, p=p)
     assert rel_err(o.detach().float().cpu().numpy(), ro) < (tf if o.dtype == dt else max(tf, TOL_FWD))
