@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/fastmax_hip.h.
+"""ctypes binding of the C ABI declared in include/fastmax_hip.h and include/fastmax_hip_generate.h.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -104,6 +104,12 @@ ABI = {
     "fastmax_hip_error_string": (cs, [ci]),
 }
 SYMBOLS = list(ABI)
+# the generation-time entry points include/fastmax_hip_generate.h declares, in its order: same library, a table of their own
+# (include/fastmax_hip.h and ABI_VERSION list the training / prefill ABI only)
+GEN_ABI = {
+    "fastmax_hip_p2_decode_step_qkv_supported": (ci, [ci, ci, ci, ci, ci]),
+    "fastmax_hip_p2_decode_step_qkv": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
+}
 
 _lib = None
 
@@ -117,7 +123,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.items():
+    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

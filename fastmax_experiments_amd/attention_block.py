@@ -11,6 +11,11 @@ Reproduces the CALL CONTRACT of the reference's ``CausalSelfAttention.forward`` 
 It is deliberately NOT a port of lit-gpt's GPT: no config registry, KV cache, MLP or norms -- only the
 attention sub-layer that hands tensors to the operator.  Everything outside the two LoRA linears and the
 attention operator is stock tensor plumbing.
+
+Generation: ``forward(x, cos, sin, input_pos, state=FastmaxDecodeState(p=2, ...))`` runs the ``fastmax`` block on the
+second-order decode state cache (decode.py) in place of the reference's zero-padded KV cache (model.py:427-430): masked p=2
+fastmax over everything the state has seen plus the T new tokens, at a fixed cost per token.  ``linearmax`` blocks cannot:
+their prologue normalises q and k over the whole sequence, which no carried state can follow.
 """
 import torch
 import torch.nn as nn
@@ -63,8 +68,15 @@ class CausalSelfAttention(nn.Module):
         self.proj.quantize_base(double_quant)
         return self
 
-    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, input_pos=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, input_pos=None, state=None) -> torch.Tensor:
+        """``state`` (a ``FastmaxDecodeState(B, n_head, head_size, p=2, n_query_groups=...)``): generate on the decode state
+        cache.  x holds the T new tokens, cos / sin the rope rows of their positions (``index_select(0, input_pos)`` of the
+        cache, as the reference's GPT.forward passes them); ``input_pos`` itself is never read, so nothing syncs with the host.
+        Without ``state`` every path is what it was."""
         B, T, C = x.size()
+        if state is not None:
+            y = self.attend_cached(x, cos, sin, state)
+            return self.proj(y.reshape(B, T, self.head_size * self.n_head))      # model.py:453-455 (no transpose: quirk Q3)
         q_per_kv = self.n_head // self.n_query_groups
         total_qkv = q_per_kv + 2
         if self._one_kernel_qkv(x, input_pos, B, T, q_per_kv):
@@ -109,6 +121,24 @@ class CausalSelfAttention(nn.Module):
 
 
 # (methods of CausalSelfAttention, kept below forward for readability)
+def attend_cached(self, x, cos, sin, state):
+    """the attention of ``forward(..., state=...)`` before the head-mixing reshape: x (B,T,C) -> (B, n_head, T, head_size) =
+    masked p=2 fastmax at the T new positions over the state's tokens and the new ones; the state advances by T.  One token
+    onto a non-empty state is a single step straight from the QKV projection's output, anything else an ``extend`` (a
+    prefill on an empty state)."""
+    if self.attn_alg == "linearmax":
+        raise NotImplementedError("generation on the decode state cache needs the fastmax (p=2) block: linearmax normalises "
+                                  "q and k over the whole sequence, which a carried state cannot follow")
+    B, T, _ = x.size()
+    if cos.shape[0] != T or sin.shape[0] != T:
+        raise ValueError(f"cos / sin should hold the rope rows of the {T} new positions, got {tuple(cos.shape)}, {tuple(sin.shape)}")
+    q_per_kv = self.n_head // self.n_query_groups
+    qkv = self.attn(x).view(B, T, self.n_query_groups, q_per_kv + 2, self.head_size)
+    if T == 1 and state.count > 0:
+        return state.step_qkv(qkv, cos, sin, self.rope_n_elem)
+    return state.extend_qkv(qkv, cos, sin, self.rope_n_elem)
+
+
 def _one_kernel_qkv(self, x, input_pos, B, T, q_per_kv) -> bool:
     """can the qkv projection, the de-interleave and RoPE run as ONE kernel (nf4_gemm.hip's tile epilogue)?  Training-size bf16
     input on the hand-written GEMM route, whole heads per 256-column tile, and a K / V layout that needs no per-head copies
@@ -143,6 +173,7 @@ def _forward_one_kernel_qkv(self, x, cos, sin, B, T, q_per_kv):
     return self.proj(y.reshape(B, T, self.head_size * self.n_head))
 
 
+CausalSelfAttention.attend_cached = attend_cached
 CausalSelfAttention._one_kernel_qkv = _one_kernel_qkv
 CausalSelfAttention._forward_one_kernel_qkv = _forward_one_kernel_qkv
 CausalSelfAttention.gemm_rope = True

@@ -27,6 +27,15 @@ template <> __device__ __forceinline__ float from_float<float>(float f) { return
 template <> __device__ __forceinline__ bf16_t from_float<bf16_t>(float f) { return bf16_t{f32_to_bf16_bits(f)}; }
 template <> __device__ __forceinline__ f16_t from_float<f16_t>(float f) { return f16_t{(_Float16)f}; }
 
+// x c + y s with three float32 roundings: two products and a sum, no fused multiply-add (hipcc contracts by default).
+// The RoPE passes use it so that their results are bit-identical to the reference's tensor ops (model.py:708).
+__device__ __forceinline__ float mul_add_unfused(float x, float c, float y, float s) {
+#pragma clang fp contract(off)
+    const float p0 = x * c;
+    const float p1 = y * s;
+    return p0 + p1;
+}
+
 // ---- strided (B,H,N,D) view ------------------------------------------------------
 struct View {
     const void* ptr;

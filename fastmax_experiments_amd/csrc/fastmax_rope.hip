@@ -35,14 +35,6 @@ template <typename T, int E> __device__ __forceinline__ void st_piece(T* p, cons
     *reinterpret_cast<ru32x4*>(p) = raw;
 }
 
-// x cos + y sin with the reference's three float32 roundings (no fused multiply-add; hipcc contracts by default)
-__device__ __forceinline__ float mul_add_unfused(float x, float c, float y, float s) {
-#pragma clang fp contract(off)
-    const float p0 = x * c;
-    const float p1 = y * s;
-    return p0 + p1;
-}
-
 // One wave = one token (b, t): its G * (qpk + 2) head rows x UPR units per row (a unit = a rotated piece pair or one tail
 // piece) are walked 64 units at a time.  When UPR divides 64 a lane keeps the same unit for every row, so the four table
 // pieces it needs (cos, sin at d and d + half: 4 x 16-byte-count floats) are loaded ONCE per token and lane -- fetched per row they

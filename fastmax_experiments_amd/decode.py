@@ -18,6 +18,10 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
        chunk's own masked part comes from the p=2 tile kernels, and the state is then advanced by the T tokens: about
        three passes over the state instead of the 2 T of T single steps.  `prefill(..., chunk=C)` feeds a prompt as
        `extend` calls of C tokens: masked p=2 attention in time linear in N (forward only).
+       `step_qkv` / `extend_qkv` take the attention block's QKV projection output (B,T,G,q_per_kv+2,hs) and the rope rows
+       of the new positions instead of split, rotated q, k, v: what `CausalSelfAttention.forward(..., state=...)` calls.
+       For one token the step kernel can de-interleave and rotate while it loads (csrc/fastmax_decode_qkv.hip): bit-identical
+       to the split + RoPE pass followed by `step`, one launch less (`fused_step`, off by default: FUSED_STEP_DEFAULT).
 """
 import ctypes
 import math
@@ -26,6 +30,12 @@ import torch
 
 from . import _lib, ops
 from .attention_mechanisms.fastmax import fastmax
+
+
+# FastmaxDecodeState.step_qkv: which of the two bit-identical routes a new state takes.  The fused step has not yet been timed
+# against split + step on an MI355X (profiles/r07_block_decode.md), so the route made only of previously measured kernels
+# stays the default; set `state.fused_step = True` for the single-launch step.
+FUSED_STEP_DEFAULT = False
 
 
 class FastmaxDecodeState:
@@ -48,6 +58,15 @@ class FastmaxDecodeState:
         if nbytes == 0:
             raise NotImplementedError(f"head size {D} not supported")
         self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+        self.count = 0
+        self.prefill_chunk = None   # extend_qkv on an empty state: prefill(..., chunk=prefill_chunk)
+        # step_qkv: True = the step kernel rotates q, k while it loads them; False = split + RoPE pass, then step (two
+        # launches).  Bit-identical.  See FUSED_STEP_DEFAULT for the measurement behind the default.
+        self.fused_step = FUSED_STEP_DEFAULT
+
+    def reset(self):
+        """Empty sequence again; the allocation is kept (a generation loop resets between prompts)."""
+        self.state.zero_()
         self.count = 0
 
     def prefill(self, q, k, v, chunk=None):
@@ -104,6 +123,69 @@ class FastmaxDecodeState:
                   ws=_lib.lib().fastmax_hip_p2_extend_workspace(B, H, Hkv, T, D))
         self.count += T
         return o
+
+    def _check_qkv(self, qkv, cos, sin, rope_n_elem, what):
+        if self.p != 2:
+            raise NotImplementedError(f"{what} needs the second-order state cache (p=2): linearmax normalises q and k over "
+                                      "the whole sequence, which a carried first-order state cannot follow")
+        B, H, G, D = self.B, self.H, self.Hkv, self.D
+        if qkv.dim() != 5 or tuple(qkv.shape[:1] + qkv.shape[2:]) != (B, G, H // G + 2, D) or qkv.shape[1] < 1:
+            raise ValueError(f"expected qkv (B,T,G,q_per_kv+2,hs) = {(B, 'T', G, H // G + 2, D)}, got {tuple(qkv.shape)}")
+        T = qkv.shape[1]
+        n = int(rope_n_elem)
+        for t in (cos, sin):
+            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < n:
+                raise ValueError(f"expected the rope rows of the {T} new positions, (T, >= {n}), got {tuple(t.shape)}")
+        return T, n
+
+    def _split_qkv(self, qkv, cos, sin, n):
+        """qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): K and V stay at their G heads.
+        One HIP pass where the split kernel takes the shape, else tensor slicing + apply_rope (model.py:397-425)."""
+        B, T, G, total, hs = qkv.shape
+        qpk = total - 2
+        if qkv.is_cuda and ops.rope_qkv_supported(qkv.dtype, hs, n):
+            return ops.RopeQKVSplit.apply(qkv, cos, sin, n, 0)
+        from .attention_block import apply_rope
+        q = qkv[:, :, :, :qpk].permute(0, 2, 3, 1, 4).reshape(B, G * qpk, T, hs)
+        k, v = (qkv[:, :, :, qpk + i].permute(0, 2, 1, 3) for i in (0, 1))
+        cos, sin = cos[:, :n], sin[:, :n]
+        q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
+        k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
+        return q, k, v
+
+    def step_qkv(self, qkv, cos, sin, rope_n_elem):
+        """p=2: ONE new token from the QKV projection's output.  qkv (B,1,G,q_per_kv+2,hs) (slots 0..q_per_kv-1 of a group are
+        its query heads, then its key head, then its value head); cos, sin: the rope row of the new position, (1, >= rope_n_elem)
+        -> o (B,H,1,hs) in qkv's dtype.  `fused_step`: de-interleave + RoPE happen inside the step kernel's loader when
+        fastmax_hip_p2_decode_step_qkv_supported says so; else (and with fused_step off) split + RoPE, then `step`."""
+        T, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "step_qkv")
+        if T != 1:
+            raise ValueError(f"step_qkv takes one token, got T={T}; use extend_qkv")
+        B, H, G, D = self.B, self.H, self.Hkv, self.D
+        dt = ops._DT.get(qkv.dtype)
+        L = _lib.lib()
+        if (self.fused_step and qkv.is_cuda and dt is not None and
+                L.fastmax_hip_p2_decode_step_qkv_supported(G, H // G, D, n, dt)):
+            qkv = qkv.contiguous()
+            tables16 = int(cos.dtype == qkv.dtype and qkv.dtype in (torch.bfloat16, torch.float16))
+            cos32, sin32 = (t[:, :n].float().contiguous() for t in (cos, sin))
+            o = torch.empty((B, H, 1, D), dtype=qkv.dtype, device=qkv.device)
+            ops._call("fastmax_hip_p2_decode_step_qkv", qkv.device,
+                      (qkv.data_ptr(), cos32.data_ptr(), sin32.data_ptr(), self.state.data_ptr(), o.data_ptr(), B, G, H // G, D, n,
+                       tables16, dt, dt, 1.0 / self.nt))
+            self.count += 1
+            return o
+        return self.step(*self._split_qkv(qkv, cos, sin, n))
+
+    def extend_qkv(self, qkv, cos, sin, rope_n_elem):
+        """p=2: T >= 1 new tokens from the QKV projection's output, qkv (B,T,G,q_per_kv+2,hs); cos, sin: the rope rows of the T
+        new positions -> o (B,H,T,hs).  Split + RoPE with K and V at their G heads, then `extend`; on an empty state
+        `prefill(..., chunk=self.prefill_chunk)` (None: the one-shot masked forward + state capture)."""
+        _, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "extend_qkv")
+        q, k, v = self._split_qkv(qkv, cos, sin, n)
+        if self.count == 0:
+            return self.prefill(q, k, v, chunk=self.prefill_chunk)
+        return self.extend(q, k, v)
 
     def _check_p2_shapes(self, q, k, n):
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D

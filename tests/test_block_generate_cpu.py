@@ -1,0 +1,136 @@
+"""CPU-side checks of generation through the attention block (include/fastmax_hip_generate.h, csrc/fastmax_decode_qkv.hip,
+decode.py step_qkv / extend_qkv, attention_block.py forward(..., state=...)): the new entry points are declared, bound and
+exported without touching the pinned ABI of include/fastmax_hip.h, `_supported` follows the documented conditions, every
+rejected argument comes back as its error code before anything is launched (host pointers stand in for device buffers: a
+rejected call never touches them), and the block's host-side contract."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_BAD_SHAPE, E_BAD_DTYPE, E_NULL = -2, -3, -6
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from fastmax_experiments_amd import _lib, build
+    build.build()
+    return _lib.lib()
+
+
+def _declared(header):
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return re.findall(r"\b(fastmax_hip_[a-z0-9_]+)\s*\(", text)
+
+
+def test_generate_header_is_bound_exported_and_apart_from_the_pinned_abi(lib):
+    from fastmax_experiments_amd import _lib
+    gen = _declared("fastmax_hip_generate.h")
+    assert gen == ["fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"]
+    assert gen == list(_lib.GEN_ABI)
+    base = set(_declared("fastmax_hip.h"))
+    for name in gen:
+        assert hasattr(lib, name), name
+        assert name not in base and name not in _lib.SYMBOLS and name not in _lib.ABI, name
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == (_lib.GEN_ABI[name][0], _lib.GEN_ABI[name][1]), name
+    assert '#include "fastmax_hip.h"' in open(os.path.join(ROOT, "include", "fastmax_hip_generate.h")).read()
+    assert lib.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
+
+
+def test_binding_rows_match_the_prototypes():
+    """parameter count and kind of each GEN_ABI row against the header's text (a wrong row hands a kernel garbage silently)"""
+    from fastmax_experiments_amd import _lib
+    text = open(os.path.join(ROOT, "include", "fastmax_hip_generate.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    protos = re.findall(r"\bint\s+(fastmax_hip_\w+)\s*\(([^)]*)\)\s*;", text)
+    assert [n for n, _ in protos] == list(_lib.GEN_ABI)
+    for name, params in protos:
+        kinds = ["pointer" if "*" in p else p.split()[-2] for p in params.split(",")]
+        restype, argtypes = _lib.GEN_ABI[name]
+        assert restype is ctypes.c_int
+        got = ["pointer" if t is ctypes.c_void_p else {ctypes.c_int: "int", ctypes.c_float: "float"}[t] for t in argtypes]
+        assert got == kinds, name
+
+
+@pytest.mark.parametrize("dt", [0, 1, 2])
+@pytest.mark.parametrize("G,qpk,D,rope", [(4, 8, 64, 64), (32, 1, 128, 128), (1, 8, 128, 128), (4, 1, 32, 8)])
+def test_supported_shapes(lib, G, qpk, D, rope, dt):
+    assert lib.fastmax_hip_p2_decode_step_qkv_supported(G, qpk, D, rope, dt) == 1
+
+
+def test_unsupported_shapes(lib):
+    f = lib.fastmax_hip_p2_decode_step_qkv_supported
+    assert f(4, 8, 64, 64, 1) == 1
+    for G, qpk, D, rope, dt in ((4, 8, 136, 64, 1), (4, 8, 64, 63, 1), (4, 8, 64, 7, 0), (4, 8, 64, 66, 1), (4, 257, 64, 64, 1),
+                                (4, 8, 64, 64, 3), (4, 8, 64, 64, -1), (0, 8, 64, 64, 1), (4, 0, 64, 64, 1), (4, 8, 0, 0, 1),
+                                (4, 8, 64, -2, 1)):
+        assert f(G, qpk, D, rope, dt) == 0, (G, qpk, D, rope, dt)
+    assert f(4, 256, 64, 64, 1) == 1 and f(4, 8, 128, 0, 2) == 1
+
+
+def test_step_qkv_rejects_bad_arguments_before_any_launch(lib):
+    keep = [ctypes.create_string_buffer(4096) for _ in range(5)]
+    qkv, cos, sin, state, o = (ctypes.cast(b, ctypes.c_void_p) for b in keep)
+    step = lib.fastmax_hip_p2_decode_step_qkv
+
+    def call(qkv=qkv, cos=cos, sin=sin, state=state, o=o, B=1, G=2, qpk=2, D=64, rope=64, t16=0, dt=1, odt=1):
+        return step(qkv, cos, sin, state, o, B, G, qpk, D, rope, t16, dt, odt, 0.125, None)
+
+    for kw in (dict(qkv=None), dict(cos=None), dict(sin=None), dict(state=None), dict(o=None)):
+        assert call(**kw) == E_NULL, kw
+    for kw in (dict(dt=3), dict(dt=-1), dict(odt=7), dict(odt=-1)):
+        assert call(**kw) == E_BAD_DTYPE, kw
+    for kw in (dict(D=136), dict(D=129), dict(D=0), dict(rope=63), dict(rope=66), dict(rope=-2), dict(qpk=257), dict(qpk=0),
+               dict(G=0), dict(B=0), dict(B=-1), dict(B=65536, G=1), dict(B=256, G=256)):
+        assert call(**kw) == E_BAD_SHAPE, kw
+
+
+def test_forward_takes_a_state_and_linearmax_refuses_it():
+    from fastmax_experiments_amd.attention_block import CausalSelfAttention, build_rope_cache
+    from fastmax_experiments_amd.decode import FastmaxDecodeState
+    sig = inspect.signature(CausalSelfAttention.forward)
+    assert list(sig.parameters) == ["self", "x", "cos", "sin", "input_pos", "state"]
+    assert sig.parameters["state"].default is None and sig.parameters["input_pos"].default is None
+    assert callable(getattr(CausalSelfAttention, "attend_cached"))
+    blk = CausalSelfAttention(n_embd=64, n_head=4, n_query_groups=2, head_size=16, attn_alg="linearmax")
+    st = FastmaxDecodeState(1, 4, 16, "cpu", p=2, n_query_groups=2)
+    cos, sin = build_rope_cache(4, 16)
+    with pytest.raises(NotImplementedError, match="whole sequence"):
+        blk(torch.zeros(1, 1, 64), cos[:1], sin[:1], torch.tensor([0]), st)
+    with pytest.raises(NotImplementedError, match="whole sequence"):
+        blk.attend_cached(torch.zeros(1, 3, 64), cos[:3], sin[:3], st)
+
+
+def test_state_host_side_contract():
+    """reset keeps the allocation; the qkv entry points refuse a first-order state and malformed operands on the host"""
+    from fastmax_experiments_amd.decode import FastmaxDecodeState
+    st = FastmaxDecodeState(1, 4, 16, "cpu", p=2, n_query_groups=2)
+    assert st.prefill_chunk is None and isinstance(st.fused_step, bool)
+    ptr = st.state.data_ptr()
+    st.state.fill_(1.0)
+    st.count = 7
+    st.reset()
+    assert st.count == 0 and st.state.data_ptr() == ptr and not st.state.any()
+    qkv = torch.zeros(1, 1, 2, 4, 16)
+    row = torch.zeros(1, 16)
+    for bad in (torch.zeros(1, 1, 2, 3, 16), torch.zeros(1, 1, 4, 4, 16), torch.zeros(1, 1, 2, 4, 8), torch.zeros(1, 2, 4, 16)):
+        with pytest.raises(ValueError):
+            st.step_qkv(bad, row, row, 16)
+        with pytest.raises(ValueError):
+            st.extend_qkv(bad, row, row, 16)
+    with pytest.raises(ValueError):
+        st.step_qkv(torch.zeros(1, 2, 2, 4, 16), torch.zeros(2, 16), torch.zeros(2, 16), 16)      # two tokens
+    with pytest.raises(ValueError):
+        st.step_qkv(qkv, torch.zeros(2, 16), row, 16)                                             # rows of two positions
+    with pytest.raises(ValueError):
+        st.extend_qkv(qkv, torch.zeros(1, 8), torch.zeros(1, 8), 16)                              # rows shorter than rope_n_elem
+    p1 = FastmaxDecodeState(1, 4, 16, "cpu", p=1)
+    for f in (p1.step_qkv, p1.extend_qkv):
+        with pytest.raises(NotImplementedError):
+            f(torch.zeros(1, 1, 4, 3, 16), row, row, 16)

@@ -3,7 +3,10 @@
 decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-order rows only.
 `--extend`: multi-token continuation of the second-order cache (`extend`, `prefill(chunk=C)`), all rows, event times.
 `--extend-case B,H,Hkv,D,T` and `--prefill-case B,H,N,D,C` (C = 0: the one-shot prefill) run ONE row, for a
-`rocprofv3 --kernel-trace --stats` run whose per-kernel totals then belong to that row alone."""
+`rocprofv3 --kernel-trace --stats` run whose per-kernel totals then belong to that row alone.
+`--block`: per-token time of the attention block generating on the second-order cache (`forward(..., state=...)`), the fused
+step beside the two-launch route (split + step), eager and as a HIP graph replay (`--no-graph`: eager only).
+`--block-case NAME,B,FUSED` runs ONE arm eagerly for a kernel trace (NAME: a key of attention_block.CONFIG_SHAPES)."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -155,10 +158,113 @@ def bench_extend():
         print(f"| one-shot vs chunked | ({B},{H},{N},{D}) | " + " | ".join(f"{x:.3f}" for x in ms) + " |", flush=True)
 
 
+BLOCK_CASES = (("tiny-llama-1.1b", 22), ("Llama-2-7b-hf", 32))          # (attention_block.CONFIG_SHAPES key, layers of the model)
+
+
+def _block_setup(name, n_layer, B, prompt=512):
+    """the sub-layer with merged weights (no LoRA branch) on a 4-bit base, bf16 activations: one block, and one state per layer
+    of the model, each holding the same `prompt` tokens -- the per-token working set of a real generation loop (the weights
+    of ONE layer, though: the projections read theirs from cache more often than a full model's would, in both columns alike)."""
+    from fastmax_experiments_amd.attention_block import CONFIG_SHAPES, CausalSelfAttention, build_rope_cache
+    cfg = CONFIG_SHAPES[name]
+    torch.manual_seed(0)
+    blk = CausalSelfAttention(r=0, **cfg).to("cuda", torch.bfloat16).eval().quantize_base()
+    H, G, hs = cfg["n_head"], cfg["n_query_groups"], cfg["head_size"]
+    cos, sin = build_rope_cache(prompt + 1, blk.rope_n_elem, device="cuda")
+    first = FastmaxDecodeState(B, H, hs, device="cuda", p=2, n_query_groups=G)
+    xp = torch.randn(B, prompt, cfg["n_embd"], device="cuda").to(torch.bfloat16)
+    blk(xp, cos[:prompt], sin[:prompt], None, first)
+    states = [first]
+    for _ in range(n_layer - 1):
+        st = FastmaxDecodeState(B, H, hs, device="cuda", p=2, n_query_groups=G)
+        st.state.copy_(first.state)
+        st.count = first.count
+        states.append(st)
+    x1 = torch.randn(B, 1, cfg["n_embd"], device="cuda").to(torch.bfloat16)
+    return blk, states, x1, cos[prompt:prompt + 1].contiguous(), sin[prompt:prompt + 1].contiguous()
+
+
+def _block_arms(blk, states, x1, c, s):
+    """-> {arm: function that runs one token through the block once per state}"""
+    def tokens(fused):
+        def run():
+            for st in states:
+                st.fused_step = fused
+                blk(x1, c, s, None, st)
+        return run
+    return {"fused": tokens(True), "split+step": tokens(False)}
+
+
+def _alternate(arms, rounds, iters):
+    """`rounds` timed windows per arm, the arms alternating inside one process -> {arm: [ms per call of the arm's function]}"""
+    ts = {a: [] for a in arms}
+    for f in arms.values():
+        f(); f()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for a, f in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ts[a].append(e0.elapsed_time(e1) / iters)
+    return ts
+
+
+def bench_block(graph=True, rounds=9):
+    """Per token and layer, microseconds: median, min and spread ((max - min) / median) over `rounds` windows per arm, the two
+    arms alternating.  Eager times include the host side of each call (Python, ctypes, allocator) and are bounded by it at
+    these sizes; the graph rows replay the same launches without the host: they are the device-side figure."""
+    print("| block decode | mode | B | layers | fused us | min | spread | split+step us | min | spread | split+step / fused |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    for name, n_layer in BLOCK_CASES:
+        for B in (1, 8):
+            blk, states, x1, c, s = _block_setup(name, n_layer, B)
+            arms = _block_arms(blk, states, x1, c, s)
+            modes = []
+            with torch.no_grad():
+                modes.append(("eager", _alternate(arms, rounds, iters=5)))
+                if graph:
+                    side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        for f in arms.values():
+                            f()
+                    torch.cuda.current_stream().wait_stream(side)
+                    replays = {}
+                    for a, f in arms.items():
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g):
+                            f()
+                        replays[a] = g.replay
+                    modes.append(("graph replay", _alternate(replays, rounds, iters=20)))
+            for mode, ts in modes:
+                cells = []
+                for a in ("fused", "split+step"):
+                    us = [t * 1e3 / n_layer for t in ts[a]]
+                    med = statistics.median(us)
+                    cells += [f"{med:.2f}", f"{min(us):.2f}", f"{(max(us) - min(us)) / med * 100:.1f}%"]
+                ratio = statistics.median(ts["split+step"]) / statistics.median(ts["fused"])
+                print(f"| {name} | {mode} | {B} | {n_layer} | " + " | ".join(cells) + f" | {ratio:.3f} |", flush=True)
+            del blk, states, arms
+
+
 def _case_arg(flag):
     return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
 
 
+if "--block-case" in sys.argv:
+    name, B, fused = sys.argv[sys.argv.index("--block-case") + 1].split(",")
+    blk, states, x1, c, s = _block_setup(name, dict(BLOCK_CASES)[name], int(B))
+    arm = _block_arms(blk, states, x1, c, s)["fused" if int(fused) else "split+step"]
+    with torch.no_grad():
+        ms = timeit(arm, iters=5, rounds=3)
+    print(f"block-case {name} B={B} fused={fused}: tokens through the block = {len(states) * 16}, event ms per token and layer "
+          f"{ms / len(states):.4f}")
+    sys.exit(0)
+if "--block" in sys.argv:
+    bench_block(graph="--no-graph" not in sys.argv)
+    sys.exit(0)
 if "--extend-case" in sys.argv:
     B, H, Hkv, D, T = _case_arg("--extend-case")
     ms_e, ms_s, n, ne, ns = extend_case(B, H, Hkv, D, T)
