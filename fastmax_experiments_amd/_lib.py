@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/fastmax_hip.h and include/fastmax_hip_generate.h.
+"""ctypes binding of the C ABI declared in include/fastmax_hip.h, include/fastmax_hip_generate.h and
+include/fastmax_hip_linearmax_decode.h.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -110,6 +111,11 @@ GEN_ABI = {
     "fastmax_hip_p2_decode_step_qkv_supported": (ci, [ci, ci, ci, ci, ci]),
     "fastmax_hip_p2_decode_step_qkv": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
 }
+# the first-order linearmax decode state cache include/fastmax_hip_linearmax_decode.h declares, in its order: a table of its own
+LINEARMAX_DECODE_ABI = {
+    "fastmax_hip_linearmax_decode_state_bytes": (sz, [ci, ci, ci, ci]),
+    "fastmax_hip_linearmax_decode_advance": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -123,7 +129,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items()):
+    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items(), *LINEARMAX_DECODE_ABI.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

@@ -14,8 +14,12 @@ attention operator is stock tensor plumbing.
 
 Generation: ``forward(x, cos, sin, input_pos, state=FastmaxDecodeState(p=2, ...))`` runs the ``fastmax`` block on the
 second-order decode state cache (decode.py) in place of the reference's zero-padded KV cache (model.py:427-430): masked p=2
-fastmax over everything the state has seen plus the T new tokens, at a fixed cost per token.  ``linearmax`` blocks cannot:
-their prologue normalises q and k over the whole sequence, which no carried state can follow.
+fastmax over everything the state has seen plus the T new tokens, at a fixed cost per token.  ``linearmax`` blocks generate
+on a ``LinearmaxDecodeState(B, n_head, head_size, device, n_query_groups=...)``: their prologue's two statistics (the largest
+centred-row norms Mq, Mk over the whole sequence) leave the bilinear sums as the one scalar a = 1 / (Mq Mk),
+o_i = (S1 + a qc_i^T S2) / (count + a qc_i . ksum) over sums of the centred, UNSCALED rows, so the carried state never needs
+rescaling and only two running maxima move (decode.py).  Each of the T rows sees the statistics of everything up to the last
+new token, as the masked forward over that sequence would compute them.
 """
 import torch
 import torch.nn as nn
@@ -69,8 +73,8 @@ class CausalSelfAttention(nn.Module):
         return self
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, input_pos=None, state=None) -> torch.Tensor:
-        """``state`` (a ``FastmaxDecodeState(B, n_head, head_size, p=2, n_query_groups=...)``): generate on the decode state
-        cache.  x holds the T new tokens, cos / sin the rope rows of their positions (``index_select(0, input_pos)`` of the
+        """``state`` (a ``FastmaxDecodeState(B, n_head, head_size, p=2, n_query_groups=...)``; for a ``linearmax`` block a
+        ``LinearmaxDecodeState(B, n_head, head_size, device, n_query_groups=...)``): generate on the decode state cache.  x holds the T new tokens, cos / sin the rope rows of their positions (``index_select(0, input_pos)`` of the
         cache, as the reference's GPT.forward passes them); ``input_pos`` itself is never read, so nothing syncs with the host.
         Without ``state`` every path is what it was."""
         B, T, C = x.size()
@@ -123,12 +127,18 @@ class CausalSelfAttention(nn.Module):
 # (methods of CausalSelfAttention, kept below forward for readability)
 def attend_cached(self, x, cos, sin, state):
     """the attention of ``forward(..., state=...)`` before the head-mixing reshape: x (B,T,C) -> (B, n_head, T, head_size) =
-    masked p=2 fastmax at the T new positions over the state's tokens and the new ones; the state advances by T.  One token
-    onto a non-empty state is a single step straight from the QKV projection's output, anything else an ``extend`` (a
-    prefill on an empty state)."""
+    masked p=2 fastmax (``linearmax`` block: masked first-order linearmax) at the T new positions over the state's tokens and
+    the new ones; the state advances by T.  One token onto a non-empty state is a single step straight from the QKV
+    projection's output, anything else an ``extend`` (a prefill on an empty state)."""
+    from .decode import FastmaxDecodeState, LinearmaxDecodeState
     if self.attn_alg == "linearmax":
-        raise NotImplementedError("generation on the decode state cache needs the fastmax (p=2) block: linearmax normalises "
-                                  "q and k over the whole sequence, which a carried state cannot follow")
+        if isinstance(state, FastmaxDecodeState):
+            raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
+                                      "statistics run over the whole sequence, which the fastmax state caches do not carry")
+        if not isinstance(state, LinearmaxDecodeState):
+            raise TypeError(f"a linearmax block generates on a LinearmaxDecodeState, got {type(state).__name__}")
+    elif isinstance(state, LinearmaxDecodeState):
+        raise TypeError("a fastmax block generates on a FastmaxDecodeState(p=2), not on a LinearmaxDecodeState")
     B, T, _ = x.size()
     if cos.shape[0] != T or sin.shape[0] != T:
         raise ValueError(f"cos / sin should hold the rope rows of the {T} new positions, got {tuple(cos.shape)}, {tuple(sin.shape)}")

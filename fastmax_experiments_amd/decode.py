@@ -1,4 +1,5 @@
-"""Opt-in decode-time state caches for fastmax: first order (p=1) and second order (p=2).
+"""Opt-in decode-time state caches: fastmax first order (p=1) and second order (p=2), and first-order
+linearmax (`LinearmaxDecodeState`).
 
 The reference generates with a zero-padded KV cache and re-runs UNMASKED attention over the whole cache for every
 new token (lit_gpt/model.py:427-430, 464-466; generate/base.py:85-92): O(N D) per token and, by quirk Q4, not the
@@ -22,6 +23,15 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
        of the new positions instead of split, rotated q, k, v: what `CausalSelfAttention.forward(..., state=...)` calls.
        For one token the step kernel can de-interleave and rotate while it loads (csrc/fastmax_decode_qkv.hip): bit-identical
        to the split + RoPE pass followed by `step`, one launch less (`fused_step`, off by default: FUSED_STEP_DEFAULT).
+
+  linearmax  the model's `fastmax_hack(q, k, v, p=1, mask=True)`: `LinearmaxDecodeState` (csrc/linearmax_decode.hip).  The
+       prologue centres every q and k row over D and divides ALL of q by one scalar per (b, h), Mq = the largest centred-row
+       norm of q over the sequence, and all of k by Mk likewise.  With qc, kc the centred, unscaled rows
+           f(q^_i . k^_j) = 1 + (qc_i . kc_j) / (Mq Mk)
+           o_i = (S1 + a qc_i^T S2) / (count + a qc_i . ksum),   a = 1 / (Mq Mk)
+           S2 = sum_j kc_j v_j^T,  S1 = sum_j v_j,  ksum = sum_j kc_j     (sums over j <= i)
+       so the two statistics leave the bilinear sums as one scalar: a state of unscaled centred sums never needs rescaling,
+       only a moves as the two running maxima grow.  O(D^2) per token and about 70 KB per KV head at D = 128.
 """
 import ctypes
 import math
@@ -30,12 +40,41 @@ import torch
 
 from . import _lib, ops
 from .attention_mechanisms.fastmax import fastmax
+from .attention_mechanisms.fastmax_hack import fastmax_hack
 
 
 # FastmaxDecodeState.step_qkv: which of the two bit-identical routes a new state takes.  The fused step has not yet been timed
 # against split + step on an MI355X (profiles/r07_block_decode.md), so the route made only of previously measured kernels
 # stays the default; set `state.fused_step = True` for the single-launch step.
 FUSED_STEP_DEFAULT = False
+
+
+def _check_qkv(B, H, G, D, qkv, cos, sin, rope_n_elem):
+    """the QKV projection's output and the rope rows of its T positions, as step_qkv / extend_qkv take them -> (T, rope_n_elem)"""
+    if qkv.dim() != 5 or tuple(qkv.shape[:1] + qkv.shape[2:]) != (B, G, H // G + 2, D) or qkv.shape[1] < 1:
+        raise ValueError(f"expected qkv (B,T,G,q_per_kv+2,hs) = {(B, 'T', G, H // G + 2, D)}, got {tuple(qkv.shape)}")
+    T = qkv.shape[1]
+    n = int(rope_n_elem)
+    for t in (cos, sin):
+        if t.dim() != 2 or t.shape[0] != T or t.shape[1] < n:
+            raise ValueError(f"expected the rope rows of the {T} new positions, (T, >= {n}), got {tuple(t.shape)}")
+    return T, n
+
+
+def _split_qkv(qkv, cos, sin, n):
+    """qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): K and V stay at their G heads.
+    One HIP pass where the split kernel takes the shape, else tensor slicing + apply_rope (model.py:397-425)."""
+    B, T, G, total, hs = qkv.shape
+    qpk = total - 2
+    if qkv.is_cuda and ops.rope_qkv_supported(qkv.dtype, hs, n):
+        return ops.RopeQKVSplit.apply(qkv, cos, sin, n, 0)
+    from .attention_block import apply_rope
+    q = qkv[:, :, :, :qpk].permute(0, 2, 3, 1, 4).reshape(B, G * qpk, T, hs)
+    k, v = (qkv[:, :, :, qpk + i].permute(0, 2, 1, 3) for i in (0, 1))
+    cos, sin = cos[:, :n], sin[:, :n]
+    q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
+    k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
+    return q, k, v
 
 
 class FastmaxDecodeState:
@@ -109,8 +148,8 @@ class FastmaxDecodeState:
         (B,n_query_groups,T,D) -> o (B,H,T,D) in q's dtype = masked p=2 fastmax at the T new positions over the cached and
         the new tokens; the state advances by T tokens."""
         if self.p != 2:
-            raise NotImplementedError("extend needs the second-order state cache (p=2): linearmax normalises q and k over the "
-                                      "whole sequence, which a carried first-order state cannot follow")
+            raise NotImplementedError("extend needs the second-order state cache (p=2); for linearmax blocks, whose statistics "
+                                      "run over the whole sequence, use LinearmaxDecodeState")
         T = q.shape[2] if q.dim() == 4 else 0
         if T < 1:
             raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
@@ -126,32 +165,12 @@ class FastmaxDecodeState:
 
     def _check_qkv(self, qkv, cos, sin, rope_n_elem, what):
         if self.p != 2:
-            raise NotImplementedError(f"{what} needs the second-order state cache (p=2): linearmax normalises q and k over "
-                                      "the whole sequence, which a carried first-order state cannot follow")
-        B, H, G, D = self.B, self.H, self.Hkv, self.D
-        if qkv.dim() != 5 or tuple(qkv.shape[:1] + qkv.shape[2:]) != (B, G, H // G + 2, D) or qkv.shape[1] < 1:
-            raise ValueError(f"expected qkv (B,T,G,q_per_kv+2,hs) = {(B, 'T', G, H // G + 2, D)}, got {tuple(qkv.shape)}")
-        T = qkv.shape[1]
-        n = int(rope_n_elem)
-        for t in (cos, sin):
-            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < n:
-                raise ValueError(f"expected the rope rows of the {T} new positions, (T, >= {n}), got {tuple(t.shape)}")
-        return T, n
+            raise NotImplementedError(f"{what} needs the second-order state cache (p=2); for linearmax blocks, whose statistics "
+                                      "run over the whole sequence, use LinearmaxDecodeState")
+        return _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
 
     def _split_qkv(self, qkv, cos, sin, n):
-        """qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): K and V stay at their G heads.
-        One HIP pass where the split kernel takes the shape, else tensor slicing + apply_rope (model.py:397-425)."""
-        B, T, G, total, hs = qkv.shape
-        qpk = total - 2
-        if qkv.is_cuda and ops.rope_qkv_supported(qkv.dtype, hs, n):
-            return ops.RopeQKVSplit.apply(qkv, cos, sin, n, 0)
-        from .attention_block import apply_rope
-        q = qkv[:, :, :, :qpk].permute(0, 2, 3, 1, 4).reshape(B, G * qpk, T, hs)
-        k, v = (qkv[:, :, :, qpk + i].permute(0, 2, 1, 3) for i in (0, 1))
-        cos, sin = cos[:, :n], sin[:, :n]
-        q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
-        k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
-        return q, k, v
+        return _split_qkv(qkv, cos, sin, n)
 
     def step_qkv(self, qkv, cos, sin, rope_n_elem):
         """p=2: ONE new token from the QKV projection's output.  qkv (B,1,G,q_per_kv+2,hs) (slots 0..q_per_kv-1 of a group are
@@ -222,4 +241,104 @@ class FastmaxDecodeState:
         ops._call("fastmax_hip_p2_decode_step", q.device,
                   (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.Hkv, self.D, dt, dt, 1.0 / self.nt))
         self.count += 1
+        return o
+
+
+class LinearmaxDecodeState:
+    """Decode state cache of a linearmax block: masked first-order linearmax L(q, k, v) = fastmax_hack(q, k, v, p=1, mask=True)
+    at O(D^2) per token (the factorisation is in the module docstring).  q (B,H,T,D); k and v (B,n_query_groups,T,D) at their
+    KV heads (default: one per query head), expanded as the model expands them.
+
+    `extend(T)` is NOT T steps, unlike the p=2 cache: every row of L sees the statistics (Mq, Mk) of the whole sequence it was
+    computed over -- the reference's own training-time behaviour -- so `extend` folds both maxima over its whole chunk before
+    it reads out any row and returns rows count .. count+T-1 of L over all count+T tokens, while `step` returns the last row
+    of L over the count+1 tokens seen so far.  Rows whose centred q or k is all zero divide by zero, as in the reference.
+    The token count the kernels use lives in the state itself; `count` is the host's copy and nothing is ever read back."""
+
+    def __init__(self, B, H, D, device, n_query_groups=None):
+        Hkv = H if n_query_groups is None else n_query_groups
+        if Hkv <= 0 or H % Hkv != 0:
+            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+        self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
+        nbytes = _lib.lib().fastmax_hip_linearmax_decode_state_bytes(B, H, Hkv, D)
+        if nbytes == 0:
+            raise NotImplementedError(f"linearmax decode state: head size {D} with {H // Hkv} query heads per KV head not supported")
+        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+        self.count = 0
+
+    def reset(self):
+        """Empty sequence again; the allocation is kept."""
+        self.state.zero_()
+        self.count = 0
+
+    def prefill(self, q, k, v):
+        """L over the prompt (the matrix-core masked forward), o (B,H,N,D); the state then holds the prompt."""
+        assert self.count == 0, "prefill starts a sequence"
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        T = q.shape[2] if q.dim() == 4 else 0
+        self._check_shapes(q, k, v, T)
+        with torch.no_grad():
+            if Hkv == H:
+                o = fastmax_hack(q, k, v, p=1, mask=True)
+            else:
+                # each group's query heads as the heads of one batch entry, its K and V as stride-0 views over them
+                r = H // Hkv
+                qg = q.reshape(B * Hkv, r, T, D)
+                kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
+                o = fastmax_hack(qg, kg, vg, p=1, mask=True).reshape(B, H, T, D)
+        self._advance(q, k, v, T, readout=False)
+        return o
+
+    def step(self, q, k, v):
+        """q (B,H,1,D), k and v (B,n_query_groups,1,D) of the new token -> o (B,H,1,D) in q's dtype: the last row of L over
+        the count + 1 tokens; one launch, O(D^2) per KV head."""
+        self._check_shapes(q, k, v, 1)
+        return self._advance(q, k, v, 1)
+
+    def extend(self, q, k, v):
+        """T >= 1 new tokens after the `count` cached ones (any count, 0 included) -> o (B,H,T,D) in q's dtype = rows
+        count .. count+T-1 of L over all count + T tokens.  T = 1 is `step`, bit for bit."""
+        T = q.shape[2] if q.dim() == 4 else 0
+        if T < 1:
+            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        self._check_shapes(q, k, v, T)
+        return self._advance(q, k, v, T)
+
+    def _split_qkv(self, qkv, cos, sin, n):
+        return _split_qkv(qkv, cos, sin, n)
+
+    def step_qkv(self, qkv, cos, sin, rope_n_elem):
+        """ONE new token from the QKV projection's output, qkv (B,1,G,q_per_kv+2,hs); cos, sin: the rope row of the new
+        position -> o (B,H,1,hs).  Split + RoPE with K and V left at their G heads, then `step`."""
+        T, n = _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
+        if T != 1:
+            raise ValueError(f"step_qkv takes one token, got T={T}; use extend_qkv")
+        return self.step(*_split_qkv(qkv, cos, sin, n))
+
+    def extend_qkv(self, qkv, cos, sin, rope_n_elem):
+        """T >= 1 new tokens from the QKV projection's output -> o (B,H,T,hs): split + RoPE, then `extend`; `prefill` on an
+        empty state."""
+        _, n = _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
+        q, k, v = _split_qkv(qkv, cos, sin, n)
+        return self.prefill(q, k, v) if self.count == 0 else self.extend(q, k, v)
+
+    def _check_shapes(self, q, k, v, n):
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        if tuple(q.shape) != (B, H, n, D) or tuple(k.shape) != (B, Hkv, n, D) or tuple(v.shape) != (B, Hkv, n, D):
+            raise ValueError(f"expected q {(B, H, n, D)} and k, v {(B, Hkv, n, D)}, got {tuple(q.shape)}, {tuple(k.shape)} "
+                             f"and {tuple(v.shape)}")
+        if q.dtype not in ops._DT:
+            raise TypeError(f"linearmax decode state takes float32, bfloat16 or float16, got {q.dtype}")
+
+    def _advance(self, q, k, v, T, readout=True):
+        """the state moves on by the T tokens; with `readout` -> their rows of L"""
+        dev = self.state.device
+        if dev.type != "cuda":
+            ops._device()          # raises: there is no CPU path
+        # the kernel takes any strides with unit stride in D (views of the split's output as they are)
+        qd, kd, vd = (t if t.stride(3) == 1 else t.contiguous() for t in (x.to(device=dev, dtype=q.dtype) for x in (q, k, v)))
+        o = torch.empty((self.B, self.H, T, self.D), dtype=q.dtype, device=dev) if readout else None
+        ops._call("fastmax_hip_linearmax_decode_advance", dev,
+                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), ops._ptr(o), self.B, self.H, self.Hkv, T, self.D, ops._DT[q.dtype]))
+        self.count += T
         return o

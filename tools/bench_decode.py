@@ -6,7 +6,9 @@ decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-orde
 `rocprofv3 --kernel-trace --stats` run whose per-kernel totals then belong to that row alone.
 `--block`: per-token time of the attention block generating on the second-order cache (`forward(..., state=...)`), the fused
 step beside the two-launch route (split + step), eager and as a HIP graph replay (`--no-graph`: eager only).
-`--block-case NAME,B,FUSED` runs ONE arm eagerly for a kernel trace (NAME: a key of attention_block.CONFIG_SHAPES)."""
+`--block-case NAME,B,FUSED` runs ONE arm eagerly for a kernel trace (NAME: a key of attention_block.CONFIG_SHAPES).
+`--linearmax`: per-token time of `LinearmaxDecodeState.step` after 512- and 16384-token prompts, beside the masked linearmax
+forward over the whole prefix (the only route without the cache) and the second-order cache's step."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -249,10 +251,54 @@ def bench_block(graph=True, rounds=9):
             del blk, states, arms
 
 
+def bench_linearmax():
+    """First-order linearmax decode state cache: `step` per token and layer, one state per layer of the model visited in turn
+    (22 / 32), after prompts of 512 and 16384 tokens; beside it what one more token costs without the cache (fastmax_hack over
+    the prefix + 1 tokens, of which only the last row is wanted; K and V as the block's stride-0 group views) and the p=2
+    cache's step at the same shape (its cost does not depend on the prompt: 64-token prefill).  Event times, host side
+    included."""
+    from attention_mechanisms.fastmax_hack import fastmax_hack
+    from fastmax_experiments_amd.decode import LinearmaxDecodeState
+    print("| shape (H, G, hs) | B | prompt | state KB/layer | linearmax step us/token.layer | masked forward over the prefix us | "
+          "p=2 cache step us/token.layer |")
+    print("|---|---|---|---|---|---|---|")
+    for name, H, G, D, layers in (("TinyLlama", 32, 4, 64, 22), ("Llama-2-7B", 32, 32, 128, 32)):
+        for B in (1, 8):
+            q1 = torch.randn(B, H, 1, D, device="cuda").to(torch.bfloat16)
+            k1, v1 = (torch.randn(B, G, 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+            p2 = [FastmaxDecodeState(B, H, D, device="cuda", p=2, n_query_groups=G) for _ in range(layers)]
+            qs, ks, vs = (torch.randn(B, h, 64, D, device="cuda").to(torch.bfloat16) for h in (H, G, G))
+            with torch.no_grad():
+                for st in p2:
+                    st.prefill(qs, ks, vs)
+                us_p2 = timeit(lambda: [st.step(q1, k1, v1) for st in p2], iters=3, rounds=5) / layers * 1e3
+            del p2
+            for N in (512, 16384):
+                q = torch.randn(B, H, N + 1, D, device="cuda").to(torch.bfloat16)
+                k, v = (torch.randn(B, G, N + 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+                states = [LinearmaxDecodeState(B, H, D, "cuda", n_query_groups=G) for _ in range(layers)]
+                states[0].prefill(q[:, :, :N], k[:, :, :N], v[:, :, :N])
+                for st in states[1:]:
+                    st.state.copy_(states[0].state)
+                    st.count = N
+                r = H // G
+                qg = q.reshape(B * G, r, N + 1, D)
+                kg, vg = (t.reshape(B * G, 1, N + 1, D).expand(B * G, r, N + 1, D) for t in (k, v))
+                with torch.no_grad():
+                    us = timeit(lambda: [st.step(q1, k1, v1) for st in states], iters=3, rounds=5) / layers * 1e3
+                    us_fwd = timeit(lambda: fastmax_hack(qg, kg, vg, p=1, mask=True), iters=3, rounds=5) * 1e3
+                kb = states[0].state.numel() * 4 / 1024
+                print(f"| {name} ({H}, {G}, {D}) | {B} | {N} | {kb:.0f} | {us:.1f} | {us_fwd:.1f} | {us_p2:.1f} |", flush=True)
+                del states, q, k, v, qg, kg, vg
+
+
 def _case_arg(flag):
     return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
 
 
+if "--linearmax" in sys.argv:
+    bench_linearmax()
+    sys.exit(0)
 if "--block-case" in sys.argv:
     name, B, fused = sys.argv[sys.argv.index("--block-case") + 1].split(",")
     blk, states, x1, c, s = _block_setup(name, dict(BLOCK_CASES)[name], int(B))
