@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/fastmax_hip.h, include/fastmax_hip_generate.h and
-include/fastmax_hip_linearmax_decode.h.
+"""ctypes binding of the C ABI declared in include/fastmax_hip.h, include/fastmax_hip_generate.h,
+include/fastmax_hip_linearmax_decode.h and include/fastmax_hip_block.h.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -116,6 +116,16 @@ LINEARMAX_DECODE_ABI = {
     "fastmax_hip_linearmax_decode_state_bytes": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_linearmax_decode_advance": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, vp]),
 }
+# the decoder block's neighbours of the attention sub-layer include/fastmax_hip_block.h declares (RMSNorm with the residual add,
+# the gated activation of the MLP, and their backward passes), in its order: a table of its own
+ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act
+BLOCK_ABI = {
+    "fastmax_hip_rmsnorm_forward": (ci, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, ci, ci, cf, ci, ci, ci, vp]),
+    "fastmax_hip_rmsnorm_backward_workspace": (sz, [ci, ci, ci, ci]),
+    "fastmax_hip_rmsnorm_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_gated_act_forward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_gated_act_backward": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -129,7 +139,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items(), *LINEARMAX_DECODE_ABI.items()):
+    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items(), *LINEARMAX_DECODE_ABI.items(), *BLOCK_ABI.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

@@ -24,21 +24,32 @@ from . import dp
 
 
 class AttentionStack(nn.Module):
-    """n_layer x (x + CausalSelfAttention(x)) with QLoRA linears, then the lm-head loss of finetune/lora.py:216-219."""
+    """n_layer x (x + CausalSelfAttention(x)) with QLoRA linears, then the lm-head loss of finetune/lora.py:216-219.
+    ``block="full"``: n_layer whole decoder blocks (block.py: RMSNorm, attention, RMSNorm, gated MLP at the config's
+    intermediate_size, both residual adds) in place of the bare attention sub-layers."""
 
     def __init__(self, config: str, n_layer: int, attn_alg: str, vocab: int = 32000, r: int = 8, alpha: int = 16,
-                 lora_dropout: float = 0.05):
+                 lora_dropout: float = 0.05, block: str = "attention"):
         """r, alpha, lora_dropout: the reference's fine-tune defaults (finetune/lora.py:40-42)"""
         super().__init__()
         from .attention_block import CONFIG_SHAPES, CausalSelfAttention
+        if block not in ("attention", "full"):
+            raise ValueError(f"block should be 'attention' or 'full', got {block!r}")
         shape = CONFIG_SHAPES[config]
         self.n_embd = shape["n_embd"]
-        self.blocks = nn.ModuleList(CausalSelfAttention(attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout, **shape) for _ in range(n_layer))
+        self.block = block
+        if block == "full":
+            from .block import Block
+            self.blocks = nn.ModuleList(Block.from_config(config, attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout)
+                                        for _ in range(n_layer))
+        else:
+            self.blocks = nn.ModuleList(CausalSelfAttention(attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout, **shape) for _ in range(n_layer))
         for b in self.blocks:
-            nn.init.normal_(b.attn.lora_B, std=0.02)              # a non-zero branch, so every LoRA gradient is exercised
+            attn = b.attn if block == "full" else b
+            nn.init.normal_(attn.attn.lora_B, std=0.02)           # a non-zero branch, so every LoRA gradient is exercised
         g = torch.Generator().manual_seed(1234)
         self.lm_head = nn.Parameter(torch.randn(vocab, self.n_embd, generator=g) * 0.02, requires_grad=False)
-        self.rope_n_elem = self.blocks[0].rope_n_elem
+        self.rope_n_elem = (self.blocks[0].attn if block == "full" else self.blocks[0]).rope_n_elem
 
     def prepare(self, device, quantize: bool = True):
         if quantize:
@@ -46,9 +57,16 @@ class AttentionStack(nn.Module):
                 b.quantize_base()
         self.to(device)
         self.lm_head.data = self.lm_head.data.to(torch.bfloat16)
+        if self.block == "full":
+            for b in self.blocks:                                 # the norms run in the activations' dtype ("bf16-true")
+                b.norm_1.to(torch.bfloat16)
+                b.norm_2.to(torch.bfloat16)
         return self
 
     def forward(self, x, cos, sin):
+        if self.block == "full":
+            from .block import run_blocks
+            return run_blocks(self.blocks, x, cos, sin)
         for b in self.blocks:
             x = x + b(x, cos, sin)
         return x
@@ -76,7 +94,7 @@ class ToyLoRA(nn.Module):
 
 def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, accum: int, steps: int, warmup: int, device,
         rank: int = 0, world: int = 1, toy: bool = False, precondition_ms: float = 0.0, graph: bool = False,
-        lora_dropout: float = 0.05) -> dict:
+        lora_dropout: float = 0.05, block: str = "attention") -> dict:
     """`warmup` untimed + `steps` timed optimizer steps; -> timings (seconds / milliseconds, this rank)."""
     on_gpu = device.type == "cuda"
     multi = dist.is_available() and dist.is_initialized() and world > 1
@@ -88,7 +106,7 @@ def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, ac
         cos = sin = None
     else:
         from .attention_block import build_rope_cache
-        model = AttentionStack(config, n_layer, attn_alg, lora_dropout=lora_dropout).prepare(device)
+        model = AttentionStack(config, n_layer, attn_alg, lora_dropout=lora_dropout, block=block).prepare(device)
         model.train()
         x = torch.randn(accum, micro_batch, seq, model.n_embd, device=device, generator=gen).to(torch.bfloat16)
         tgt = torch.randint(0, model.lm_head.shape[0], (accum, micro_batch, seq), device=device, generator=gen)
