@@ -1,5 +1,4 @@
-"""ctypes binding of the C ABI declared in include/fastmax_hip.h, include/fastmax_hip_generate.h,
-include/fastmax_hip_linearmax_decode.h and include/fastmax_hip_block.h.
+"""ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -41,9 +40,13 @@ i64p, pp, planp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Problem), ctype
 QKV = [vp, i64p, vp, i64p, vp, i64p]          # q, q_strides, k, k_strides, v, v_strides
 BWD = [pp] + QKV + [vp, vp, vp, i64p]         # ..., o, g, grad_o, go_strides
 NF4 = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
-# every function include/fastmax_hip.h declares, in its order: name -> (restype, argtypes).
+ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act (include/fastmax_hip_block.h)
+# the public headers under include/: one library, one FASTMAX_ABI_VERSION
+HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
+# every function the HEADERS declare, in their order and in each header's own order: name -> (restype, argtypes).
 # tests/test_binding_cpu.py checks each row against the prototype.
 ABI = {
+    # fastmax_hip.h
     "fastmax_hip_tune": (ci, [cs, ci]),
     "fastmax_hip_tune_get": (ci, [cs]),
     "fastmax_hip_build_flags": (ci, []),
@@ -103,29 +106,21 @@ ABI = {
     "fastmax_hip_abi_version": (ci, []),
     "fastmax_hip_select_path": (ci, [pp]),
     "fastmax_hip_error_string": (cs, [ci]),
-}
-SYMBOLS = list(ABI)
-# the generation-time entry points include/fastmax_hip_generate.h declares, in its order: same library, a table of their own
-# (include/fastmax_hip.h and ABI_VERSION list the training / prefill ABI only)
-GEN_ABI = {
+    # fastmax_hip_generate.h: generation through the attention block
     "fastmax_hip_p2_decode_step_qkv_supported": (ci, [ci, ci, ci, ci, ci]),
     "fastmax_hip_p2_decode_step_qkv": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
-}
-# the first-order linearmax decode state cache include/fastmax_hip_linearmax_decode.h declares, in its order: a table of its own
-LINEARMAX_DECODE_ABI = {
+    # fastmax_hip_linearmax_decode.h: the first-order linearmax decode state cache
     "fastmax_hip_linearmax_decode_state_bytes": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_linearmax_decode_advance": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, vp]),
-}
-# the decoder block's neighbours of the attention sub-layer include/fastmax_hip_block.h declares (RMSNorm with the residual add,
-# the gated activation of the MLP, and their backward passes), in its order: a table of its own
-ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act
-BLOCK_ABI = {
+    # fastmax_hip_block.h: the decoder block's neighbours of the attention sub-layer (RMSNorm with the residual add, the gated
+    # activation of the MLP, and their backward passes)
     "fastmax_hip_rmsnorm_forward": (ci, [vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, ci, ci, cf, ci, ci, ci, vp]),
     "fastmax_hip_rmsnorm_backward_workspace": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_rmsnorm_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
     "fastmax_hip_gated_act_forward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_gated_act_backward": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
 }
+SYMBOLS = list(ABI)
 
 _lib = None
 
@@ -139,7 +134,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (*ABI.items(), *GEN_ABI.items(), *LINEARMAX_DECODE_ABI.items(), *BLOCK_ABI.items()):
+    for name, (restype, argtypes) in ABI.items():
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

@@ -24,27 +24,17 @@ new token, as the masked forward over that sequence would compute them.
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import lora, ops
 from .attention_mechanisms.fastmax import fastmax
 from .attention_mechanisms.fastmax_hack import fastmax_hack, fastmax_hack_grouped, grouped_route_supported
+from .decode import FastmaxDecodeState, LinearmaxDecodeState
 from .lora import LoRALinear, LoRAQKVLinear
-
-
-def build_rope_cache(seq_len: int, n_elem: int, device=None, base: int = 10000, condense_ratio: int = 1):
-    """cos / sin tables of lit_gpt/model.py:676-699 (public RoPE formula)."""
-    theta = 1.0 / (base ** (torch.arange(0, n_elem, 2, device=device).float() / n_elem))
-    seq_idx = torch.arange(seq_len, device=device) / condense_ratio
-    idx_theta = torch.outer(seq_idx, theta).repeat(1, 2)
-    return torch.cos(idx_theta), torch.sin(idx_theta)
-
-
-def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-    half = x.size(-1) // 2
-    rotated = torch.cat((-x[..., half:], x[..., :half]), dim=-1)
-    return ((x * cos) + (rotated * sin)).to(dtype=x.dtype)
+from .ops import apply_rope, build_rope_cache  # noqa: F401  (re-exported: the public RoPE formula lives beside its kernels)
 
 
 class CausalSelfAttention(nn.Module):
+    gemm_rope = True          # qkv projection + de-interleave + RoPE as one kernel where it applies (settable per instance: A/B)
+
     def __init__(self, n_embd: int, n_head: int, n_query_groups: int = None, head_size: int = None, bias: bool = False,
                  rotary_percentage: float = 1.0, attn_alg: str = "fastmax", r: int = 8, alpha: int = 16,
                  dropout: float = 0.0, to_query: bool = True, to_key: bool = False, to_value: bool = True,
@@ -88,9 +78,7 @@ class CausalSelfAttention(nn.Module):
         qkv = self.attn(x)
         fused = (self.fused_neighbours and x.device.type == "cuda" and input_pos is None and
                  ops.rope_qkv_supported(qkv.dtype, self.head_size, self.rope_n_elem))
-        grouped = (fused and self.attn_alg == "linearmax" and q_per_kv > 1 and torch.is_grad_enabled() and
-                   (x.requires_grad or any(p.requires_grad for p in self.attn.parameters())) and
-                   grouped_route_supported(x.device, qkv.dtype, self.head_size, B * self.n_head))
+        grouped = fused and self._grouped_training_route(x, qkv.dtype, B, q_per_kv)
         views = fused and q_per_kv > 1 and self.group_views
         if grouped:
             # training, grouped-query heads: K stays at its n_query_groups heads through RoPE and the linearmax prologue
@@ -109,12 +97,9 @@ class CausalSelfAttention(nn.Module):
             # shapes the one-pass kernel does not take (decode with input_pos, rotary widths that are not whole 16-byte
             # pieces): plain slicing of the (B, T, group, slot, hs) view -- slots 0..q_per_kv-1 are the group's query heads,
             # then its key head, then its value head (model.py:397-420) -- with K, V repeated per query head
-            qkv5 = qkv.view(B, T, self.n_query_groups, total_qkv, self.head_size)
-            q = qkv5[:, :, :, :q_per_kv].permute(0, 2, 3, 1, 4).reshape(B, self.n_head, T, self.head_size)
-            k, v = (qkv5[:, :, :, q_per_kv + i].permute(0, 2, 1, 3).repeat_interleave(q_per_kv, dim=1) for i in (0, 1))
-            n = self.rope_n_elem
-            q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
-            k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
+            q, k, v = ops.eager_rope_qkv_split(qkv.view(B, T, self.n_query_groups, total_qkv, self.head_size), cos, sin,
+                                               self.rope_n_elem)
+            k, v = (t.repeat_interleave(q_per_kv, dim=1) for t in (k, v))
         mask = input_pos is None                                   # model.py:462-466, 477-481
         if self.attn_alg == "linearmax":
             y = fastmax_hack(q, k, v, p=1, mask=mask)              # model.py:472
@@ -123,70 +108,64 @@ class CausalSelfAttention(nn.Module):
         y = y.reshape(B, T, self.head_size * self.n_head)          # model.py:453-455 (no transpose: quirk Q3)
         return self.proj(y)
 
+    def _grouped_training_route(self, x, dtype, B, q_per_kv) -> bool:
+        """training with grouped-query heads on a linearmax block: K stays at its n_query_groups heads through RoPE and the
+        prologue (fastmax_hack_grouped).  ``dtype``: the QKV projection's output dtype; on the one-kernel route, which takes
+        bf16 in and gives bf16 out, that is x's own"""
+        return (self.attn_alg == "linearmax" and q_per_kv > 1 and torch.is_grad_enabled() and
+                (x.requires_grad or any(p.requires_grad for p in self.attn.parameters())) and
+                grouped_route_supported(x.device, dtype, self.head_size, B * self.n_head))
 
-# (methods of CausalSelfAttention, kept below forward for readability)
-def attend_cached(self, x, cos, sin, state):
-    """the attention of ``forward(..., state=...)`` before the head-mixing reshape: x (B,T,C) -> (B, n_head, T, head_size) =
-    masked p=2 fastmax (``linearmax`` block: masked first-order linearmax) at the T new positions over the state's tokens and
-    the new ones; the state advances by T.  One token onto a non-empty state is a single step straight from the QKV
-    projection's output, anything else an ``extend`` (a prefill on an empty state)."""
-    from .decode import FastmaxDecodeState, LinearmaxDecodeState
-    if self.attn_alg == "linearmax":
-        if isinstance(state, FastmaxDecodeState):
-            raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
-                                      "statistics run over the whole sequence, which the fastmax state caches do not carry")
-        if not isinstance(state, LinearmaxDecodeState):
-            raise TypeError(f"a linearmax block generates on a LinearmaxDecodeState, got {type(state).__name__}")
-    elif isinstance(state, LinearmaxDecodeState):
-        raise TypeError("a fastmax block generates on a FastmaxDecodeState(p=2), not on a LinearmaxDecodeState")
-    B, T, _ = x.size()
-    if cos.shape[0] != T or sin.shape[0] != T:
-        raise ValueError(f"cos / sin should hold the rope rows of the {T} new positions, got {tuple(cos.shape)}, {tuple(sin.shape)}")
-    q_per_kv = self.n_head // self.n_query_groups
-    qkv = self.attn(x).view(B, T, self.n_query_groups, q_per_kv + 2, self.head_size)
-    if T == 1 and state.count > 0:
-        return state.step_qkv(qkv, cos, sin, self.rope_n_elem)
-    return state.extend_qkv(qkv, cos, sin, self.rope_n_elem)
+    def attend_cached(self, x, cos, sin, state):
+        """the attention of ``forward(..., state=...)`` before the head-mixing reshape: x (B,T,C) -> (B, n_head, T, head_size) =
+        masked p=2 fastmax (``linearmax`` block: masked first-order linearmax) at the T new positions over the state's tokens and
+        the new ones; the state advances by T.  One token onto a non-empty state is a single step straight from the QKV
+        projection's output, anything else an ``extend`` (a prefill on an empty state)."""
+        if self.attn_alg == "linearmax":
+            if isinstance(state, FastmaxDecodeState):
+                raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
+                                          "statistics run over the whole sequence, which the fastmax state caches do not carry")
+            if not isinstance(state, LinearmaxDecodeState):
+                raise TypeError(f"a linearmax block generates on a LinearmaxDecodeState, got {type(state).__name__}")
+        elif isinstance(state, LinearmaxDecodeState):
+            raise TypeError("a fastmax block generates on a FastmaxDecodeState(p=2), not on a LinearmaxDecodeState")
+        B, T, _ = x.size()
+        if cos.shape[0] != T or sin.shape[0] != T:
+            raise ValueError(f"cos / sin should hold the rope rows of the {T} new positions, got {tuple(cos.shape)}, {tuple(sin.shape)}")
+        q_per_kv = self.n_head // self.n_query_groups
+        qkv = self.attn(x).view(B, T, self.n_query_groups, q_per_kv + 2, self.head_size)
+        if T == 1 and state.count > 0:
+            return state.step_qkv(qkv, cos, sin, self.rope_n_elem)
+        return state.extend_qkv(qkv, cos, sin, self.rope_n_elem)
 
+    def _one_kernel_qkv(self, x, input_pos, B, T, q_per_kv) -> bool:
+        """can the qkv projection, the de-interleave and RoPE run as ONE kernel (nf4_gemm.hip's tile epilogue)?  Training-size bf16
+        input on the hand-written GEMM route, whole heads per 256-column tile, and a K / V layout that needs no per-head copies
+        (group views, or one query head per group)"""
+        attn = self.attn
+        if not (self.fused_neighbours and self.gemm_rope and x.device.type == "cuda" and input_pos is None and x.dtype == torch.bfloat16):
+            return False
+        if not (isinstance(attn, lora.LoRAQKVLinear) and attn.rope_fusable(x)):
+            return False
+        if q_per_kv > 1 and not self.group_views:
+            return False
+        N, K = attn.linear.out_features, attn.linear.in_features
+        return (ops.rope_qkv_supported(x.dtype, self.head_size, self.rope_n_elem) and
+                lora.gemm_rope_supported(N, K, B * T, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem))
 
-def _one_kernel_qkv(self, x, input_pos, B, T, q_per_kv) -> bool:
-    """can the qkv projection, the de-interleave and RoPE run as ONE kernel (nf4_gemm.hip's tile epilogue)?  Training-size bf16
-    input on the hand-written GEMM route, whole heads per 256-column tile, and a K / V layout that needs no per-head copies
-    (group views, or one query head per group)"""
-    from . import lora
-    attn = self.attn
-    if not (self.fused_neighbours and self.gemm_rope and x.device.type == "cuda" and input_pos is None and x.dtype == torch.bfloat16):
-        return False
-    if not (isinstance(attn, lora.LoRAQKVLinear) and attn.rope_fusable(x)):
-        return False
-    if q_per_kv > 1 and not self.group_views:
-        return False
-    N, K = attn.linear.out_features, attn.linear.in_features
-    return (ops.rope_qkv_supported(x.dtype, self.head_size, self.rope_n_elem) and
-            lora.gemm_rope_supported(N, K, B * T, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem))
-
-
-def _forward_one_kernel_qkv(self, x, cos, sin, B, T, q_per_kv):
-    tables16 = cos.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float16)
-    cos32, sin32 = ops._rope_tables_f32(cos, sin, T, self.rope_n_elem)
-    grouped = (self.attn_alg == "linearmax" and q_per_kv > 1 and torch.is_grad_enabled() and
-               (x.requires_grad or any(p.requires_grad for p in self.attn.parameters())) and
-               grouped_route_supported(x.device, x.dtype, self.head_size, B * self.n_head))
-    expand = (4 if grouped else 3) if q_per_kv > 1 else 0
-    q, k, v = self.attn(x, rope=(cos32, sin32, B, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem, tables16, expand))
-    if grouped:
-        y = fastmax_hack_grouped(q, k, v, q_per_kv, p=1)
-    elif self.attn_alg == "linearmax":
-        y = fastmax_hack(q, k, v, p=1, mask=True)
-    else:
-        y = fastmax(q, k, v, p=2, mask=True)
-    return self.proj(y.reshape(B, T, self.head_size * self.n_head))
-
-
-CausalSelfAttention.attend_cached = attend_cached
-CausalSelfAttention._one_kernel_qkv = _one_kernel_qkv
-CausalSelfAttention._forward_one_kernel_qkv = _forward_one_kernel_qkv
-CausalSelfAttention.gemm_rope = True
+    def _forward_one_kernel_qkv(self, x, cos, sin, B, T, q_per_kv):
+        tables16 = cos.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float16)
+        cos32, sin32 = ops._rope_tables_f32(cos, sin, T, self.rope_n_elem)
+        grouped = self._grouped_training_route(x, x.dtype, B, q_per_kv)
+        expand = (4 if grouped else 3) if q_per_kv > 1 else 0
+        q, k, v = self.attn(x, rope=(cos32, sin32, B, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem, tables16, expand))
+        if grouped:
+            y = fastmax_hack_grouped(q, k, v, q_per_kv, p=1)
+        elif self.attn_alg == "linearmax":
+            y = fastmax_hack(q, k, v, p=1, mask=True)
+        else:
+            y = fastmax(q, k, v, p=2, mask=True)
+        return self.proj(y.reshape(B, T, self.head_size * self.n_head))
 
 
 # head shapes of the BASELINE.json configs (lit_gpt/config.py:197-205, 1394-1411, 735-747) and of the reference config with the

@@ -5,7 +5,7 @@ The reference's ``Block.forward`` (lit_gpt/model.py:340-361), sequential-residua
     x = mlp(norm_2(x)) + x
 with ``RMSNorm`` (lit_gpt/rmsnorm.py:20-31) and ``LLaMAMLP`` / ``GemmaMLP`` (model.py:622-641, LoRA wiring lora.py:661-709).
 ``CausalSelfAttention`` is attention_block.py's; the three MLP linears are ``LoRALinear`` (NF4 base after ``quantize_base``).
-What this file adds runs in csrc/block_neighbours.hip (C ABI: include/fastmax_hip_block.h, ``_lib.BLOCK_ABI``):
+What this file adds runs in csrc/block_neighbours.hip (C ABI: include/fastmax_hip_block.h, bound by ``_lib.ABI``):
     rms_norm / rms_norm_add    the norm, optionally with the residual add in front of it as ONE pass that also writes the sum
     gated_act                  act(fc_1(x)) * fc_2(x), forward and a one-pass backward that recomputes act
 Rounding points are the reference's: the add and the normalised row are rounded to the activation dtype, statistics are

@@ -34,7 +34,6 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
        only a moves as the two running maxima grow.  O(D^2) per token and about 70 KB per KV head at D = 128.
 """
 import ctypes
-import math
 
 import torch
 
@@ -49,35 +48,80 @@ from .attention_mechanisms.fastmax_hack import fastmax_hack
 FUSED_STEP_DEFAULT = False
 
 
-def _check_qkv(B, H, G, D, qkv, cos, sin, rope_n_elem):
-    """the QKV projection's output and the rope rows of its T positions, as step_qkv / extend_qkv take them -> (T, rope_n_elem)"""
-    if qkv.dim() != 5 or tuple(qkv.shape[:1] + qkv.shape[2:]) != (B, G, H // G + 2, D) or qkv.shape[1] < 1:
-        raise ValueError(f"expected qkv (B,T,G,q_per_kv+2,hs) = {(B, 'T', G, H // G + 2, D)}, got {tuple(qkv.shape)}")
-    T = qkv.shape[1]
-    n = int(rope_n_elem)
-    for t in (cos, sin):
-        if t.dim() != 2 or t.shape[0] != T or t.shape[1] < n:
-            raise ValueError(f"expected the rope rows of the {T} new positions, (T, >= {n}), got {tuple(t.shape)}")
-    return T, n
+class _DecodeState:
+    """What the state caches share: the record `state` (float32, zeroed) of `count` tokens for B sequences of H query heads on
+    Hkv KV heads of size D, and the entry points that take the attention block's QKV projection output.  A subclass gives
+    `prefill`, `step` and `extend` on split, rotated q (B,H,T,D) and k, v (B,Hkv,T,D)."""
+
+    def __init__(self, B, H, Hkv, D, nbytes, device, unsupported):
+        if nbytes == 0:
+            raise NotImplementedError(unsupported)
+        self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
+        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+        self.count = 0
+
+    def reset(self):
+        """Empty sequence again; the allocation is kept (a generation loop resets between prompts)."""
+        self.state.zero_()
+        self.count = 0
+
+    # qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): one HIP pass where the split kernel takes
+    # the shape, else tensor slicing + apply_rope (model.py:397-425)
+    _split_qkv = staticmethod(ops.rope_qkv_split)
+
+    def _check_shapes(self, q, k, v, n):
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        if tuple(q.shape) != (B, H, n, D) or tuple(k.shape) != (B, Hkv, n, D) or tuple(v.shape) != (B, Hkv, n, D):
+            raise ValueError(f"expected q {(B, H, n, D)} and k, v {(B, Hkv, n, D)}, got {tuple(q.shape)}, {tuple(k.shape)} "
+                             f"and {tuple(v.shape)}")
+
+    def _masked_forward(self, attend, q, k, v):
+        """attend(q, k, v) over a whole prompt whose K and V sit at their Hkv heads -> o (B,H,T,D)"""
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        if Hkv == H:
+            return attend(q, k, v)
+        # each group's query heads as the heads of one batch entry, its K and V as stride-0 views over them
+        r, T = H // Hkv, q.shape[2]
+        qg = q.reshape(B * Hkv, r, T, D)
+        kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
+        return attend(qg, kg, vg).reshape(B, H, T, D)
+
+    def _check_qkv(self, qkv, cos, sin, rope_n_elem, what):
+        """the QKV projection's output and the rope rows of its T positions, as step_qkv / extend_qkv take them -> (T, rope_n_elem)"""
+        B, H, G, D = self.B, self.H, self.Hkv, self.D
+        if qkv.dim() != 5 or tuple(qkv.shape[:1] + qkv.shape[2:]) != (B, G, H // G + 2, D) or qkv.shape[1] < 1:
+            raise ValueError(f"expected qkv (B,T,G,q_per_kv+2,hs) = {(B, 'T', G, H // G + 2, D)}, got {tuple(qkv.shape)}")
+        T = qkv.shape[1]
+        n = int(rope_n_elem)
+        for t in (cos, sin):
+            if t.dim() != 2 or t.shape[0] != T or t.shape[1] < n:
+                raise ValueError(f"expected the rope rows of the {T} new positions, (T, >= {n}), got {tuple(t.shape)}")
+        return T, n
+
+    def step_qkv(self, qkv, cos, sin, rope_n_elem):
+        """ONE new token from the QKV projection's output, qkv (B,1,G,q_per_kv+2,hs) (slots 0..q_per_kv-1 of a group are its
+        query heads, then its key head, then its value head); cos, sin: the rope row of the new position, (1, >= rope_n_elem)
+        -> o (B,H,1,hs) in qkv's dtype.  Split + RoPE with K and V left at their G heads, then `step`."""
+        T, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "step_qkv")
+        if T != 1:
+            raise ValueError(f"step_qkv takes one token, got T={T}; use extend_qkv")
+        return self._step_qkv(qkv, cos, sin, n)
+
+    def _step_qkv(self, qkv, cos, sin, n):
+        return self.step(*self._split_qkv(qkv, cos, sin, n))
+
+    def extend_qkv(self, qkv, cos, sin, rope_n_elem):
+        """T >= 1 new tokens from the QKV projection's output, qkv (B,T,G,q_per_kv+2,hs); cos, sin: the rope rows of the T new
+        positions -> o (B,H,T,hs).  Split + RoPE with K and V at their G heads, then `extend`; `prefill` on an empty state."""
+        _, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "extend_qkv")
+        q, k, v = self._split_qkv(qkv, cos, sin, n)
+        return self._prefill_qkv(q, k, v) if self.count == 0 else self.extend(q, k, v)
+
+    def _prefill_qkv(self, q, k, v):
+        return self.prefill(q, k, v)
 
 
-def _split_qkv(qkv, cos, sin, n):
-    """qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): K and V stay at their G heads.
-    One HIP pass where the split kernel takes the shape, else tensor slicing + apply_rope (model.py:397-425)."""
-    B, T, G, total, hs = qkv.shape
-    qpk = total - 2
-    if qkv.is_cuda and ops.rope_qkv_supported(qkv.dtype, hs, n):
-        return ops.RopeQKVSplit.apply(qkv, cos, sin, n, 0)
-    from .attention_block import apply_rope
-    q = qkv[:, :, :, :qpk].permute(0, 2, 3, 1, 4).reshape(B, G * qpk, T, hs)
-    k, v = (qkv[:, :, :, qpk + i].permute(0, 2, 1, 3) for i in (0, 1))
-    cos, sin = cos[:, :n], sin[:, :n]
-    q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
-    k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
-    return q, k, v
-
-
-class FastmaxDecodeState:
+class FastmaxDecodeState(_DecodeState):
     def __init__(self, B, H, D, device, normalize_term=8, tensors_normalized=False, p=1, n_query_groups=None):
         if p not in (1, 2):
             raise ValueError(f"p should be 1 or 2, got p={p}")
@@ -87,26 +131,16 @@ class FastmaxDecodeState:
         if p == 2 and (Hkv <= 0 or H % Hkv != 0):
             raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
         self.p = p
-        self.B, self.H, self.D = B, H, D
-        if p == 2:
-            self.Hkv = Hkv          # the second-order state is kept per KV head
         self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
         self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
         L = _lib.lib()
+        # the second-order state is kept per KV head
         nbytes = L.fastmax_hip_decode_state_bytes(B, H, D) if p == 1 else L.fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
-        if nbytes == 0:
-            raise NotImplementedError(f"head size {D} not supported")
-        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-        self.count = 0
+        super().__init__(B, H, Hkv, D, nbytes, device, f"head size {D} not supported")
         self.prefill_chunk = None   # extend_qkv on an empty state: prefill(..., chunk=prefill_chunk)
         # step_qkv: True = the step kernel rotates q, k while it loads them; False = split + RoPE pass, then step (two
         # launches).  Bit-identical.  See FUSED_STEP_DEFAULT for the measurement behind the default.
         self.fused_step = FUSED_STEP_DEFAULT
-
-    def reset(self):
-        """Empty sequence again; the allocation is kept (a generation loop resets between prompts)."""
-        self.state.zero_()
-        self.count = 0
 
     def prefill(self, q, k, v, chunk=None):
         """Masked forward over the prompt; also captures the end-of-prompt state.  Returns o (B,H,N,D).
@@ -117,30 +151,37 @@ class FastmaxDecodeState:
                 raise ValueError(f"chunk should be a positive number of tokens, got chunk={chunk}")
             if self.p != 2:
                 raise NotImplementedError("chunked prefill needs the second-order state cache (p=2)")
-            assert self.count == 0, "prefill starts a sequence"
-            self._check_p2_shapes(q, k, q.shape[2])
+        assert self.count == 0, "prefill starts a sequence"
+        self._check_shapes(q, k, v, q.shape[2])
+        if chunk is not None:
             o = torch.empty((self.B, self.H, q.shape[2], self.D), dtype=q.dtype, device=q.device)
             for s in range(0, q.shape[2], chunk):
                 o[:, :, s:s + chunk] = self.extend(q[:, :, s:s + chunk], k[:, :, s:s + chunk], v[:, :, s:s + chunk])
             return o
-        if self.p == 2:
-            return self._prefill_p2(q, k, v)
-        assert self.count == 0, "prefill starts a sequence"
-        o = fastmax(q, k, v, mask=True, p=1, **self._kw)
-        self._prefill_state(ops._prep(k, k.device), ops._prep(v, v.device))
+        o = self._masked_forward(lambda *qkv: fastmax(*qkv, mask=True, p=self.p, **self._kw), q, k, v)
+        # the state of the whole prompt from its prepared k, v
+        kd, vd = ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device)
+        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, self.p, True, self.nt, 0.0)
+        ops._call(f"fastmax_hip_p{self.p}_prefill_state", kd.device, (ctypes.byref(prob), *ops._qkv(kd, vd), self.state.data_ptr()))
+        self.count = kd.shape[2]
         return o
 
     def step(self, q, k, v):
         """q,k,v: (B,H,1,D) of the new token -> o (B,H,1,D); O(D^2) per head.
         p=2: k and v are (B,n_query_groups,1,D); O(D^3) per KV head."""
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         if self.p == 2:
-            return self._step_p2(q, k, v)
-        qd, kd, vd = (ops._prep(t, t.device) for t in (q, k, v))
-        self.count += 1
-        o = torch.empty((self.B, self.H, 1, self.D), dtype=q.dtype, device=q.device)
+            self._check_shapes(q, k, v, 1)
+            k, v = k.to(q.dtype), v.to(q.dtype)
+        qd, kd, vd = (ops._prep(t, q.device) for t in (q, k, v))
+        o = torch.empty((B, H, 1, D), dtype=q.dtype, device=q.device)
         dt = ops._DT[q.dtype]
-        ops._call("fastmax_hip_p1_decode_step", q.device,
-                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.D, dt, dt, 1.0 / self.nt, self.count))
+        args = (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr())
+        if self.p == 2:
+            ops._call("fastmax_hip_p2_decode_step", q.device, args + (B, H, Hkv, D, dt, dt, 1.0 / self.nt))
+        else:
+            ops._call("fastmax_hip_p1_decode_step", q.device, args + (B, H, D, dt, dt, 1.0 / self.nt, self.count + 1))
+        self.count += 1
         return o
 
     def extend(self, q, k, v):
@@ -153,7 +194,7 @@ class FastmaxDecodeState:
         T = q.shape[2] if q.dim() == 4 else 0
         if T < 1:
             raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
-        self._check_p2_shapes(q, k, T)
+        self._check_shapes(q, k, v, T)
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
         o = torch.empty((B, H, T, D), dtype=q.dtype, device=q.device)
@@ -167,84 +208,32 @@ class FastmaxDecodeState:
         if self.p != 2:
             raise NotImplementedError(f"{what} needs the second-order state cache (p=2); for linearmax blocks, whose statistics "
                                       "run over the whole sequence, use LinearmaxDecodeState")
-        return _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
+        return super()._check_qkv(qkv, cos, sin, rope_n_elem, what)
 
-    def _split_qkv(self, qkv, cos, sin, n):
-        return _split_qkv(qkv, cos, sin, n)
-
-    def step_qkv(self, qkv, cos, sin, rope_n_elem):
-        """p=2: ONE new token from the QKV projection's output.  qkv (B,1,G,q_per_kv+2,hs) (slots 0..q_per_kv-1 of a group are
-        its query heads, then its key head, then its value head); cos, sin: the rope row of the new position, (1, >= rope_n_elem)
-        -> o (B,H,1,hs) in qkv's dtype.  `fused_step`: de-interleave + RoPE happen inside the step kernel's loader when
+    def _step_qkv(self, qkv, cos, sin, n):
+        """`fused_step`: de-interleave + RoPE happen inside the step kernel's loader when
         fastmax_hip_p2_decode_step_qkv_supported says so; else (and with fused_step off) split + RoPE, then `step`."""
-        T, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "step_qkv")
-        if T != 1:
-            raise ValueError(f"step_qkv takes one token, got T={T}; use extend_qkv")
         B, H, G, D = self.B, self.H, self.Hkv, self.D
         dt = ops._DT.get(qkv.dtype)
         L = _lib.lib()
-        if (self.fused_step and qkv.is_cuda and dt is not None and
+        if not (self.fused_step and qkv.is_cuda and dt is not None and
                 L.fastmax_hip_p2_decode_step_qkv_supported(G, H // G, D, n, dt)):
-            qkv = qkv.contiguous()
-            tables16 = int(cos.dtype == qkv.dtype and qkv.dtype in (torch.bfloat16, torch.float16))
-            cos32, sin32 = (t[:, :n].float().contiguous() for t in (cos, sin))
-            o = torch.empty((B, H, 1, D), dtype=qkv.dtype, device=qkv.device)
-            ops._call("fastmax_hip_p2_decode_step_qkv", qkv.device,
-                      (qkv.data_ptr(), cos32.data_ptr(), sin32.data_ptr(), self.state.data_ptr(), o.data_ptr(), B, G, H // G, D, n,
-                       tables16, dt, dt, 1.0 / self.nt))
-            self.count += 1
-            return o
-        return self.step(*self._split_qkv(qkv, cos, sin, n))
-
-    def extend_qkv(self, qkv, cos, sin, rope_n_elem):
-        """p=2: T >= 1 new tokens from the QKV projection's output, qkv (B,T,G,q_per_kv+2,hs); cos, sin: the rope rows of the T
-        new positions -> o (B,H,T,hs).  Split + RoPE with K and V at their G heads, then `extend`; on an empty state
-        `prefill(..., chunk=self.prefill_chunk)` (None: the one-shot masked forward + state capture)."""
-        _, n = self._check_qkv(qkv, cos, sin, rope_n_elem, "extend_qkv")
-        q, k, v = self._split_qkv(qkv, cos, sin, n)
-        if self.count == 0:
-            return self.prefill(q, k, v, chunk=self.prefill_chunk)
-        return self.extend(q, k, v)
-
-    def _check_p2_shapes(self, q, k, n):
-        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
-        if tuple(q.shape) != (B, H, n, D) or tuple(k.shape) != (B, Hkv, n, D):
-            raise ValueError(f"expected q {(B, H, n, D)} and k, v {(B, Hkv, n, D)}, got {tuple(q.shape)} and {tuple(k.shape)}")
-
-    def _prefill_p2(self, q, k, v):
-        assert self.count == 0, "prefill starts a sequence"
-        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
-        T = q.shape[2]
-        self._check_p2_shapes(q, k, T)
-        if Hkv == H:
-            o = fastmax(q, k, v, mask=True, p=2, **self._kw)
-        else:
-            # each group's query heads as the heads of one batch entry, its K and V as stride-0 views over them
-            r = H // Hkv
-            qg = q.reshape(B * Hkv, r, T, D)
-            kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
-            o = fastmax(qg, kg, vg, mask=True, p=2, **self._kw).reshape(B, H, T, D)
-        self._prefill_state(ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device))
-        return o
-
-    def _prefill_state(self, kd, vd):
-        """the state of the whole prompt from its prepared k, v"""
-        prob = ops._problem(kd, kd, kd.dtype, kd.dtype, self.p, True, self.nt, 0.0)
-        ops._call(f"fastmax_hip_p{self.p}_prefill_state", kd.device, (ctypes.byref(prob), *ops._qkv(kd, vd), self.state.data_ptr()))
-        self.count = kd.shape[2]
-
-    def _step_p2(self, q, k, v):
-        self._check_p2_shapes(q, k, 1)
-        qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
-        o = torch.empty((self.B, self.H, 1, self.D), dtype=q.dtype, device=q.device)
-        dt = ops._DT[q.dtype]
-        ops._call("fastmax_hip_p2_decode_step", q.device,
-                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), self.B, self.H, self.Hkv, self.D, dt, dt, 1.0 / self.nt))
+            return super()._step_qkv(qkv, cos, sin, n)
+        qkv = qkv.contiguous()
+        tables16 = int(cos.dtype == qkv.dtype and qkv.dtype in (torch.bfloat16, torch.float16))
+        cos32, sin32 = (t[:, :n].float().contiguous() for t in (cos, sin))
+        o = torch.empty((B, H, 1, D), dtype=qkv.dtype, device=qkv.device)
+        ops._call("fastmax_hip_p2_decode_step_qkv", qkv.device,
+                  (qkv.data_ptr(), cos32.data_ptr(), sin32.data_ptr(), self.state.data_ptr(), o.data_ptr(), B, G, H // G, D, n,
+                   tables16, dt, dt, 1.0 / self.nt))
         self.count += 1
         return o
 
+    def _prefill_qkv(self, q, k, v):
+        return self.prefill(q, k, v, chunk=self.prefill_chunk)     # None: the one-shot masked forward + state capture
 
-class LinearmaxDecodeState:
+
+class LinearmaxDecodeState(_DecodeState):
     """Decode state cache of a linearmax block: masked first-order linearmax L(q, k, v) = fastmax_hack(q, k, v, p=1, mask=True)
     at O(D^2) per token (the factorisation is in the module docstring).  q (B,H,T,D); k and v (B,n_query_groups,T,D) at their
     KV heads (default: one per query head), expanded as the model expands them.
@@ -259,33 +248,17 @@ class LinearmaxDecodeState:
         Hkv = H if n_query_groups is None else n_query_groups
         if Hkv <= 0 or H % Hkv != 0:
             raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
-        self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
         nbytes = _lib.lib().fastmax_hip_linearmax_decode_state_bytes(B, H, Hkv, D)
-        if nbytes == 0:
-            raise NotImplementedError(f"linearmax decode state: head size {D} with {H // Hkv} query heads per KV head not supported")
-        self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-        self.count = 0
-
-    def reset(self):
-        """Empty sequence again; the allocation is kept."""
-        self.state.zero_()
-        self.count = 0
+        super().__init__(B, H, Hkv, D, nbytes, device,
+                         f"linearmax decode state: head size {D} with {H // Hkv} query heads per KV head not supported")
 
     def prefill(self, q, k, v):
         """L over the prompt (the matrix-core masked forward), o (B,H,N,D); the state then holds the prompt."""
         assert self.count == 0, "prefill starts a sequence"
-        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         T = q.shape[2] if q.dim() == 4 else 0
         self._check_shapes(q, k, v, T)
         with torch.no_grad():
-            if Hkv == H:
-                o = fastmax_hack(q, k, v, p=1, mask=True)
-            else:
-                # each group's query heads as the heads of one batch entry, its K and V as stride-0 views over them
-                r = H // Hkv
-                qg = q.reshape(B * Hkv, r, T, D)
-                kg, vg = (t.reshape(B * Hkv, 1, T, D).expand(B * Hkv, r, T, D) for t in (k, v))
-                o = fastmax_hack(qg, kg, vg, p=1, mask=True).reshape(B, H, T, D)
+            o = self._masked_forward(lambda *qkv: fastmax_hack(*qkv, p=1, mask=True), q, k, v)
         self._advance(q, k, v, T, readout=False)
         return o
 
@@ -304,29 +277,8 @@ class LinearmaxDecodeState:
         self._check_shapes(q, k, v, T)
         return self._advance(q, k, v, T)
 
-    def _split_qkv(self, qkv, cos, sin, n):
-        return _split_qkv(qkv, cos, sin, n)
-
-    def step_qkv(self, qkv, cos, sin, rope_n_elem):
-        """ONE new token from the QKV projection's output, qkv (B,1,G,q_per_kv+2,hs); cos, sin: the rope row of the new
-        position -> o (B,H,1,hs).  Split + RoPE with K and V left at their G heads, then `step`."""
-        T, n = _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
-        if T != 1:
-            raise ValueError(f"step_qkv takes one token, got T={T}; use extend_qkv")
-        return self.step(*_split_qkv(qkv, cos, sin, n))
-
-    def extend_qkv(self, qkv, cos, sin, rope_n_elem):
-        """T >= 1 new tokens from the QKV projection's output -> o (B,H,T,hs): split + RoPE, then `extend`; `prefill` on an
-        empty state."""
-        _, n = _check_qkv(self.B, self.H, self.Hkv, self.D, qkv, cos, sin, rope_n_elem)
-        q, k, v = _split_qkv(qkv, cos, sin, n)
-        return self.prefill(q, k, v) if self.count == 0 else self.extend(q, k, v)
-
     def _check_shapes(self, q, k, v, n):
-        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
-        if tuple(q.shape) != (B, H, n, D) or tuple(k.shape) != (B, Hkv, n, D) or tuple(v.shape) != (B, Hkv, n, D):
-            raise ValueError(f"expected q {(B, H, n, D)} and k, v {(B, Hkv, n, D)}, got {tuple(q.shape)}, {tuple(k.shape)} "
-                             f"and {tuple(v.shape)}")
+        super()._check_shapes(q, k, v, n)
         if q.dtype not in ops._DT:
             raise TypeError(f"linearmax decode state takes float32, bfloat16 or float16, got {q.dtype}")
 

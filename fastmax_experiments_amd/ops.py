@@ -292,6 +292,42 @@ def rope_qkv_supported(dtype, head_size, rope_n_elem):
     return dtype in _DT and rope_n_elem % 2 == 0 and (rope_n_elem // 2) % e == 0 and (head_size - rope_n_elem) % e == 0
 
 
+def build_rope_cache(seq_len: int, n_elem: int, device=None, base: int = 10000, condense_ratio: int = 1):
+    """cos / sin tables of lit_gpt/model.py:676-699 (public RoPE formula)."""
+    theta = 1.0 / (base ** (torch.arange(0, n_elem, 2, device=device).float() / n_elem))
+    seq_idx = torch.arange(seq_len, device=device) / condense_ratio
+    idx_theta = torch.outer(seq_idx, theta).repeat(1, 2)
+    return torch.cos(idx_theta), torch.sin(idx_theta)
+
+
+def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
+    half = x.size(-1) // 2
+    rotated = torch.cat((-x[..., half:], x[..., :half]), dim=-1)
+    return ((x * cos) + (rotated * sin)).to(dtype=x.dtype)
+
+
+def eager_rope_qkv_split(qkv, cos, sin, n):
+    """tensor slicing + apply_rope (model.py:397-425, without the GQA expand): qkv (B,T,G,q_per_kv+2,hs) -- slots
+    0..q_per_kv-1 of a group are its query heads, then its key head, then its value head -> q (B,H,T,hs) and k rotated on
+    their first n dims, k and v (B,G,T,hs) at their G heads"""
+    B, T, G, total, hs = qkv.shape
+    qpk = total - 2
+    q = qkv[:, :, :, :qpk].permute(0, 2, 3, 1, 4).reshape(B, G * qpk, T, hs)
+    k, v = (qkv[:, :, :, qpk + i].permute(0, 2, 1, 3) for i in (0, 1))
+    cos, sin = cos[:, :n], sin[:, :n]
+    q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
+    k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
+    return q, k, v
+
+
+def rope_qkv_split(qkv, cos, sin, n):
+    """qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): K and V stay at their G heads.
+    One HIP pass where the split kernel takes the shape, else `eager_rope_qkv_split`."""
+    if qkv.is_cuda and rope_qkv_supported(qkv.dtype, qkv.shape[4], n):
+        return RopeQKVSplit.apply(qkv, cos, sin, n, 0)
+    return eager_rope_qkv_split(qkv, cos, sin, n)
+
+
 _ROPE_F32 = {}
 
 

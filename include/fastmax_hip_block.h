@@ -1,7 +1,7 @@
 /* fastmax_hip_block.h -- the decoder block's neighbours of the attention sub-layer in libfastmax_hip.so (MI355X / gfx950 only;
  * csrc/block_neighbours.hip): RMSNorm with an optional residual add in front, its backward pass, and the gated activation of
  * the LLaMA / Gemma MLP with its backward pass.  The dtype and error enums are those of fastmax_hip.h; the entry points here
- * are not part of FASTMAX_ABI_VERSION's list and are bound by their own table (BLOCK_ABI in fastmax_experiments_amd/_lib.py).
+ * belong to the same library and FASTMAX_ABI_VERSION and are bound by the one table ABI in fastmax_experiments_amd/_lib.py.
  *
  * Conventions: every matrix operand is (M rows, C or I columns) with a row stride in ELEMENTS and unit stride along the row;
  * `dtype` (FASTMAX_F32 / BF16 / F16) is the activation dtype; arithmetic is float32; every kernel runs on `stream`, nothing

@@ -1,7 +1,7 @@
 /* fastmax_hip_generate.h -- generation-time entry points of libfastmax_hip.so that take the attention block's QKV
  * projection output as it is (MI355X / gfx950 only).  The conventions, the dtype and error enums and the decode state cache
- * these calls advance are those of fastmax_hip.h; the entry points here are not part of FASTMAX_ABI_VERSION's list and are
- * bound by their own table (GEN_ABI in fastmax_experiments_amd/_lib.py).
+ * these calls advance are those of fastmax_hip.h; the entry points here belong to the same library and FASTMAX_ABI_VERSION
+ * and are bound by the one table ABI in fastmax_experiments_amd/_lib.py.
  */
 #ifndef FASTMAX_HIP_GENERATE_H
 #define FASTMAX_HIP_GENERATE_H

@@ -1,7 +1,7 @@
 /* fastmax_hip_linearmax_decode.h -- decode-time state cache for masked first-order linearmax
  * (fastmax_hack(q, k, v, p=1, mask=True)) in libfastmax_hip.so (MI355X / gfx950 only; csrc/linearmax_decode.hip).
- * The conventions and the dtype and error enums are those of fastmax_hip.h; the entry points here are not part of
- * FASTMAX_ABI_VERSION's list and are bound by their own table (LINEARMAX_DECODE_ABI in fastmax_experiments_amd/_lib.py).
+ * The conventions and the dtype and error enums are those of fastmax_hip.h; the entry points here belong to the same
+ * library and FASTMAX_ABI_VERSION and are bound by the one table ABI in fastmax_experiments_amd/_lib.py.
  *
  * linearmax centres every q and k row over D and divides all of q by ONE scalar per (b, h), Mq = the largest centred-row norm
  * of q over the sequence, and all of k by Mk in the same way.  With qc, kc the centred, unscaled rows

@@ -1,17 +1,14 @@
 """CPU-side checks of generation through the attention block (include/fastmax_hip_generate.h, csrc/fastmax_decode_qkv.hip,
-decode.py step_qkv / extend_qkv, attention_block.py forward(..., state=...)): the new entry points are declared, bound and
-exported without touching the pinned ABI of include/fastmax_hip.h, `_supported` follows the documented conditions, every
+decode.py step_qkv / extend_qkv, attention_block.py forward(..., state=...)): the entry points are bound and exported (their rows
+against the header's prototypes: test_binding_cpu.py), `_supported` follows the documented conditions, every
 rejected argument comes back as its error code before anything is launched (host pointers stand in for device buffers: a
 rejected call never touches them), and the block's host-side contract."""
 import ctypes
 import inspect
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_BAD_SHAPE, E_BAD_DTYPE, E_NULL = -2, -3, -6
 
 
@@ -22,40 +19,13 @@ def lib():
     return _lib.lib()
 
 
-def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    return re.findall(r"\b(fastmax_hip_[a-z0-9_]+)\s*\(", text)
-
-
-def test_generate_header_is_bound_exported_and_apart_from_the_pinned_abi(lib):
+def test_generate_entry_points_are_bound_and_exported(lib):
     from fastmax_experiments_amd import _lib
-    gen = _declared("fastmax_hip_generate.h")
-    assert gen == ["fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"]
-    assert gen == list(_lib.GEN_ABI)
-    base = set(_declared("fastmax_hip.h"))
-    for name in gen:
+    for name in ("fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"):
         assert hasattr(lib, name), name
-        assert name not in base and name not in _lib.SYMBOLS and name not in _lib.ABI, name
         fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (_lib.GEN_ABI[name][0], _lib.GEN_ABI[name][1]), name
-    assert '#include "fastmax_hip.h"' in open(os.path.join(ROOT, "include", "fastmax_hip_generate.h")).read()
+        assert (fn.restype, list(fn.argtypes)) == (_lib.ABI[name][0], _lib.ABI[name][1]), name
     assert lib.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
-
-
-def test_binding_rows_match_the_prototypes():
-    """parameter count and kind of each GEN_ABI row against the header's text (a wrong row hands a kernel garbage silently)"""
-    from fastmax_experiments_amd import _lib
-    text = open(os.path.join(ROOT, "include", "fastmax_hip_generate.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    protos = re.findall(r"\bint\s+(fastmax_hip_\w+)\s*\(([^)]*)\)\s*;", text)
-    assert [n for n, _ in protos] == list(_lib.GEN_ABI)
-    for name, params in protos:
-        kinds = ["pointer" if "*" in p else p.split()[-2] for p in params.split(",")]
-        restype, argtypes = _lib.GEN_ABI[name]
-        assert restype is ctypes.c_int
-        got = ["pointer" if t is ctypes.c_void_p else {ctypes.c_int: "int", ctypes.c_float: "float"}[t] for t in argtypes]
-        assert got == kinds, name
 
 
 @pytest.mark.parametrize("dt", [0, 1, 2])
@@ -134,3 +104,34 @@ def test_state_host_side_contract():
     for f in (p1.step_qkv, p1.extend_qkv):
         with pytest.raises(NotImplementedError):
             f(torch.zeros(1, 1, 4, 3, 16), row, row, 16)
+
+
+@pytest.mark.parametrize("dtype,table_dtype", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
+                                               (torch.bfloat16, torch.float32)])
+@pytest.mark.parametrize("B,T,G,qpk,hs,rope_n", [(2, 5, 2, 3, 16, 16), (1, 3, 1, 4, 16, 4), (2, 1, 4, 1, 8, 8)])
+def test_shared_eager_split_is_the_forward_fallback_bit_for_bit(B, T, G, qpk, hs, rope_n, dtype, table_dtype):
+    """forward's eager fallback used to slice, repeat K and V per query head, then rotate; it now takes the eager split the
+    decode state caches use (K, V at their G heads) and repeats afterwards.  RoPE acts on each row alone: identical bits."""
+    from fastmax_experiments_amd import ops
+    from fastmax_experiments_amd.attention_block import apply_rope, build_rope_cache
+    gen = torch.Generator().manual_seed(B * 1000 + T * 100 + G * 10 + qpk)
+    qkv = torch.randn(B, T, G * (qpk + 2) * hs, generator=gen).to(dtype)
+    cos, sin = (t.to(table_dtype) for t in build_rope_cache(T, rope_n))
+    n_head, n_query_groups, q_per_kv, total_qkv, head_size = G * qpk, G, qpk, qpk + 2, hs
+
+    # the earlier inline expression of CausalSelfAttention.forward, verbatim but for `self.`
+    qkv5 = qkv.view(B, T, n_query_groups, total_qkv, head_size)
+    q = qkv5[:, :, :, :q_per_kv].permute(0, 2, 3, 1, 4).reshape(B, n_head, T, head_size)
+    k, v = (qkv5[:, :, :, q_per_kv + i].permute(0, 2, 1, 3).repeat_interleave(q_per_kv, dim=1) for i in (0, 1))
+    n = rope_n
+    q = torch.cat((apply_rope(q[..., :n], cos, sin), q[..., n:]), dim=-1)
+    k = torch.cat((apply_rope(k[..., :n], cos, sin), k[..., n:]), dim=-1)
+
+    q2, k2, v2 = ops.eager_rope_qkv_split(qkv5, cos, sin, rope_n)
+    k2, v2 = (t.repeat_interleave(qpk, dim=1) for t in (k2, v2))
+    for got, want in ((q2, q), (k2, k), (v2, v)):
+        assert got.dtype == want.dtype == dtype and got.shape == want.shape
+        assert torch.equal(got, want)
+    # on the CPU the decode state caches' split is this eager one
+    for got, want in zip(ops.rope_qkv_split(qkv5, cos, sin, rope_n), ops.eager_rope_qkv_split(qkv5, cos, sin, rope_n)):
+        assert torch.equal(got, want)

@@ -1,8 +1,8 @@
 """The decoder block's neighbours of the attention sub-layer, everything that needs no device
-(include/fastmax_hip_block.h, _lib.BLOCK_ABI, fastmax_experiments_amd/block.py, tests/golden/rmsnorm_*.npz and mlp_*.npz):
+(include/fastmax_hip_block.h, fastmax_experiments_amd/block.py, tests/golden/rmsnorm_*.npz and mlp_*.npz):
 
-1. every row of BLOCK_ABI against the prototype in the header, in the header's order; the library exports every name; the four
-   tables pinned before and ABI_VERSION are what they were;
+1. the library exports every name of the header and binds it as its row of _lib.ABI says (the rows against the prototypes, the
+   FASTMAX_ACT_* enum and the pin over the whole table: test_binding_cpu.py);
 2. the float64 restatements in block_ref.py (RMSNorm, the gated MLP) reproduce every fixture the reference's own code produced:
    fp32 fixtures to 1e-6 relative, 16-bit fixtures to one unit in the last place of their dtype.  The GPU tests lean on these
    restatements at the shapes the fixtures do not have;
@@ -10,9 +10,6 @@
    meets the "no CPU path" error;
 4. Block's state dict carries the reference's key names."""
 import ctypes
-import os
-import re
-import zlib
 
 import numpy as np
 import pytest
@@ -21,42 +18,22 @@ import torch
 import block_ref as br
 from conftest import golden_names, load_golden, rel_err
 from fastmax_experiments_amd import _lib
-from test_binding_cpu import c_kind, ctypes_kind
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def header_prototypes():
-    text = open(os.path.join(ROOT, "include", "fastmax_hip_block.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
-    protos = []
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \*]*?)\b(fastmax_hip_\w+)\s*\(([^)]*)\)\s*;", text):
-        params = params.strip()
-        protos.append((name, c_kind(ret), [] if params in ("", "void") else [c_kind(p) for p in params.split(",")]))
-    return protos
-
-
-def test_block_abi_matches_every_prototype():
-    protos = header_prototypes()
-    assert [n for n, _, _ in protos] == list(_lib.BLOCK_ABI) and len(protos) == 5
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.BLOCK_ABI[name]
-        assert ctypes_kind(restype) == ret, name
-        assert len(argtypes) == len(kinds), name
-        for i, (t, kind) in enumerate(zip(argtypes, kinds)):
-            assert ctypes_kind(t) == kind, f"{name}: parameter {i} is bound as {ctypes_kind(t)}, the header says {kind}"
-    text = open(os.path.join(ROOT, "include", "fastmax_hip_block.h")).read()
-    acts = dict(re.findall(r"FASTMAX_(ACT_[A-Z]+) = (\d+)", text))
-    assert {k: int(v) for k, v in acts.items()} == {"ACT_SILU": _lib.ACT_SILU, "ACT_GELU": _lib.ACT_GELU}
+BLOCK_ENTRY_POINTS = ["fastmax_hip_rmsnorm_forward", "fastmax_hip_rmsnorm_backward_workspace", "fastmax_hip_rmsnorm_backward",
+                      "fastmax_hip_gated_act_forward", "fastmax_hip_gated_act_backward"]
 
 
 def test_library_exports_every_name():
     L = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.BLOCK_ABI:
+    for name in BLOCK_ENTRY_POINTS:
         assert hasattr(L, name), name
-    assert _lib.lib() is not None          # binds all five tables or raises
+    bound = _lib.lib()          # binds the whole table or raises
+    for name in BLOCK_ENTRY_POINTS:
+        fn = getattr(bound, name)
+        assert (fn.restype, list(fn.argtypes)) == (_lib.ABI[name][0], _lib.ABI[name][1]), name
+    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
 
 
 def test_workspace_query_needs_no_device():
@@ -64,24 +41,6 @@ def test_workspace_query_needs_no_device():
     assert q(1000, 128, _lib.BF16, 0) == 0 and q(0, 128, _lib.F32, 1) == 0
     assert q(1000, 128, _lib.BF16, 1) == ((1000 + 15) // 16) * 128 * 4          # one float32 row of partials per 16 rows
     assert q(3, 4096, _lib.F32, 1) == 4096 * 4
-
-
-def test_pinned_tables_and_abi_version_are_unchanged():
-    """the tables the earlier headers pin: names in order and their signatures, as a checksum taken from the parent commit"""
-    def digest(table):
-        rows = [(n, ctypes_kind(r), [ctypes_kind(a) for a in args]) for n, (r, args) in table.items()]
-        return zlib.crc32(repr(rows).encode())
-    assert _lib.ABI_VERSION == 9
-    assert len(_lib.ABI) == 59 and _lib.SYMBOLS == list(_lib.ABI)
-    assert list(_lib.GEN_ABI) == ["fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"]
-    assert list(_lib.LINEARMAX_DECODE_ABI) == ["fastmax_hip_linearmax_decode_state_bytes", "fastmax_hip_linearmax_decode_advance"]
-    assert [len(a) for _, a in _lib.GEN_ABI.values()] == [5, 15]
-    assert [len(a) for _, a in _lib.LINEARMAX_DECODE_ABI.values()] == [4, 15]
-    assert digest(_lib.ABI) == PINNED_ABI_CRC
-    assert not set(_lib.BLOCK_ABI) & (set(_lib.ABI) | set(_lib.GEN_ABI) | set(_lib.LINEARMAX_DECODE_ABI))
-
-
-PINNED_ABI_CRC = 329697078          # crc32 of the (name, return kind, parameter kinds) rows of ABI at the parent commit
 
 
 # ---- 2. the restatements reproduce the fixtures ---------------------------------------------------------------------------------
