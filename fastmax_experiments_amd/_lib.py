@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI.
+"""ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
+header (OPTIM_HEADER) has the table OPTIM_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -121,6 +122,16 @@ ABI = {
     "fastmax_hip_gated_act_backward": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
 }
 SYMBOLS = list(ABI)
+# the optimizer's side header: same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
+# tests/test_flat_adamw_cpu.py checks each row against the prototype.
+OPTIM_HEADER = "fastmax_hip_optim.h"
+OPTIM_ABI = {
+    "fastmax_hip_adamw_workspace": (sz, [i64]),
+    "fastmax_hip_adamw_chunk": (ci, []),
+    "fastmax_hip_adamw_norm": (ci, [vp, ci, i64, cf, vp, sz, vp]),
+    "fastmax_hip_adamw_update": (ci, [vp, ci, i64, vp, vp, vp, i64, vp, i64, vp, i64, cf, vp, cf, cf, cf, cf, cf, cf, cf, cf,
+                                      ci, ci, ci, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -134,11 +145,12 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.items():
-        if not hasattr(L, name):
-            raise RuntimeError(f"libfastmax_hip.so does not export {name}")
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (ABI, OPTIM_ABI):
+        for name, (restype, argtypes) in table.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"libfastmax_hip.so does not export {name}")
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     if L.fastmax_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libfastmax_hip.so ABI version mismatch")
     _lib = L

@@ -4,7 +4,8 @@ One process per GPU (`torch.distributed`, backend "nccl" = RCCL over xGMI on ROC
 tests).  The attention operator itself needs no collective -- every (b,h) pair is independent -- so data
 parallelism is: shard the batch over ranks, accumulate micro-batch gradients locally, and at the
 accumulation boundary run ONE all-reduce over a single flat bucket that aliases every trainable (LoRA)
-gradient, then divide by the world size.
+gradient, then divide by the world size.  With an `optim.FlatAdamW` the division, the clip, the AdamW update and
+the zeroing of the bucket are one HIP pass over that bucket (two with the norm) instead of a chain of tensor ops.
 
 Mirrors the step structure of the reference's `finetune/lora.py:fit` (207-226):
   gradient_accumulation_iters = global_batch_size // devices // micro_batch_size   (lit_gpt/args.py:46-57)
@@ -21,6 +22,8 @@ from typing import Callable, Iterable, List, Optional
 
 import torch
 import torch.distributed as dist
+
+from .optim import FlatAdamW
 
 
 def trainable_lora_parameters(module: torch.nn.Module) -> List[torch.nn.Parameter]:
@@ -91,6 +94,13 @@ class FlatGradBucket:
             self.flat.div_(dist.get_world_size(group))
         self.scatter()
 
+    def all_reduce_sum(self, group=None):
+        """The collective alone, for an optimizer that reads the bucket itself (optim.FlatAdamW): gather, sum over ranks; the
+        division by the world size is the optimizer's `grad_scale`, and nothing is scattered back."""
+        self.gather()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
+
 
 @dataclass
 class TrainArgs:
@@ -120,7 +130,17 @@ class DataParallelStepper:
         self.scheduler, self.group = scheduler, group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.accum = train.gradient_accumulation_iters(self.world)
-        self.bucket = FlatGradBucket([p for p in model.parameters() if p.requires_grad], dtype=bucket_dtype)
+        trainable = [p for p in model.parameters() if p.requires_grad]
+        if isinstance(optimizer, FlatAdamW):
+            # the optimizer was built on a bucket: that bucket is the step's (its tables hold the bucket's offsets)
+            self.bucket = optimizer.bucket
+            if len(self.bucket.params) != len(trainable) or any(a is not b for a, b in zip(self.bucket.params, trainable)):
+                raise ValueError("the FlatAdamW's bucket should hold the model's trainable parameters, in order")
+            if bucket_dtype is not None and bucket_dtype != self.bucket.dtype:
+                raise ValueError(f"bucket_dtype {bucket_dtype} differs from the FlatAdamW's bucket ({self.bucket.dtype})")
+        else:
+            self.bucket = FlatGradBucket(trainable, dtype=bucket_dtype)
+        self._flat_route = isinstance(optimizer, FlatAdamW)
         self.iter_num = 0
         self.step_count = 0
         # time_comm: bracket the one collective of every optimizer step (device events on a HIP device, host clock else)
@@ -128,18 +148,20 @@ class DataParallelStepper:
         self.comm_ms: list = []
 
     def _timed_all_reduce(self):
+        # FlatAdamW divides by the world size and reads the bucket itself: the collective is the sum alone
+        all_reduce = self.bucket.all_reduce_sum if self._flat_route else self.bucket.all_reduce_mean
         if not self.time_comm:
-            return self.bucket.all_reduce_mean(self.group)
+            return all_reduce(self.group)
         if self.bucket.flat.device.type == "cuda":
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            self.bucket.all_reduce_mean(self.group)
+            all_reduce(self.group)
             e1.record()
             self.comm_ms.append((e0, e1))                 # resolved lazily: no host sync inside the step
         else:
             import time
             t0 = time.perf_counter()
-            self.bucket.all_reduce_mean(self.group)
+            all_reduce(self.group)
             self.comm_ms.append((time.perf_counter() - t0) * 1e3)
 
     def comm_times_ms(self):
@@ -150,8 +172,10 @@ class DataParallelStepper:
         """Record one micro-batch (forward + backward of loss / accum into the bucket) as a HIP graph; `micro_step` then
         copies its batch into the recorded input tensors and replays.  The step is ~600 kernel launches of 5-500 us each:
         replayed as one graph the GPU no longer waits for the host between them.  The collective and the optimizer stay
-        outside the graph.  Needs static shapes (every micro-batch like `sample_batch`) and a step without host
-        synchronisation -- which the HIP path is (workspaces come from the caching allocator, scalars stay on the device)."""
+        outside the graph (torch's AdamW takes lr and the step count from the host; optim.FlatAdamW keeps them on the device and
+        can be recorded on its own, see its `step(lr=tensor)`).  Needs static shapes (every micro-batch like `sample_batch`)
+        and a step without host synchronisation -- which the HIP path is (workspaces come from the caching allocator, scalars
+        stay on the device)."""
         dev = self.bucket.flat.device
         if not all(self.bucket._aliased):
             # a parameter whose dtype differs from the bucket's gets a separate .grad tensor that the recorded AccumulateGrad
@@ -191,10 +215,14 @@ class DataParallelStepper:
             (loss / self.accum).backward()
         if not is_accumulating:
             self._timed_all_reduce()
-            if self.train.max_norm is not None:
-                torch.nn.utils.clip_grad_norm_(self.bucket.params, self.train.max_norm)
-            self.optimizer.step()
-            self.bucket.zero()                    # optimizer.zero_grad(): keep the views aliased
+            if self._flat_route:
+                # one pass: / world, clip, AdamW, zero.  The .grad views stay aliased; gather() left the others at None
+                self.optimizer.step(grad_scale=1.0 / self.world, max_norm=self.train.max_norm, zero_grad=True)
+            else:
+                if self.train.max_norm is not None:
+                    torch.nn.utils.clip_grad_norm_(self.bucket.params, self.train.max_norm)
+                self.optimizer.step()
+                self.bucket.zero()                    # optimizer.zero_grad(): keep the views aliased
             if self.scheduler is not None:
                 self.scheduler.step()
             self.step_count += 1

@@ -94,8 +94,12 @@ class ToyLoRA(nn.Module):
 
 def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, accum: int, steps: int, warmup: int, device,
         rank: int = 0, world: int = 1, toy: bool = False, precondition_ms: float = 0.0, graph: bool = False,
-        lora_dropout: float = 0.05, block: str = "attention") -> dict:
-    """`warmup` untimed + `steps` timed optimizer steps; -> timings (seconds / milliseconds, this rank)."""
+        lora_dropout: float = 0.05, block: str = "attention", optimizer: str = "torch") -> dict:
+    """`warmup` untimed + `steps` timed optimizer steps; -> timings (seconds / milliseconds, this rank).
+    ``optimizer``: "torch" (torch.optim.AdamW after the bucket's all-reduce-mean) or "flat" (optim.FlatAdamW: the boundary as one
+    pass over the flat bucket)."""
+    if optimizer not in ("torch", "flat"):
+        raise ValueError(f"optimizer should be 'torch' or 'flat', got {optimizer!r}")
     on_gpu = device.type == "cuda"
     multi = dist.is_available() and dist.is_initialized() and world > 1
     gen = torch.Generator(device=device).manual_seed(100 + rank)
@@ -112,7 +116,11 @@ def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, ac
         tgt = torch.randint(0, model.lm_head.shape[0], (accum, micro_batch, seq), device=device, generator=gen)
         cos, sin = (t.to(torch.bfloat16) for t in build_rope_cache(seq, model.rope_n_elem, device=device))
     params = dp.trainable_lora_parameters(model)
-    opt = torch.optim.AdamW(params, lr=1e-4)
+    if optimizer == "flat":
+        from .optim import FlatAdamW
+        opt = FlatAdamW(dp.FlatGradBucket(params), lr=1e-4)
+    else:
+        opt = torch.optim.AdamW(params, lr=1e-4)
     train = dp.TrainArgs(global_batch_size=micro_batch * accum * world, micro_batch_size=micro_batch)
     st = dp.DataParallelStepper(model, opt, train, lambda m, b: m.loss(b[0], b[1], cos, sin), time_comm=True)
     assert st.accum == accum
