@@ -145,13 +145,10 @@ class CausalSelfAttention(nn.Module):
         attn = self.attn
         if not (self.fused_neighbours and self.gemm_rope and x.device.type == "cuda" and input_pos is None and x.dtype == torch.bfloat16):
             return False
-        if not (isinstance(attn, lora.LoRAQKVLinear) and attn.rope_fusable(x)):
+        if not isinstance(attn, lora.LoRAQKVLinear) or (q_per_kv > 1 and not self.group_views):
             return False
-        if q_per_kv > 1 and not self.group_views:
-            return False
-        N, K = attn.linear.out_features, attn.linear.in_features
         return (ops.rope_qkv_supported(x.dtype, self.head_size, self.rope_n_elem) and
-                lora.gemm_rope_supported(N, K, B * T, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem))
+                attn.plan(x, (T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem)).rope)
 
     def _forward_one_kernel_qkv(self, x, cos, sin, B, T, q_per_kv):
         tables16 = cos.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float16)

@@ -14,18 +14,17 @@ per byte with the first element in the high nibble.  Parity with bitsandbytes' o
 Fused forward (csrc/nf4_lora.hip):  y = x deq(W)^T + bias + (dropout(x) A^T) (scaling * scatter(B))^T
 """
 import ctypes
-import logging
 import os
 import weakref
 import math
-from typing import Any, Tuple, Union
+from typing import Any, NamedTuple, Tuple, Union
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _DT, _stream
+from .ops import _DT, _stream, rope_qkv_backward
 
 NF4_CODE = torch.tensor([-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
                          -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
@@ -245,8 +244,8 @@ class NF4Linear(nn.Module):
 
     # Opt-in, MI355X-specific: keep a decoded bf16 copy of the frozen weight next to the 4-bit codes.  288 GB of HBM hold
     # the bf16 copies of a 7B model (14 GB) with room to spare; the checkpoint and the optimizer state stay 4-bit / LoRA-only,
-    # but every product becomes a plain library GEMM with no decode in the loop (2-5x at <= 2048 rows, where the fused
-    # kernel's grid cannot fill 256 CUs, and no per-call decode above).  Dropped by load_dense() / merge().
+    # but every 16-bit product becomes the tile GEMM on that copy with no decode in the loop (2-5x at <= 2048 rows, where the
+    # few-rows kernel's grid cannot fill 256 CUs, and no per-call decode above).  Dropped by load_dense() / merge().
     _dense_cache = None
 
     def cache_dense(self, enable: bool = True):
@@ -273,141 +272,162 @@ class NF4Linear(nn.Module):
         self._dense_cache = None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return qlora_linear(x, self, None, None)
-
-
-_announced = set()
-
-
-def _announce_once(key: str, msg: str) -> None:
-    """a route other than the hand-written one was taken for a reason the caller did not ask for: say so, once per reason"""
-    if key not in _announced:
-        _announced.add(key)
-        logging.getLogger(__name__).warning(msg)
+        plan = qlora_plan("nf4", x.device.type, x.dtype, x.numel() // x.shape[-1], self.in_features, self.out_features,
+                          cache_dense=self._dense_cache is not None)
+        return qlora_linear(x, self, plan)
 
 
 # ---------------------------------------------------------------------------------------------
-# the fused op
+# the route plan: which kernels one call of a (Q)LoRA linear runs
 # ---------------------------------------------------------------------------------------------
-
-
-# Above this many rows of x the frozen weight is decoded ONCE into dense bf16 (HIP kernel; kept resident across passes within
-# RESIDENT_BYTES, else a per-stream scratch) and the product is the hand-written 256 x 256-tile GEMM of nf4_gemm.hip (route
-# "gemm"; "library" = hipBLASLt for A/B): the 128-tile fused kernel re-decodes each W tile in every one of the M/128 workgroup
-# rows and is vector-ALU-bound there (measured 0.54-0.72 PF/s against 1.1-1.5 PF/s dense at M = 8k..16k); below it the fused
-# kernel wins on weight bytes (0.5 B/element instead of 2).
+# From this many rows of x on, a 16-bit call decodes the frozen NF4 weight ONCE into dense bf16 (see _weight_operand) and runs the
+# hand-written 256 x 256-tile GEMM of nf4_gemm.hip: the 128-tile few-rows kernel re-decodes each W tile in every one of the
+# M/128 workgroup rows and is vector-ALU-bound there (measured 0.54-0.72 PF/s against 1.1-1.5 PF/s dense at M = 8k..16k); below
+# it the few-rows kernel wins on weight bytes (0.5 B/element instead of 2).
 DENSE_M = int(os.environ.get("FASTMAX_NF4_DENSE_M", "2048"))
-_dense_scratch = {}
+
+# How the tile GEMM reads a frozen NF4 weight that has no cache_dense() copy:
+#   "gemm"   (default) decoded once per layer (or per call, past the residency budget) by a HIP kernel; bias and the LoRA branch
+#            are the GEMM's last 16- or 32-deep step; dx through the same kernel on W^T
+#   "fused"  the NF4 codes decoded INSIDE the GEMM's loop (no dense copy for the forward product): wins only where M / 256 is
+#            small -- every 256-row block re-decodes the weight tile and the decode shares the vector ALU / LDS with the fragments
+QLORA_ROUTE = os.environ.get("FASTMAX_QLORA_ROUTE", "gemm")
+if QLORA_ROUTE not in ("gemm", "fused"):
+    raise ValueError(f"FASTMAX_QLORA_ROUTE={QLORA_ROUTE!r}: the routes are 'gemm' and 'fused'")
+# A/B switches, read once: 0 puts LoRA on a dense frozen bf16 base back on the reference's tensor-op form / runs the qkv
+# projection and the QKV split + RoPE as two kernels
+DENSE_LORA_GEMM = os.environ.get("FASTMAX_DENSE_LORA_GEMM", "1") != "0"
+GEMM_ROPE = os.environ.get("FASTMAX_GEMM_ROPE", "1") != "0"
 
 
-def _dense_weight(wq, scales, N, K):
-    """bf16 (N, K) view of a scratch buffer holding the decoded weight.  One buffer per (device, stream): valid until the next
-    QLoRA call on that stream; work on another stream gets its own buffer instead of racing on this one."""
-    key = (wq.device, torch.cuda.current_stream(wq.device).cuda_stream)
-    buf = _dense_scratch.get(key)
-    if buf is None or buf.numel() < N * K:
-        buf = torch.empty(N * K, dtype=torch.bfloat16, device=wq.device)
-        _dense_scratch[key] = buf
-    with torch.cuda.device(wq.device):
-        rc = _lib.lib().fastmax_hip_nf4_dequantize_s(wq.data_ptr(), scales.ref, buf.data_ptr(), N * K, _lib.BF16,
-                                                     _stream(wq.device))
-    _lib.check(rc, "fastmax_hip_nf4_dequantize_s")
-    return buf[: N * K].view(N, K)
-
-
-class _QLoRALinearFn(torch.autograd.Function):
-    """y = x deq(W)^T + bias + ea eb^T.  Few rows: all in one HIP kernel (dx through the same dequant GEMM).  Many rows
-    (M >= DENSE_M, bf16): HIP decode into the scratch + the tile GEMM.  d(ea), d(eb): the streaming rank-r kernels."""
-
-    @staticmethod
-    def forward(ctx, x2, ea, eb, wq, scales, bias, N, K, wdense=None, owner=None):
-        M = x2.shape[0]
-        ctx.scales = scales
-        ctx.owner = owner
-        dt = _lib.BF16 if x2.dtype == torch.bfloat16 else _lib.F32
-        ctx.dense = dt == _lib.BF16 and (M >= DENSE_M or wdense is not None)
-        ctx.wdense = wdense
-        ctx.hip_gemm = ctx.dense and QLORA_ROUTE != "library" and N % 64 == 0 and K % 64 == 0 and \
-            (ea is None or ea.shape[1] in (16, 32))
-        if ctx.hip_gemm:
-            # every product in libfastmax_hip.so: HIP decode into the scratch + the 256 x 256-tile GEMM (bias and the LoRA
-            # branch fused as its last step)
-            y = hip_gemm(x2, wdense if wdense is not None else _dense_weight(wq, scales, N, K), None, bias, ea, eb, N)
-            ctx.save_for_backward(ea, eb, wq)
-            ctx.dims = (M, N, K, dt)
-            return y
-        if ctx.dense:
-            if QLORA_ROUTE != "library":
-                _announce_once(f"dense-lib-{N % 64}-{K % 64}-{0 if ea is None else ea.shape[1]}",
-                               f"QLoRA linear ({M} x {K}) -> {N}: the tile GEMM needs N and K to be multiples of 64 and a LoRA operand of "
-                               "16 or 32 columns; this layer runs as HIP decode + library GEMM")
-            y = x2 @ (wdense if wdense is not None else _dense_weight(wq, scales, N, K)).t()
-            if ea is not None:
-                y.addmm_(ea, eb.t())
-            if bias is not None:
-                y += bias.to(y.dtype)
-            ctx.save_for_backward(ea, eb, wq)
-            ctx.dims = (M, N, K, dt)
-            return y
-        y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
-        with torch.cuda.device(x2.device):
-            rc = _lib.lib().fastmax_hip_nf4_linear_forward_s(
-                x2.data_ptr(), x2.stride(0), wq.data_ptr(), scales.ref,
-                None if bias is None else bias.data_ptr(), None if ea is None else ea.data_ptr(),
-                None if eb is None else eb.data_ptr(), y.data_ptr(), N, M, N, K, dt, _stream(x2.device))
-        _lib.check(rc, "fastmax_hip_nf4_linear_forward_s")
-        ctx.save_for_backward(ea, eb, wq)
-        ctx.dims = (M, N, K, dt)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        ea, eb, wq = ctx.saved_tensors
-        scales = ctx.scales
-        M, N, K, dt = ctx.dims
-        dy = dy.contiguous()
-        dx = d_ea = d_eb = None
-        if ctx.needs_input_grad[0] and ctx.hip_gemm:
-            wt = _resident_weight(ctx.owner, True) if M >= DENSE_M else None
-            dx = hip_gemm(dy, wt if wt is not None else _dense_weight_t(wq, scales, N, K), None, None, None, None, K)
-        elif ctx.needs_input_grad[0] and ctx.dense:
-            dx = dy @ (ctx.wdense if ctx.wdense is not None else _dense_weight(wq, scales, N, K))
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
-            with torch.cuda.device(dy.device):
-                rc = _lib.lib().fastmax_hip_nf4_linear_backward_input_s(dy.data_ptr(), N, wq.data_ptr(), scales.ref,
-                                                                        dx.data_ptr(), K, M, N, K, dt, _stream(dy.device))
-            _lib.check(rc, "fastmax_hip_nf4_linear_backward_input_s")
-        if ea is not None:
-            dyb = dy.to(torch.bfloat16)
-            RP = ea.shape[1]
-            thin = (LORA_THIN and dyb.is_cuda and RP in (16, 32) and N % 64 == 0 and ea.dtype == torch.bfloat16 and
-                    eb.dtype == torch.bfloat16 and dyb.stride(1) == 1 and (dyb.stride(0) * 2) % 16 == 0 and dyb.data_ptr() % 16 == 0)
-            if thin:
-                # the rank-r products of the backward pass as streaming HIP kernels (lora_thin.hip), one pass over dy each
-                if ctx.needs_input_grad[1]:
-                    d_ea, _ = lora_down(dyb, eb.t().contiguous(), want_t=False)          # (M, RP) = dy eb
-                if ctx.needs_input_grad[2]:
-                    MP = (M + 15) // 16 * 16
-                    eat = torch.zeros((RP, MP), dtype=torch.bfloat16, device=dyb.device)
-                    eat[:, :M] = ea.t()
-                    d_eb = lora_tn(eat, dyb, dtype=torch.bfloat16, transpose=True)       # (N, RP) = dy^T ea
-            else:
-                if ctx.needs_input_grad[1]:
-                    d_ea = dyb @ eb                   # shapes the thin kernels do not take: tensor ops
-                if ctx.needs_input_grad[2]:
-                    d_eb = dyb.t() @ ea
-        return dx, d_ea, d_eb, None, None, None, None, None, None, None
-
-
-# ---- rank-r products around the library GEMM (csrc/lora_thin.hip) ------------------------------------------------
-LORA_THIN = os.environ.get("FASTMAX_LORA_THIN", "1") != "0"
+class QLoRAPlan(NamedTuple):
+    route: str       # the frozen product: "tensor_ops" (torch, as the reference), "few_rows" (nf4_lora.hip: NF4 decoded per tile;
+    #                  libfastmax_hip.so takes its gemv at M <= 16), "gemm" (tile GEMM on the decoded / dense weight), "gemm_fused" (tile
+    #                  GEMM decoding in its loop)
+    lora: str        # the branch: "none", "in_kernel" (x A^T by lora_down, the rest inside the GEMM), "operands" (x A^T by
+    #                  F.linear, handed to the kernel as ea / eb), "tensor_ops" (around the frozen product, as the reference)
+    rank_pad: int    # columns of the branch operands the kernel sees (0: no kernel sees them)
+    dropout: str     # LoRA dropout: "none", "in_kernel" (mask regenerated from a seed by the rank-r kernels), "tensor_op" (nn.Dropout)
+    rope: bool       # may the product leave the GEMM as rotated (q, k, v)?  Needs rope_shape
 
 
 def _pad_rank(r: int) -> int:
     return 16 if r <= 16 else 32
 
 
+def _rope_shape_ok(N, K, M, T, G, qpk, hs, rope_n) -> bool:
+    """shapes the qkv projection + RoPE epilogue takes (the 256 x 256-tile kernel: more than 128 tiles, whole heads per tile)"""
+    return (N == G * (qpk + 2) * hs and 256 % hs == 0 and rope_n % 16 == 0 and K % 64 == 0 and M % T == 0
+            and ((M + 255) // 256) * ((N + 255) // 256) > 128)
+
+
+def qlora_plan(base: str, device_type: str, dtype, M: int, K: int, N: int, rank: int = 0, drop_p: float = 0.0,
+               cache_dense: bool = False, lora_enabled: bool = True, bias_trains: bool = False, rope_shape=None) -> QLoRAPlan:
+    """The one decision "which kernels run for this call", from plain data (no tensor is touched).
+    base: "nf4" (NF4Linear), "dense" (a frozen contiguous bf16 nn.Linear) or "other"; dtype, M: of x (M rows of K); rank: rows
+    of lora_A (r times the adapted parts); drop_p: the LoRA dropout probability in effect; cache_dense: the NF4 base holds its
+    decoded copy; lora_enabled: False for r = 0 or a merged layer; bias_trains: the dense base's bias takes a gradient;
+    rope_shape: (T, groups, q per kv, head size, rope_n) when the caller wants the qkv + RoPE epilogue.
+    Raises what the call would raise: an NF4 base off the GPU, or with a shape the NF4 kernels do not take."""
+    r = rank if lora_enabled else 0
+    drop = "none" if r == 0 or drop_p <= 0.0 else "tensor_op"
+    bf16 = device_type == "cuda" and dtype == torch.bfloat16
+    if base != "nf4":
+        # LoRA on an unquantised base (lit_gpt/lora.py:170-177): the tile GEMM on the weight itself at training row counts.
+        # Its autograd function treats weight AND bias as frozen data, so a trainable bias
+        # (mark_only_lora_as_trainable(bias="all"), lit_gpt/lora.py:436-461) stays on the tensor-op form
+        if (base == "dense" and 0 < r <= RANK_PAD and DENSE_LORA_GEMM and QLORA_ROUTE == "gemm" and bf16 and not bias_trains
+                and M >= DENSE_M and K % 128 == 0 and N % 64 == 0):
+            return QLoRAPlan("gemm", "in_kernel", _pad_rank(r), "in_kernel" if drop != "none" else "none",
+                             GEMM_ROPE and rope_shape is not None and _rope_shape_ok(N, K, M, *rope_shape))
+        return QLoRAPlan("tensor_ops", "tensor_ops" if r else "none", 0, drop, False)
+    if device_type != "cuda":
+        raise RuntimeError("the NF4 + LoRA linear runs on an MI355X only; there is no CPU fallback")
+    if K % 128 or N % 64:
+        raise NotImplementedError(f"fused NF4 linear needs in_features % 128 == 0 and out_features % 64 == 0, got {K}, {N}")
+    decoded = M >= DENSE_M or cache_dense                  # a dense bf16 weight is at hand, or worth making
+    if bf16 and decoded and 0 < r <= RANK_PAD:
+        in_loop = QLORA_ROUTE == "fused" and not cache_dense
+        return QLoRAPlan("gemm_fused" if in_loop else "gemm", "in_kernel", _pad_rank(r), "in_kernel" if drop != "none" else "none",
+                         QLORA_ROUTE == "gemm" and GEMM_ROPE and rope_shape is not None and _rope_shape_ok(N, K, M, *rope_shape))
+    # the kernels compute in bf16 or fp32; every other dtype (fp16) is cast to bf16 on the way in
+    route = "gemm" if decoded and dtype != torch.float32 else "few_rows"
+    if r == 0:
+        return QLoRAPlan(route, "none", 0, "none", False)
+    if r > RANK_PAD:
+        return QLoRAPlan(route, "tensor_ops", 0, drop, False)
+    # the few-rows kernel carries the branch as one 32-wide k-step, the tile GEMM as a 16- or 32-wide one
+    return QLoRAPlan(route, "operands", _pad_rank(r) if route == "gemm" else RANK_PAD, drop, False)
+
+
+# ---------------------------------------------------------------------------------------------
+# the decoded-weight source
+# ---------------------------------------------------------------------------------------------
+# Decoded copies of FROZEN weights kept across the forward and backward passes of a step (and across steps).  NF4 bases: W (N, K)
+# for the product and W^T (K, N) for dx, decoded once per layer by the HIP kernels instead of once per layer per pass (2 x ~25 us
+# per linear per step at Llama-2-7B widths), up to a global budget -- the bf16 copies of a whole 7B model are 26 GB of the
+# MI355X's 288 GB; beyond it a layer falls back to the per-call scratch decode, and FASTMAX_DENSE_RESIDENT_BYTES=0 turns
+# residency off.  Dense bases: only W^T (the weight itself serves the product), not counted against the budget.  Entries carry
+# the identity of the weight tensor (object, address, version counter, device), so quantize_base / merge / load / .to() and
+# in-place writes start over, and they live as long as the layer does.
+RESIDENT_BYTES = int(os.environ.get("FASTMAX_DENSE_RESIDENT_BYTES", str(64 << 30)))
+_resident = weakref.WeakKeyDictionary()               # frozen base layer -> {"tag": ..., "w": tensor | None, "wt": tensor | None}
+_resident_used = [0]
+_scratch = {}                                     # (device, stream, transposed) -> flat bf16 buffer
+
+
+def _decode_scratch(base: "NF4Linear", transposed: bool) -> torch.Tensor:
+    """bf16 W (N, K), or W^T (K, N), decoded into a scratch buffer.  One buffer per (device, stream, orientation): valid until the
+    next QLoRA call on that stream; work on another stream gets its own buffer instead of racing on this one."""
+    wq, scales = base.weight.data, scales_of(base)
+    N, K = base.out_features, base.in_features
+    key = (wq.device, torch.cuda.current_stream(wq.device).cuda_stream, transposed)
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < N * K:
+        buf = torch.empty(N * K, dtype=torch.bfloat16, device=wq.device)
+        _scratch[key] = buf
+    with torch.cuda.device(wq.device):
+        if transposed:
+            rc = _lib.lib().fastmax_hip_nf4_dequantize_transposed(wq.data_ptr(), scales.ref, buf.data_ptr(), N, K, _stream(wq.device))
+        else:
+            rc = _lib.lib().fastmax_hip_nf4_dequantize_s(wq.data_ptr(), scales.ref, buf.data_ptr(), N * K, _lib.BF16, _stream(wq.device))
+    _lib.check(rc, "fastmax_hip_nf4_dequantize")
+    return buf[: N * K].view((K, N) if transposed else (N, K))
+
+
+def _weight_operand(base: nn.Module, transposed: bool, allow_resident: bool = True) -> torch.Tensor:
+    """The bf16 weight operand of the tile GEMM: W (N, K) for the product, W^T (K, N) with ``transposed`` for dx.
+    NF4Linear: the cache_dense() copy (W only), else the copy kept within RESIDENT_BYTES (made here on first use, unless
+    ``allow_resident`` is False or the budget is spent), else the scratch decode.  Dense frozen base: the weight itself, or its
+    kept transpose."""
+    nf4 = isinstance(base, NF4Linear)
+    w = base.weight
+    if not transposed and (not nf4 or base._dense_cache is not None):
+        return base._dense_cache if nf4 else w.data
+    if nf4 and not (allow_resident and RESIDENT_BYTES > 0):
+        return _decode_scratch(base, transposed)
+    tag = (id(w), w.data_ptr(), w._version, w.device)
+    ent = _resident.get(base)
+    if ent is None or ent["tag"] != tag:
+        if ent is not None and nf4:
+            _resident_used[0] -= sum(t.numel() * 2 for t in (ent["w"], ent["wt"]) if t is not None)
+        ent = _resident[base] = {"tag": tag, "w": None, "wt": None}
+    key = "wt" if transposed else "w"
+    if ent[key] is None:
+        nbytes = base.out_features * base.in_features * 2
+        if not nf4:
+            ent[key] = w.detach().t().contiguous()
+        elif _resident_used[0] + nbytes > RESIDENT_BYTES:
+            return _decode_scratch(base, transposed)
+        else:
+            ent[key] = _decode_scratch(base, transposed).clone()
+            _resident_used[0] += nbytes
+    return ent[key]
+
+
+# ---------------------------------------------------------------------------------------------
+# the kernels' callers
+# ---------------------------------------------------------------------------------------------
 def lora_down(x: torch.Tensor, bt: torch.Tensor, want_t: bool = True, drop=None):
     """e (M, RP) = x (M, K) bt (RP, K)^T, and e^T (RP, roundup(M, 16)) zero padded; bf16.
     drop = (seed tensor on the device, p): x passes through the dropout mask of that seed first (scaled by 1 / (1 - p))."""
@@ -416,14 +436,11 @@ def lora_down(x: torch.Tensor, bt: torch.Tensor, want_t: bool = True, drop=None)
     e = torch.empty((M, RP), dtype=torch.bfloat16, device=x.device)
     MP = (M + 15) // 16 * 16
     et = torch.empty((RP, MP), dtype=torch.bfloat16, device=x.device) if want_t else None
+    L = _lib.lib()
+    call, extra = (L.fastmax_hip_lora_down, ()) if drop is None else (L.fastmax_hip_lora_down_dropout, (drop[0].data_ptr(), float(drop[1])))
     with torch.cuda.device(x.device):
-        if drop is None:
-            rc = _lib.lib().fastmax_hip_lora_down(x.data_ptr(), x.stride(0), bt.data_ptr(), bt.stride(0), e.data_ptr(), RP,
-                                                  None if et is None else et.data_ptr(), MP, M, K, RP, _stream(x.device))
-        else:
-            rc = _lib.lib().fastmax_hip_lora_down_dropout(x.data_ptr(), x.stride(0), bt.data_ptr(), bt.stride(0), e.data_ptr(), RP,
-                                                          None if et is None else et.data_ptr(), MP, M, K, RP, drop[0].data_ptr(),
-                                                          float(drop[1]), _stream(x.device))
+        rc = call(x.data_ptr(), x.stride(0), bt.data_ptr(), bt.stride(0), e.data_ptr(), RP,
+                  None if et is None else et.data_ptr(), MP, M, K, RP, *extra, _stream(x.device))
     _lib.check(rc, "fastmax_hip_lora_down")
     return e, et
 
@@ -462,15 +479,10 @@ def lora_tn(et: torch.Tensor, x: torch.Tensor, R: int = None, dtype=torch.float3
     kdt = torch.bfloat16 if dtype == torch.bfloat16 else torch.float32
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     out = torch.empty((ncols, R) if transpose else (R, ncols), dtype=kdt, device=x.device)
+    call, extra = (L.fastmax_hip_lora_tn, ()) if drop is None else (L.fastmax_hip_lora_tn_dropout, (drop[0].data_ptr(), float(drop[1])))
     with torch.cuda.device(x.device):
-        if drop is None:
-            rc = L.fastmax_hip_lora_tn(et.data_ptr(), et.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(),
-                                       _lib.BF16 if kdt == torch.bfloat16 else _lib.F32, int(transpose), R, ws.data_ptr(),
-                                       M, ncols, RP, _stream(x.device))
-        else:
-            rc = L.fastmax_hip_lora_tn_dropout(et.data_ptr(), et.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(),
-                                               _lib.BF16 if kdt == torch.bfloat16 else _lib.F32, int(transpose), R, ws.data_ptr(),
-                                               M, ncols, RP, drop[0].data_ptr(), float(drop[1]), _stream(x.device))
+        rc = call(et.data_ptr(), et.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(),
+                  _lib.BF16 if kdt == torch.bfloat16 else _lib.F32, int(transpose), R, ws.data_ptr(), M, ncols, RP, *extra, _stream(x.device))
     _lib.check(rc, "fastmax_hip_lora_tn")
     return out if dtype == kdt else out.to(dtype)
 
@@ -479,15 +491,11 @@ def lora_up_(y: torch.Tensor, e: torch.Tensor, bn: torch.Tensor, bias=None, tran
     """y (M, N) += e (M, R) bn^T (+ bias), in place; bn is (N, R), or (R, N) with ``transposed``; bf16, bias float32.
     drop = (seed, p): the added product passes through the dropout mask of that seed (y has the shape of the dropped-out x)."""
     M, N = y.shape
+    L = _lib.lib()
+    call, extra = (L.fastmax_hip_lora_up, ()) if drop is None else (L.fastmax_hip_lora_up_dropout, (drop[0].data_ptr(), float(drop[1])))
     with torch.cuda.device(y.device):
-        if drop is None:
-            rc = _lib.lib().fastmax_hip_lora_up(y.data_ptr(), y.stride(0), e.data_ptr(), e.stride(0), bn.data_ptr(), bn.stride(0),
-                                                int(transposed), None if bias is None else bias.data_ptr(), M, N, e.shape[1],
-                                                _stream(y.device))
-        else:
-            rc = _lib.lib().fastmax_hip_lora_up_dropout(y.data_ptr(), y.stride(0), e.data_ptr(), e.stride(0), bn.data_ptr(), bn.stride(0),
-                                                        int(transposed), None if bias is None else bias.data_ptr(), M, N, e.shape[1],
-                                                        drop[0].data_ptr(), float(drop[1]), _stream(y.device))
+        rc = call(y.data_ptr(), y.stride(0), e.data_ptr(), e.stride(0), bn.data_ptr(), bn.stride(0), int(transposed),
+                  None if bias is None else bias.data_ptr(), M, N, e.shape[1], *extra, _stream(y.device))
     _lib.check(rc, "fastmax_hip_lora_up")
     return y
 
@@ -528,16 +536,6 @@ class _ScatterRowsFn(torch.autograd.Function):
         return dB, None, None, None, None, None, None
 
 
-# How the frozen product runs at training row counts (M >= DENSE_M, bf16):
-#   "gemm"    (default) hand-written 256 x 256-tile GEMM (csrc/nf4_gemm.hip) on the weight decoded ONCE per call into a bf16
-#             scratch by a HIP kernel, bias and the LoRA branch fused into the GEMM (one more 32-deep step); dx through the same
-#             kernel on W^T (decoded transposed).  Measured (profiles/r02_qlora_gemm.md): 9-33 % faster than the library route
-#   "fused"   the same kernel with the NF4 codes decoded INSIDE its loop (no scratch): wins only where M / 256 is small --
-#             every 256-row block re-decodes the weight tile and the decode shares the vector ALU / LDS with the fragments
-#   "library" decode once + hipBLASLt through torch.matmul + the rank-r streaming kernels (round 1's route; kept for A/B)
-QLORA_ROUTE = os.environ.get("FASTMAX_QLORA_ROUTE", "gemm")
-
-
 def hip_gemm(x2: torch.Tensor, w: torch.Tensor, scales, bias, ea, eb, N: int) -> torch.Tensor:
     """y (M, N) = x2 (M, K) w^T + bias + ea (M, RP) eb (N, RP)^T in libfastmax_hip.so; w: dense bf16 (N, K) when ``scales`` is
     None, else the packed NF4 codes of an (N, K) weight with their block scales (decoded inside the kernel's loop)."""
@@ -551,56 +549,6 @@ def hip_gemm(x2: torch.Tensor, w: torch.Tensor, scales, bias, ea, eb, N: int) ->
                                                _stream(x2.device))
     _lib.check(rc, "fastmax_hip_qlora_gemm")
     return y
-
-
-_dense_scratch_t = {}
-
-
-# Decoded copies of FROZEN NF4 weights kept across the forward and backward passes of a step (and across steps): W (N, K) for the
-# product and W^T (K, N) for dx, decoded once per layer by the HIP kernels instead of once per layer per pass (2 x ~25 us per
-# linear per step at Llama-2-7B widths).  Kept per module up to a global budget -- the bf16 copies of a whole 7B model are 26 GB
-# of the MI355X's 288 GB; beyond the budget a layer falls back to the per-call scratch decode.  Keyed by the identity of the code
-# tensor, so quantize_base / merge / load / .to() start over.  FASTMAX_DENSE_RESIDENT_BYTES=0 turns it off.
-RESIDENT_BYTES = int(os.environ.get("FASTMAX_DENSE_RESIDENT_BYTES", str(64 << 30)))
-_resident = weakref.WeakKeyDictionary()           # NF4Linear -> {"tag": ..., "w": tensor | None, "wt": tensor | None}
-_resident_used = [0]
-
-
-def _resident_weight(base, transposed: bool):
-    """the kept bf16 W (or W^T) of an NF4Linear, decoding it on first use; None when the budget is spent or residency is off"""
-    if RESIDENT_BYTES <= 0 or base is None:
-        return None
-    wq = base.weight
-    tag = (id(wq), wq.data_ptr(), wq._version, wq.device)
-    ent = _resident.get(base)
-    if ent is None or ent["tag"] != tag:
-        if ent is not None:
-            _resident_used[0] -= sum(t.numel() * 2 for t in (ent["w"], ent["wt"]) if t is not None)
-        ent = {"tag": tag, "w": None, "wt": None}
-        _resident[base] = ent
-    key = "wt" if transposed else "w"
-    if ent[key] is None:
-        N, K = base.out_features, base.in_features
-        if _resident_used[0] + N * K * 2 > RESIDENT_BYTES:
-            return None
-        scales = scales_of(base)
-        src = _dense_weight_t(wq.data, scales, N, K) if transposed else _dense_weight(wq.data, scales, N, K)
-        ent[key] = src.clone()
-        _resident_used[0] += N * K * 2
-    return ent[key]
-
-
-def _dense_weight_t(wq, scales, N, K):
-    """bf16 (K, N) = W^T decoded from the codes of W (N, K) into a per-(device, stream) scratch (the operand of dx = dy W)"""
-    key = (wq.device, torch.cuda.current_stream(wq.device).cuda_stream)
-    buf = _dense_scratch_t.get(key)
-    if buf is None or buf.numel() < N * K:
-        buf = torch.empty(N * K, dtype=torch.bfloat16, device=wq.device)
-        _dense_scratch_t[key] = buf
-    with torch.cuda.device(wq.device):
-        rc = _lib.lib().fastmax_hip_nf4_dequantize_transposed(wq.data_ptr(), scales.ref, buf.data_ptr(), N, K, _stream(wq.device))
-    _lib.check(rc, "fastmax_hip_nf4_dequantize_transposed")
-    return buf[: N * K].view(K, N)
 
 
 def hip_gemm_rope(x2, w, bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n, tables16):
@@ -620,41 +568,90 @@ def hip_gemm_rope(x2, w, bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n
     return q, k, v
 
 
-def gemm_rope_supported(N, K, M, T, G, qpk, hs, rope_n) -> bool:
-    """shapes the fused qkv projection + RoPE epilogue takes (the 256 x 256-tile kernel: more than 128 tiles, whole heads
-    per tile); FASTMAX_GEMM_ROPE=0 turns it off"""
-    return (os.environ.get("FASTMAX_GEMM_ROPE", "1") != "0" and QLORA_ROUTE == "gemm" and N == G * (qpk + 2) * hs and 256 % hs == 0
-            and rope_n % 16 == 0 and K % 64 == 0 and M % T == 0 and ((M + 255) // 256) * ((N + 255) // 256) > 128)
+def _bias32(base: nn.Module):
+    """the frozen bias as the kernels take it: float32 data, or None"""
+    if base.bias is None:
+        return None
+    return base.bias.data if base.bias.dtype == torch.float32 else base.bias.data.float()
 
 
-_frozen_wt = weakref.WeakKeyDictionary()
+def _rows(x: torch.Tensor, K: int) -> torch.Tensor:
+    """x as (M, K) rows the kernels can address: unit column stride, 16-byte aligned rows"""
+    x2 = x.reshape(-1, K)
+    if x2.stride(1) != 1 or (x2.stride(0) * x2.element_size()) % 16 or x2.data_ptr() % 16:
+        x2 = x2.contiguous()
+    return x2
 
 
-def _frozen_transpose(owner: nn.Module) -> torch.Tensor:
-    """W^T (K, N) of a dense FROZEN base layer for the dx product, built once per layer (and again if the weight is written or
-    replaced: the entry carries the parameter's identity, version counter and device) instead of once per layer per backward
-    pass; it lives as long as the layer does.  A second N K 2 bytes per dense-base layer, on a 288 GB part."""
-    w = owner.weight
-    tag = (id(w), w._version, w.data_ptr(), w.device)
-    hit = _frozen_wt.get(owner)
-    if hit is None or hit[0] != tag:
-        hit = (tag, w.detach().t().contiguous())
-        _frozen_wt[owner] = hit
-    return hit[1]
+class _QLoRALinearFn(torch.autograd.Function):
+    """y = x deq(W)^T + bias + ea eb^T on an NF4Linear, the branch operands given (or absent).  plan.route "few_rows": all in
+    one HIP kernel (dx through the same dequant GEMM); "gemm": the tile GEMM on the decoded weight, dx on its transpose.
+    d(ea), d(eb): the streaming rank-r kernels."""
+
+    @staticmethod
+    def forward(ctx, x2, ea, eb, base, plan):
+        M = x2.shape[0]
+        N, K = base.out_features, base.in_features
+        bias = _bias32(base)
+        ctx.base, ctx.gemm = base, plan.route == "gemm"
+        ctx.save_for_backward(ea, eb)
+        if ctx.gemm:
+            return hip_gemm(x2, _weight_operand(base, False), None, bias, ea, eb, N)
+        y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
+        with torch.cuda.device(x2.device):
+            rc = _lib.lib().fastmax_hip_nf4_linear_forward_s(
+                x2.data_ptr(), x2.stride(0), base.weight.data_ptr(), scales_of(base).ref,
+                None if bias is None else bias.data_ptr(), None if ea is None else ea.data_ptr(),
+                None if eb is None else eb.data_ptr(), y.data_ptr(), N, M, N, K, _KDT[x2.dtype], _stream(x2.device))
+        _lib.check(rc, "fastmax_hip_nf4_linear_forward_s")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ea, eb = ctx.saved_tensors
+        base = ctx.base
+        N, K = base.out_features, base.in_features
+        dy = dy.contiguous()
+        M = dy.shape[0]
+        dx = d_ea = d_eb = None
+        if ctx.needs_input_grad[0] and ctx.gemm:
+            # below DENSE_M rows the call came here for its cache_dense() copy: no second resident copy is made for dx
+            dx = hip_gemm(dy, _weight_operand(base, True, allow_resident=M >= DENSE_M), None, None, None, None, K)
+        elif ctx.needs_input_grad[0]:
+            dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
+            with torch.cuda.device(dy.device):
+                rc = _lib.lib().fastmax_hip_nf4_linear_backward_input_s(dy.data_ptr(), N, base.weight.data_ptr(), scales_of(base).ref,
+                                                                        dx.data_ptr(), K, M, N, K, _KDT[dy.dtype], _stream(dy.device))
+            _lib.check(rc, "fastmax_hip_nf4_linear_backward_input_s")
+        if ea is not None:
+            # the rank-r products of the backward pass as streaming HIP kernels (lora_thin.hip), one pass over dy each
+            dyb = dy.to(torch.bfloat16)
+            if dyb.data_ptr() % 16:
+                dyb = dyb.clone()
+            RP = ea.shape[1]
+            if ctx.needs_input_grad[1]:
+                d_ea, _ = lora_down(dyb, eb.t().contiguous(), want_t=False)          # (M, RP) = dy eb
+            if ctx.needs_input_grad[2]:
+                MP = (M + 15) // 16 * 16
+                eat = torch.zeros((RP, MP), dtype=torch.bfloat16, device=dyb.device)
+                eat[:, :M] = ea.t()
+                d_eb = lora_tn(eat, dyb, dtype=torch.bfloat16, transpose=True)       # (N, RP) = dy^T ea
+        return dx, d_ea, d_eb, None, None
 
 
 class _QLoRAGemmFn(torch.autograd.Function):
-    """y = x deq(W)^T + bias + (x A^T) eb^T with every product in libfastmax_hip.so (lit_gpt/lora.py:170-177, 419-433 and
-    their autograd mirror, without dropout): the frozen product and dx by the 256 x 256-tile GEMM with the LoRA branch as
-    its last step, x A^T / dy eb by lora_down, dA / dB by lora_tn."""
+    """y = x W^T + bias + (dropout(x) A^T) eb^T with every product in libfastmax_hip.so (lit_gpt/lora.py:170-177, 419-433 and
+    their autograd mirror): the frozen product and dx by the 256 x 256-tile GEMM with the LoRA branch as its last step,
+    x A^T / dy eb by lora_down, dA / dB by lora_tn.  ``base``: an NF4Linear or a dense frozen bf16 layer."""
 
     @staticmethod
-    def forward(ctx, x2, A, ebt, wq, scales, bias, N, K, wdense, fused, rope=None, owner=None, drop_p=0.0):
+    def forward(ctx, x2, A, ebt, base, plan, rope, drop_p):
         """rope = (cos32, sin32, B, T, G, qpk, hs, rope_n, tables16, expand): the product is an attention sub-layer's qkv
         projection and leaves the kernel as (q, k, v) -- de-interleaved and rotated, in the layout of ops.RopeQKVSplit's
         `expand` mode 0 (k, v at their G heads; also mode 1 when qpk == 1), 3 or 4 (stride-0 group views) -- instead of y"""
+        N, K = base.out_features, base.in_features
         R, RP = A.shape[0], ebt.shape[0]
-        ctx.scales = scales
+        bias = _bias32(base)
         if R == RP:
             abt = A.detach().to(torch.bfloat16).contiguous()
         else:
@@ -665,176 +662,69 @@ class _QLoRAGemmFn(torch.autograd.Function):
         ctx.drop = (new_dropout_seed(x2.device), float(drop_p)) if drop_p > 0.0 else None
         ea, eat = lora_down(x2, abt, drop=ctx.drop)
         eb = ebt.t().contiguous()                                  # (N, RP): the B-side operand of the GEMM's last step
-        ctx.save_for_backward(x2, eat, abt, ebt, wq)
-        ctx.dims = (N, K, R, A.dtype)
-        ctx.rope = rope
-        ctx.dense_base = wdense if wq is None else None           # a dense frozen base: its own weight serves dx
-        ctx.dense_owner = owner if wq is None else None           # ... and its layer keeps the transposed copy
-        ctx.nf4_owner = owner if wq is not None else None         # an NF4 layer: its resident W^T (if any) serves dx
+        ctx.save_for_backward(x2, eat, abt, ebt)
+        ctx.base, ctx.rope, ctx.rank, ctx.a_dtype = base, rope, R, A.dtype
         if rope is not None:
             cos32, sin32, B, T, G, qpk, hs, rope_n, tables16, expand = rope
-            w = wdense if wdense is not None else _dense_weight(wq, scales, N, K)
-            q, k, v = hip_gemm_rope(x2, w, bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n, tables16)
+            q, k, v = hip_gemm_rope(x2, _weight_operand(base, False), bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n, tables16)
             if expand in (3, 4):                                      # ops.RopeQKVSplit's group views: nothing is copied
                 kv = lambda t: t.view(B * G, 1, T, hs).expand(B * G, qpk, T, hs)
                 return q.view(B * G, qpk, T, hs), (kv(k) if expand == 3 else k), kv(v)
             return q, k, v
-        if fused and wdense is None:
-            y = hip_gemm(x2, wq, scales, bias, ea, eb, N)
-        else:
-            y = hip_gemm(x2, wdense if wdense is not None else _dense_weight(wq, scales, N, K), None, bias, ea, eb, N)
-        return y
+        if plan.route == "gemm_fused":
+            return hip_gemm(x2, base.weight.data, scales_of(base), bias, ea, eb, N)
+        return hip_gemm(x2, _weight_operand(base, False), None, bias, ea, eb, N)
 
     @staticmethod
     def backward(ctx, dy, *more):
-        x2, eat, abt, ebt, wq = ctx.saved_tensors
-        N, K, R, a_dt = ctx.dims
+        x2, eat, abt, ebt = ctx.saved_tensors
+        N, K = ctx.base.out_features, ctx.base.in_features
         if ctx.rope is not None:
-            # gradients of q (B, G qpk, T, hs), k, v (B, G, T, hs): inverse rotation + re-interleave in one pass, then as before
-            from . import ops
-            cos32, sin32, B, T, G, qpk, hs, rope_n, _, expand = ctx.rope
-            # modes 3 / 4: the gradients of the stride-0 views arrive dense, one per query head, and the pass sums a group
+            # gradients of q (B, G qpk, T, hs), k, v (B, G, T, hs): inverse rotation + re-interleave in one pass, then as before.
+            # Modes 3 / 4: the gradients of the stride-0 views arrive dense, one per query head, and the pass sums a group
             # while it reads them -- exactly ops.RopeQKVSplit.backward
-            dy = ops.rope_qkv_backward(dy, more[0], more[1], cos32, sin32, B, T, G, qpk, hs, rope_n,
-                                       {0: 0, 1: 0, 3: 1, 4: 2}[expand]).view(B * T, N)
+            cos32, sin32, B, T, G, qpk, hs, rope_n, _, expand = ctx.rope
+            dy = rope_qkv_backward(dy, more[0], more[1], cos32, sin32, B, T, G, qpk, hs, rope_n,
+                                   {0: 0, 1: 0, 3: 1, 4: 2}[expand]).view(B * T, N)
         dy = dy.contiguous()
         dx = dA = d_ebt = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             d_ea, d_eat = lora_down(dy, ebt)
         if ctx.needs_input_grad[0]:
             # dx = dy W + d_ea abt: the GEMM over n with W^T as its weight operand and the LoRA step (d_ea, abt^T)
-            if ctx.dense_base is None:
-                wt = _resident_weight(ctx.nf4_owner, True)
-                if wt is None:
-                    wt = _dense_weight_t(wq, ctx.scales, N, K)
-            else:
-                wt = _frozen_transpose(ctx.dense_owner) if ctx.dense_owner is not None else ctx.dense_base.t().contiguous()
+            wt = _weight_operand(ctx.base, True)
             if ctx.drop is None:
                 dx = hip_gemm(dy, wt, None, None, d_ea, abt.t().contiguous(), K)
             else:
                 # the branch's share of dx passes through the same mask: the frozen product alone, then one masked rank update
                 dx = lora_up_(hip_gemm(dy, wt, None, None, None, None, K), d_ea, abt, transposed=True, drop=ctx.drop)
         if ctx.needs_input_grad[1]:
-            dA = lora_tn(d_eat, x2, R, a_dt, drop=ctx.drop)
+            dA = lora_tn(d_eat, x2, ctx.rank, ctx.a_dtype, drop=ctx.drop)
         if ctx.needs_input_grad[2]:
             d_ebt = lora_tn(eat, dy, dtype=torch.bfloat16)
-        return dx, dA, d_ebt, None, None, None, None, None, None, None, None, None, None
+        return dx, dA, d_ebt, None, None, None, None
 
 
-class _QLoRAThinFn(torch.autograd.Function):
-    """The many-rows route with the LoRA branch in libfastmax_hip.so: y = x deq(W)^T + bias + (x A^T) eb^T.
-    Base products are library GEMMs on the decoded (or cached) weight; the rank-r products are lora_down / lora_tn / lora_up,
-    one streaming pass each (lit_gpt/lora.py:170-177, 419-433 and their autograd mirror, without dropout)."""
-
-    @staticmethod
-    def forward(ctx, x2, A, ebt, wq, scales, bias, N, K, wdense):
-        R, RP = A.shape[0], ebt.shape[0]
-        ctx.scales = scales
-        if R == RP:                                   # no padding needed: use A as it is
-            abt = A.detach().to(torch.bfloat16).contiguous()
-        else:
-            abt = torch.zeros((RP, K), dtype=torch.bfloat16, device=x2.device)
-            abt[:R] = A.detach()
-        y = x2 @ (wdense if wdense is not None else _dense_weight(wq, scales, N, K)).t()
-        ea, eat = lora_down(x2, abt)
-        lora_up_(y, ea, ebt, bias, transposed=True)
-        ctx.save_for_backward(x2, eat, abt, ebt, wq)
-        ctx.wdense = wdense
-        ctx.dims = (N, K, R, A.dtype)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, eat, abt, ebt, wq = ctx.saved_tensors
-        scales = ctx.scales
-        N, K, R, a_dt = ctx.dims
-        dy = dy.contiguous()
-        dx = dA = d_ebt = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            d_ea, d_eat = lora_down(dy, ebt)
-        if ctx.needs_input_grad[0]:
-            dx = dy @ (ctx.wdense if ctx.wdense is not None else _dense_weight(wq, scales, N, K))
-            lora_up_(dx, d_ea, abt, transposed=True)
-        if ctx.needs_input_grad[1]:
-            dA = lora_tn(d_eat, x2, R, a_dt)
-        if ctx.needs_input_grad[2]:
-            d_ebt = lora_tn(eat, dy, dtype=torch.bfloat16)
-        return dx, dA, d_ebt, None, None, None, None, None, None
-
-
-def thin_route(x: torch.Tensor, base: "NF4Linear") -> bool:
-    """Does this input take the library-GEMM route with the HIP rank-r kernels?"""
-    if not LORA_THIN or x.device.type != "cuda" or x.dtype != torch.bfloat16:
-        return False
-    M = x.numel() // x.shape[-1]
-    return M >= DENSE_M or base._dense_cache is not None
-
-
-def qlora_linear_thin(x, base: "NF4Linear", A, ebt, rope=None, drop_p: float = 0.0):
-    """x: (..., K) bf16 device tensor; A: (r, K); ebt: (RP, N) bf16 operand of the branch (scaling applied, rank zero padded);
-    drop_p: LoRA dropout probability in effect (0 outside training)."""
+def qlora_linear(x: torch.Tensor, base: "NF4Linear", plan: QLoRAPlan, ea=None, eb=None) -> torch.Tensor:
+    """the frozen product of an NF4Linear on plan.route "few_rows" or "gemm", with the branch operands given or absent.
+    x: (..., K) device tensor; ea: (..., r) = dropout(x) A^T or None; eb: (N, r), scaling applied, or None."""
     N, K = base.out_features, base.in_features
-    if K % 128 or N % 64:
-        raise NotImplementedError(f"fused NF4 linear needs in_features % 128 == 0 and out_features % 64 == 0, got {K}, {N}")
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or (x2.stride(0) * x2.element_size()) % 16 or x2.data_ptr() % 16:
-        x2 = x2.contiguous()
-    bias = None if base.bias is None else base.bias.data
-    if bias is not None and bias.dtype != torch.float32:
-        bias = bias.float()
-    if not isinstance(base, NF4Linear):
-        # a dense bf16 frozen base (LoRA without quantisation, lit_gpt/lora.py:170-177): the same tile GEMM on the weight itself
-        y = _QLoRAGemmFn.apply(x2, A, ebt, None, None, bias, N, K, base.weight.data, False, rope, base, drop_p)
-        return y if rope is not None else y.reshape(*x.shape[:-1], N)
-    scales = scales_of(base)
-    if QLORA_ROUTE != "library" and N % 64 == 0 and K % 64 == 0:
-        fused = QLORA_ROUTE == "fused" and rope is None
-        wd = base._dense_cache
-        if wd is None and not fused:
-            wd = _resident_weight(base, False)                       # decoded once per layer, not once per pass
-        if rope is not None:
-            return _QLoRAGemmFn.apply(x2, A, ebt, base.weight.data, scales, bias, N, K, wd, False, rope, base, drop_p)
-        y = _QLoRAGemmFn.apply(x2, A, ebt, base.weight.data, scales, bias, N, K, wd, fused, None, base, drop_p)
-    else:
-        if drop_p > 0.0:
-            raise NotImplementedError("LoRA dropout on the many-rows route needs FASTMAX_QLORA_ROUTE=gemm (the default) or fused")
-        y = _QLoRAThinFn.apply(x2, A, ebt, base.weight.data, scales, bias, N, K, base._dense_cache)
-    return y.reshape(*x.shape[:-1], N)
-
-
-def qlora_linear(x, base: NF4Linear, ea, eb):
-    """x: (..., K) device tensor (bf16 or f32). ea: (M, r_tot) or None, eb: (N, r_tot) or None."""
-    if x.device.type != "cuda":
-        raise RuntimeError("the NF4 + LoRA linear runs on an MI355X only; there is no CPU fallback")
-    N, K = base.out_features, base.in_features
-    if K % 128 or N % 64:
-        raise NotImplementedError(f"fused NF4 linear needs in_features % 128 == 0 and out_features % 64 == 0, got {K}, {N}")
-    cdt = x.dtype if x.dtype in (torch.bfloat16, torch.float32) else torch.bfloat16
-    x2 = x.reshape(-1, K).to(cdt)
-    if x2.stride(1) != 1 or (x2.stride(0) * x2.element_size()) % 16 or x2.data_ptr() % 16:
-        x2 = x2.contiguous()
+    x2 = _rows(x.to(x.dtype if x.dtype in _KDT else torch.bfloat16), K)
     if ea is not None:
         r = ea.shape[-1]
-        library_route = cdt == torch.bfloat16 and (x2.shape[0] >= DENSE_M or base._dense_cache is not None)
-        if library_route and QLORA_ROUTE != "library" and r <= 32:
-            # decode-once route on the hand-written GEMM: the branch is its last step, rank padded to 16 or 32
-            rp = _pad_rank(r)
-            ea = F.pad(ea.reshape(-1, r).to(torch.bfloat16), (0, rp - r)).contiguous()
-            eb = F.pad(eb.to(torch.bfloat16), (0, rp - r)).contiguous()
-        elif library_route:
-            # decode-once / cached route: the LoRA branch is a plain addmm -- no padding to the fused kernel's 32-wide k-step
-            ea, eb = ea.reshape(-1, r).to(torch.bfloat16), eb.to(torch.bfloat16)
-        else:
-            ea = F.pad(ea.reshape(-1, r).to(torch.bfloat16), (0, RANK_PAD - r)).contiguous()
-            eb = F.pad(eb.to(torch.bfloat16), (0, RANK_PAD - r)).contiguous()
-    bias = None if base.bias is None else base.bias.data
-    if bias is not None and bias.dtype != torch.float32:
-        bias = bias.float()
-    wd = base._dense_cache
-    if wd is None and cdt == torch.bfloat16 and x2.shape[0] >= DENSE_M:
-        wd = _resident_weight(base, False)                       # training rows: the decoded weight stays (budgeted)
-    y = _QLoRALinearFn.apply(x2, ea, eb, base.weight.data, scales_of(base), bias, N, K, wd, base)
+        ea = F.pad(ea.reshape(-1, r).to(torch.bfloat16), (0, plan.rank_pad - r)).contiguous()
+        eb = F.pad(eb.to(torch.bfloat16), (0, plan.rank_pad - r)).contiguous()
+    y = _QLoRALinearFn.apply(x2, ea, eb, base, plan)
     return y.reshape(*x.shape[:-1], N).to(x.dtype)
+
+
+def qlora_linear_thin(x: torch.Tensor, base: nn.Module, A, ebt, rope=None, drop_p: float = 0.0, plan: QLoRAPlan = None):
+    """plan.lora "in_kernel" (x A^T and the gradients' rank-r products by the streaming kernels of lora_thin.hip): x: (..., K)
+    bf16 device tensor; base: an NF4Linear or a dense frozen bf16 layer; A: (r, K); ebt: (plan.rank_pad, N) bf16 operand of the
+    branch (scaling applied, rank zero padded); drop_p: LoRA dropout probability in effect (0 outside training).  With ``rope``
+    (see _QLoRAGemmFn.forward) the result is (q, k, v)."""
+    y = _QLoRAGemmFn.apply(_rows(x, base.in_features), A, ebt, base, plan, rope, drop_p)
+    return y if rope is not None else y.reshape(*x.shape[:-1], base.out_features)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -919,46 +809,37 @@ class LoRALinear(LoRALayer):
         d = self.lora_dropout
         return float(d.p) if isinstance(d, nn.Dropout) and self.training else 0.0
 
-    def _hand_written_dropout_ok(self) -> bool:
-        """dropout inside the rank-r kernels exists on the tile-GEMM route (FASTMAX_QLORA_ROUTE=gemm / fused)"""
-        return self._drop_p() == 0.0 or QLORA_ROUTE != "library"
-
-    def rope_fusable(self, x: torch.Tensor) -> bool:
-        """would forward(x, rope=...) take the one-kernel route (qkv projection + de-interleave + RoPE)?"""
-        if not (self._lora_enabled() and self.lora_A.shape[0] <= RANK_PAD):
-            return False
-        if not isinstance(self.linear, NF4Linear):
-            return self._dense_base_on_tile_gemm(x)
-        return thin_route(x, self.linear) and QLORA_ROUTE == "gemm"
+    def plan(self, x: torch.Tensor, rope_shape=None) -> QLoRAPlan:
+        """the route forward(x) takes; with rope_shape = (T, groups, q per kv, head size, rope_n), .rope says whether
+        forward(x, rope=...) may be asked for the one-kernel qkv projection + de-interleave + RoPE"""
+        lin = self.linear
+        if isinstance(lin, NF4Linear):
+            kind = "nf4"
+        else:
+            w = getattr(lin, "weight", None)
+            frozen_bf16 = isinstance(lin, nn.Linear) and w.dtype == torch.bfloat16 and not w.requires_grad and w.is_contiguous()
+            kind = "dense" if frozen_bf16 else "other"
+        bias = getattr(lin, "bias", None)
+        enabled = self._lora_enabled()
+        return qlora_plan(kind, x.device.type, x.dtype, x.numel() // x.shape[-1], getattr(lin, "in_features", 0),
+                          getattr(lin, "out_features", 0), rank=self.lora_A.shape[0] if enabled else 0, drop_p=self._drop_p(),
+                          cache_dense=getattr(lin, "_dense_cache", None) is not None, lora_enabled=enabled,
+                          bias_trains=bias is not None and bias.requires_grad, rope_shape=rope_shape)
 
     def forward(self, x: torch.Tensor, rope=None) -> torch.Tensor:
-        if not self._lora_enabled():
+        plan = self.plan(x, None if rope is None else rope[3:8])
+        if rope is not None and not plan.rope:
+            raise RuntimeError(f"the qkv + RoPE epilogue was asked of a call whose plan does not allow it: {plan}")
+        if plan.lora == "none":
             return self.linear(x)
-        if isinstance(self.linear, NF4Linear) and self.lora_A.shape[0] <= RANK_PAD:
-            if thin_route(x, self.linear) and self._hand_written_dropout_ok():
-                return qlora_linear_thin(x, self.linear, self.lora_A, self._dense_rows_t(), rope, self._drop_p())
+        if plan.lora == "in_kernel":
+            return qlora_linear_thin(x, self.linear, self.lora_A, self._dense_rows_t(), rope, self._drop_p(), plan)
+        if plan.lora == "operands":
             ea = F.linear(self.lora_dropout(x), self.lora_A.to(x.dtype))
-            return qlora_linear(x, self.linear, ea, self._dense_rows() * self.scaling)
-        if self._dense_base_on_tile_gemm(x):
-            return qlora_linear_thin(x, self.linear, self.lora_A, self._dense_rows_t(), rope, self._drop_p())
+            return qlora_linear(x, self.linear, plan, ea, self._dense_rows() * self.scaling)
         pretrained = self.linear(x)
         lora = (self.lora_dropout(x) @ self.lora_A.transpose(0, 1).to(x.dtype)) @ self._dense_rows().transpose(0, 1).to(x.dtype)
         return pretrained + lora * self.scaling
-
-    def _dense_base_on_tile_gemm(self, x: torch.Tensor) -> bool:
-        """a dense (unquantised) frozen bf16 base at training row counts: the hand-written tile GEMM with the LoRA branch and
-        the bias fused, like the NF4 route after its decode (FASTMAX_DENSE_LORA_GEMM=0: tensor ops, as the reference)"""
-        lin = self.linear
-        if isinstance(lin, NF4Linear) or not isinstance(lin, nn.Linear) or os.environ.get("FASTMAX_DENSE_LORA_GEMM", "1") == "0":
-            return False
-        M = x.numel() // x.shape[-1]
-        w = lin.weight
-        # the tile GEMM's autograd function treats the base (weight AND bias) as frozen data: a trainable bias
-        # (mark_only_lora_as_trainable(bias="all" / "lora_only"), lit_gpt/lora.py:436-461) stays on the tensor-op route
-        frozen_bias = lin.bias is None or not lin.bias.requires_grad
-        return (LORA_THIN and QLORA_ROUTE == "gemm" and x.device.type == "cuda" and x.dtype == torch.bfloat16
-                and w.dtype == torch.bfloat16 and not w.requires_grad and frozen_bias and w.is_contiguous() and M >= DENSE_M
-                and self.lora_A.shape[0] <= RANK_PAD and lin.in_features % 128 == 0 and lin.out_features % 64 == 0)
 
 
 class LoRAQKVLinear(LoRALinear):
@@ -1068,10 +949,10 @@ def lora_filter(key: str, value: Any) -> bool:
 
 
 def enable_gemm_tuning(filename: str = None, tune: bool = True) -> None:
-    """Opt-in: let PyTorch's TunableOp pick the hipBLASLt solution for the dense GEMMs of the many-rows route (the decoded
-    frozen weight times x / dy).  The library's default heuristic is not the fastest solution at these shapes: measured on the
-    TinyLlama sub-layer (16384 rows), 1.37 -> 1.25-1.30 ms forward+backward.  The first call of every new shape is timed
-    over the candidate solutions (seconds); `filename` keeps the choices across runs."""
+    """Opt-in: let PyTorch's TunableOp pick the hipBLASLt solution for the GEMMs torch still runs (the tensor-op LoRA form, the
+    head).  hipBLASLt's default heuristic is not its fastest solution at training shapes: measured in round 1, when the frozen
+    product itself was such a GEMM, on the TinyLlama sub-layer (16384 rows), 1.37 -> 1.25-1.30 ms forward+backward.  The first
+    call of every new shape is timed over the candidate solutions (seconds); `filename` keeps the choices across runs."""
     torch.cuda.tunable.enable(True)
     torch.cuda.tunable.tuning_enable(bool(tune))
     if filename:

@@ -230,3 +230,57 @@ def test_mark_only_lora_as_trainable_bias_modes():
     assert not flags()["0.linear.bias"] and not flags()["1.bias"]
     with pytest.raises(NotImplementedError):
         lora.mark_only_lora_as_trainable(m, bias="some")
+
+
+# ---- the route plan -------------------------------------------------------------------------
+def _route_rows():
+    import json
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import qlora_routes
+    with open(qlora_routes.GOLDEN) as f:
+        return qlora_routes, json.load(f)
+
+
+def test_route_plan_answers_as_recorded():
+    """tests/golden/qlora_routes.json: for every row of plain-data arguments, what the layers ran on an MI355X before the plan
+    existed (which autograd Function, which branch of it, which rank padding, whether the RoPE epilogue ran)"""
+    tool, golden = _route_rows()
+    assert [g["args"] for g in golden] == tool.rows() and len(golden) > 250
+    bad = [(g["args"], g["plan"], tool.answer(g["args"])) for g in golden if tool.answer(g["args"]) != g["plan"]]
+    assert not bad, f"{len(bad)} rows differ, first (arguments, recorded, now): {bad[0]}"
+
+
+def test_route_rows_reach_every_answer():
+    _, golden = _route_rows()
+    plans = [g["plan"] for g in golden]
+    assert {p.get("route") for p in plans} == {"tensor_ops", "few_rows", "gemm", "gemm_fused", None}
+    assert {p.get("lora") for p in plans} == {"none", "in_kernel", "operands", "tensor_ops", None}
+    assert {p.get("rank_pad") for p in plans} == {0, 16, 32, None}
+    assert {p.get("dropout") for p in plans} == {"none", "in_kernel", "tensor_op", None}
+    assert {p.get("rope") for p in plans} == {True, False, None}
+    assert {p.get("raises") for p in plans} == {"RuntimeError", None}
+
+
+def test_layers_read_the_plan(monkeypatch):
+    """the layer's plan() feeds qlora_plan from its own state; a RoPE request the plan
+    does not allow raises instead of returning an unrotated product"""
+    layer = lora.LoRALinear(256, 384, r=8, lora_alpha=16, lora_dropout=0.05).to(torch.bfloat16)
+    lora.mark_only_lora_as_trainable(layer)
+    x = torch.empty(2048, 256, dtype=torch.bfloat16, device="meta")
+    assert layer.plan(x) == lora.QLoRAPlan("tensor_ops", "tensor_ops", 0, "tensor_op", False)      # not on the GPU
+    seen = []
+    monkeypatch.setattr(lora, "qlora_plan", lambda *a, **k: seen.append((a, k)) or lora.QLoRAPlan("tensor_ops", "none", 0, "none", False))
+    layer.eval()
+    layer.merged = True
+    layer.plan(x, rope_shape=(2048, 2, 4, 32, 32))
+    (a, k), = seen
+    assert a == ("dense", "meta", torch.bfloat16, 2048, 256, 384)
+    assert k == dict(rank=0, drop_p=0.0, cache_dense=False, lora_enabled=False, bias_trains=False, rope_shape=(2048, 2, 4, 32, 32))
+    monkeypatch.undo()
+    layer.merged = False
+    with pytest.raises(RuntimeError, match="RoPE"):
+        layer(torch.zeros(4, 256, dtype=torch.bfloat16), rope=(None, None, 1, 4, 2, 4, 32, 32, False, 0))
+    with pytest.raises(NotImplementedError):
+        lora.qlora_plan("nf4", "cuda", torch.bfloat16, 4, 64, 64)

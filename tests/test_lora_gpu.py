@@ -210,9 +210,9 @@ def test_lora_thin_kernels_against_tensor_ops(M, K, N, R):
 
 
 @pytest.mark.parametrize("kind", ["linear", "qkv_gqa_qv", "qkv_gqa_all"])
-def test_many_rows_route_matches_the_tensor_op_route(kind, monkeypatch):
-    """M >= DENSE_M: the HIP rank-r route (_QLoRAThinFn) against the same layer with FASTMAX_LORA_THIN off (library GEMMs
-    for every product) and against the dense float32 formulation -- forward, dx, dA, dB"""
+def test_many_rows_route_matches_the_tensor_op_route(kind):
+    """M >= DENSE_M: the tile-GEMM route with the HIP rank-r kernels against the same function as plain bf16 tensor ops on the
+    dequantised weight (library GEMMs for every product, autograd for dx, dA, dB) and against the dense float32 formulation"""
     from fastmax_experiments_amd import lora
     torch.manual_seed(3)
     if kind == "linear":
@@ -225,21 +225,22 @@ def test_many_rows_route_matches_the_tensor_op_route(kind, monkeypatch):
     layer.quantize_base().cuda().to(torch.bfloat16)
     lora.mark_only_lora_as_trainable(layer)
     x = torch.randn(3, 700, 256, device="cuda", dtype=torch.bfloat16)
-    gy = None
-    res = []
-    for thin in (True, False):
-        monkeypatch.setattr(lora, "LORA_THIN", thin)
-        assert lora.thin_route(x, layer.linear) == thin
-        xx = x.clone().requires_grad_(True)
-        y = layer(xx)
-        if gy is None:
-            gy = torch.randn_like(y)
-        y.backward(gy)
-        res.append((y.detach(), xx.grad, layer.lora_A.grad.clone(), layer.lora_B.grad.clone()))
-        layer.lora_A.grad = layer.lora_B.grad = None
-    for a, b in zip(*res):
+    plan = layer.plan(x)
+    assert (plan.route, plan.lora, plan.rank_pad) == ("gemm", "in_kernel", 16 if layer.lora_A.shape[0] <= 16 else 32)
+    xx = x.clone().requires_grad_(True)
+    y = layer(xx)
+    gy = torch.randn_like(y)
+    y.backward(gy)
+    got = (y.detach(), xx.grad, layer.lora_A.grad.clone(), layer.lora_B.grad.clone())
+    layer.lora_A.grad = layer.lora_B.grad = None
+    xx = x.clone().requires_grad_(True)
+    yr = F.linear(xx, layer.linear.dequantize(torch.bfloat16), layer.linear.bias.to(torch.bfloat16))
+    yr = yr + (xx @ layer.lora_A.t()) @ (layer._dense_rows() * layer.scaling).t()
+    yr.backward(gy)
+    want = (yr.detach(), xx.grad, layer.lora_A.grad.clone(), layer.lora_B.grad.clone())
+    for a, b in zip(got, want):
         assert a.dtype == b.dtype and _rel(a, b) < 2e-2
-    assert _rel(res[0][0], _dense_reference(layer, x)) < 2e-2
+    assert _rel(got[0], _dense_reference(layer, x)) < 2e-2
 
 
 def test_many_rows_route_keeps_the_hand_written_kernels_under_dropout(monkeypatch):
@@ -439,15 +440,13 @@ def test_hand_written_qlora_gemm(M, N, K, rp, dq):
     assert torch.equal(y_dense, y_nf4)                      # same bf16 weight values either way -> the same bits
     assert torch.equal(y_dense, y_dense256)                 # same accumulation order per element in both tilings
     if N % 64 == 0 and K % 64 == 0:
-        wt = lora._dense_weight_t(q.weight.data, scales, N, K)
-        assert torch.equal(wt, wd.t())
+        assert torch.equal(lora._decode_scratch(q, True), wd.t())
 
 
-@pytest.mark.parametrize("route", ["gemm", "fused", "library"])
+@pytest.mark.parametrize("route", ["gemm", "fused"])
 def test_training_size_qlora_layer_routes_agree(route, monkeypatch):
-    """LoRAQKVLinear at a training row count through the three routes of the frozen product (hand-written GEMM on the decoded
-    weight -- the default --, NF4 decoded inside the GEMM loop, decode once + library GEMM): forward and all gradients against
-    dense float32 math"""
+    """LoRAQKVLinear at a training row count through the two routes of the frozen product (hand-written GEMM on the decoded
+    weight -- the default --, NF4 decoded inside the GEMM loop): forward and all gradients against dense float32 math"""
     from fastmax_experiments_amd import lora
     monkeypatch.setattr(lora, "QLORA_ROUTE", route)
     torch.manual_seed(7)
@@ -514,10 +513,10 @@ def test_dense_base_lora_layers_on_the_tile_gemm(kind, monkeypatch):
     x = torch.randn(2, 1500, 256, device="cuda", dtype=torch.bfloat16)
     gy = None
     res = []
-    for flag in ("1", "0"):
-        monkeypatch.setenv("FASTMAX_DENSE_LORA_GEMM", flag)
+    for tile_gemm in (True, False):
+        monkeypatch.setattr(lora, "DENSE_LORA_GEMM", tile_gemm)
         xa = x.clone().requires_grad_(True)
-        assert layer._dense_base_on_tile_gemm(xa) == (flag == "1")
+        assert (layer.plan(xa).route == "gemm") == tile_gemm
         y = layer(xa)
         gy = torch.randn_like(y) if gy is None else gy
         y.backward(gy)
@@ -538,23 +537,25 @@ def test_dense_base_with_a_trainable_bias_keeps_its_gradient():
     torch.nn.init.normal_(layer.lora_B, std=0.05)
     lora.mark_only_lora_as_trainable(layer, bias="all")
     x = torch.randn(2, 1500, 256, device="cuda", dtype=torch.bfloat16, requires_grad=True)
-    assert layer.linear.bias.requires_grad and not layer._dense_base_on_tile_gemm(x)
+    assert layer.linear.bias.requires_grad and layer.plan(x).route == "tensor_ops"
     layer(x).sum().backward()
     assert layer.linear.bias.grad is not None and float(layer.linear.bias.grad.float().abs().sum()) > 0
     # frozen bias: the tile GEMM route, with W^T cached per layer
     lora.mark_only_lora_as_trainable(layer)
-    assert layer._dense_base_on_tile_gemm(x)
+    assert layer.plan(x).route == "gemm"
+    used = lora._resident_used[0]
     for _ in range(2):
         x.grad = None
         layer(x).sum().backward()
-    wt = lora._frozen_wt[layer.linear][1]
+    wt = lora._resident[layer.linear]["wt"]
     assert torch.equal(wt, layer.linear.weight.detach().t())
+    assert lora._resident_used[0] == used                            # a dense transpose is not counted against the budget
     first = x.grad.clone()
     with torch.no_grad():
         layer.linear.weight.mul_(0.5)                                # written in place: the version counter moves
     x.grad = None
     layer(x).sum().backward()
-    assert lora._frozen_wt[layer.linear][1] is not wt
+    assert lora._resident[layer.linear]["wt"] is not wt
     assert not torch.equal(x.grad, first)
 
 
@@ -599,3 +600,61 @@ def test_decoded_weights_stay_resident_across_passes(monkeypatch):
     layer.merged = False
     run()
     assert not torch.equal(lora._resident[layer.linear]["w"], ent["w"])
+
+
+def test_operand_source_does_not_change_the_bits(monkeypatch):
+    """M = 2304 on the default route: the tile GEMM reads the same bf16 weight values whether they come from the per-call
+    scratch decode, the resident copy or the cache_dense() copy, so forward and every gradient are the same bits"""
+    from fastmax_experiments_amd import lora
+    torch.manual_seed(9)
+    layer = lora.LoRALinear(256, 384, r=8, lora_alpha=16, bias=True)
+    torch.nn.init.normal_(layer.lora_B, std=0.05)
+    layer.quantize_base().cuda().to(torch.bfloat16)
+    lora.mark_only_lora_as_trainable(layer)
+    x = torch.randn(2304, 256, device="cuda", dtype=torch.bfloat16)
+    gy = torch.randn(2304, 384, device="cuda", dtype=torch.bfloat16)
+
+    def run():
+        assert layer.plan(x)[:3] == ("gemm", "in_kernel", 16)
+        xa = x.clone().requires_grad_(True)
+        y = layer(xa)
+        y.backward(gy)
+        out = (y.detach().clone(), xa.grad.clone(), layer.lora_A.grad.clone(), layer.lora_B.grad.clone())
+        layer.lora_A.grad = layer.lora_B.grad = None
+        return out
+
+    monkeypatch.setattr(lora, "RESIDENT_BYTES", 0)
+    scratch = run()
+    assert layer.linear not in lora._resident
+    monkeypatch.setattr(lora, "RESIDENT_BYTES", 1 << 30)
+    resident = run()
+    assert lora._resident[layer.linear]["w"] is not None and lora._resident[layer.linear]["wt"] is not None
+    layer.linear.cache_dense()
+    cached = run()
+    for a, b, c in zip(scratch, resident, cached):
+        assert torch.equal(a, b) and torch.equal(a, c)
+
+
+def _parity_cases():
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import qlora_parity
+    return qlora_parity
+
+
+@pytest.mark.parametrize("name", _parity_cases().ALL_HIP)
+def test_all_hip_cases_give_the_recorded_bits(name, monkeypatch):
+    """tests/golden/qlora_parity.json: digests of y, dx, dA, dB recorded (tools/qlora_parity.py) from the layers as they were
+    before the route plan and the single weight source existed, for every case whose products are all kernels of
+    libfastmax_hip.so -- the same kernels on the same operand values give the same bits"""
+    import json
+    from fastmax_experiments_amd import lora
+    parity = _parity_cases()
+    with open(parity.GOLDEN) as f:
+        want = json.load(f)[name]
+    ropes = []
+    real = lora.hip_gemm_rope
+    monkeypatch.setattr(lora, "hip_gemm_rope", lambda *a, **k: (ropes.append(1), real(*a, **k))[1])
+    assert parity.run_case(name) == want
+    assert bool(ropes) == name.startswith("rope_block")              # the RoPE case, and only it, takes the tile epilogue

@@ -67,8 +67,8 @@ def main():
             print(f"| {M} | {N} | {K} | {name} | {ms:.3f} | {flops / ms / 1e9:.0f} | {err} |", flush=True)
 
         row("library: x @ Wd^T (weight already dense)", lambda: x @ wd.t())
-        row("library route: decode once + x @ Wd^T + addmm(ea, eb) + bias",
-            lambda: (x @ lora._dense_weight(q.weight.data, scales, N, K).t()).addmm_(ea, eb.t()).add_(q.bias.to(torch.bfloat16)))
+        row("torch GEMMs: decode once + x @ Wd^T + addmm(ea, eb) + bias",
+            lambda: (x @ lora._decode_scratch(q, False).t()).addmm_(ea, eb.t()).add_(q.bias.to(torch.bfloat16)))
         for sched, label in ((0, "default loop (copies by one wave of a SIMD pair, fragments read under the MFMAs)"),
                              (14, "plain loop (every wave: copies, reads, MFMAs)"), (12, "128 x 256 tiles"), (13, "256 x 256 tiles forced")):
             _lib.check(_lib.lib().fastmax_hip_tune(b"gemm_sched", sched), "tune")
@@ -80,7 +80,7 @@ def main():
                 lambda: gemm(x, q.weight.data, scales, q.bias, ea, eb), lambda: gemm(x, q.weight.data, scales, q.bias, ea, eb))
         _lib.check(_lib.lib().fastmax_hip_tune(b"gemm_sched", 0), "tune")
         row("hand-written pair (sched 0): HIP decode to bf16 scratch + dense-W kernel (+ bias + LoRA step)",
-            lambda: gemm(x, lora._dense_weight(q.weight.data, scales, N, K), None, q.bias, ea, eb))
+            lambda: gemm(x, lora._decode_scratch(q, False), None, q.bias, ea, eb))
 
 
 if __name__ == "__main__":
