@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
-header (OPTIM_HEADER) has the table OPTIM_ABI, set on the same handle.
+header (OPTIM_HEADER) has the table OPTIM_ABI and the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, set on
+the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -132,6 +133,14 @@ OPTIM_ABI = {
     "fastmax_hip_adamw_update": (ci, [vp, ci, i64, vp, vp, vp, i64, vp, i64, vp, i64, cf, vp, cf, cf, cf, cf, cf, cf, cf, cf,
                                       ci, ci, ci, vp, sz, vp]),
 }
+# the next-token head's side header (last-row logits, exact top-k, seeded sampling): same library, same FASTMAX_ABI_VERSION
+# (additions only), a table of its own.  tests/test_next_token_cpu.py checks each row against the prototype.
+NEXT_TOKEN_HEADER = "fastmax_hip_next_token.h"
+NEXT_TOKEN_ABI = {
+    "fastmax_hip_last_logits": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_sample": (ci, [vp, i64, vp, ci, ci, ci, cf, i64, i64, vp]),
+    "fastmax_hip_topk_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -145,7 +154,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")
