@@ -21,15 +21,26 @@ o_i = (S1 + a qc_i^T S2) / (count + a qc_i . ksum) over sums of the centred, UNS
 rescaling and only two running maxima move (decode.py).  Each of the T rows sees the statistics of everything up to the last
 new token, as the masked forward over that sequence would compute them.
 """
+import importlib
+from typing import NamedTuple, Union
+
 import torch
 import torch.nn as nn
 
-from . import lora, ops
-from .attention_mechanisms.fastmax import fastmax
-from .attention_mechanisms.fastmax_hack import fastmax_hack, fastmax_hack_grouped, grouped_route_supported
+from . import ops
+from .attention_mechanisms.fastmax import MAX_HEADS_PER_LAUNCH, fastmax
+from .attention_mechanisms.fastmax_hack import LinearmaxPlan, fastmax_hack_grouped, linearmax, linearmax_plan
 from .decode import FastmaxDecodeState, LinearmaxDecodeState
 from .lora import LoRALinear, LoRAQKVLinear
 from .ops import apply_rope, build_rope_cache  # noqa: F401  (re-exported: the public RoPE formula lives beside its kernels)
+
+_switches = importlib.import_module(linearmax.__module__)          # the module (its package rebinds the name to the function)
+
+
+class AttentionPlan(NamedTuple):
+    qkv: str                                 # how q, k, v are produced: "gemm_epilogue", "hip_pass" or "eager"
+    kv_layout: int                           # the K / V layout handed on: one of ops.KV_LAYOUTS
+    operator: Union[str, LinearmaxPlan]      # "fastmax" (p = 2), or the linearmax call's own plan
 
 
 class CausalSelfAttention(nn.Module):
@@ -66,55 +77,70 @@ class CausalSelfAttention(nn.Module):
         """``state`` (a ``FastmaxDecodeState(B, n_head, head_size, p=2, n_query_groups=...)``; for a ``linearmax`` block a
         ``LinearmaxDecodeState(B, n_head, head_size, device, n_query_groups=...)``): generate on the decode state cache.  x holds the T new tokens, cos / sin the rope rows of their positions (``index_select(0, input_pos)`` of the
         cache, as the reference's GPT.forward passes them); ``input_pos`` itself is never read, so nothing syncs with the host.
-        Without ``state`` every path is what it was."""
+        Without ``state``: ``plan``, one of its three q, k, v producers, the operator."""
         B, T, C = x.size()
         if state is not None:
             y = self.attend_cached(x, cos, sin, state)
-            return self.proj(y.reshape(B, T, self.head_size * self.n_head))      # model.py:453-455 (no transpose: quirk Q3)
-        q_per_kv = self.n_head // self.n_query_groups
-        total_qkv = q_per_kv + 2
-        if self._one_kernel_qkv(x, input_pos, B, T, q_per_kv):
-            return self._forward_one_kernel_qkv(x, cos, sin, B, T, q_per_kv)
-        qkv = self.attn(x)
-        fused = (self.fused_neighbours and x.device.type == "cuda" and input_pos is None and
-                 ops.rope_qkv_supported(qkv.dtype, self.head_size, self.rope_n_elem))
-        grouped = fused and self._grouped_training_route(x, qkv.dtype, B, q_per_kv)
-        views = fused and q_per_kv > 1 and self.group_views
-        if grouped:
-            # training, grouped-query heads: K stays at its n_query_groups heads through RoPE and the linearmax prologue
-            # (statistics and gradient once per key head).  group_views: neither K nor V is ever copied per query head --
-            # (batch, group) is the kernels' batch axis and K, V are stride-0 views; else the prologue's store writes the copies
-            q, k, v = ops.RopeQKVSplit.apply(qkv.view(B, T, self.n_query_groups, total_qkv, self.head_size), cos, sin,
-                                             self.rope_n_elem, 4 if views else 2)
-            y = fastmax_hack_grouped(q, k, v, q_per_kv, p=1)
-            y = y.reshape(B, T, self.head_size * self.n_head)      # model.py:453-455 (no transpose: quirk Q3)
-            return self.proj(y)
-        elif fused:
-            # de-interleave + RoPE (+ GQA expand, or group views: see ops.RopeQKVSplit) in one HIP pass (SURVEY.md 8f row 1)
-            q, k, v = ops.RopeQKVSplit.apply(qkv.view(B, T, self.n_query_groups, total_qkv, self.head_size), cos, sin,
-                                             self.rope_n_elem, 3 if views else 1)
         else:
-            # shapes the one-pass kernel does not take (decode with input_pos, rotary widths that are not whole 16-byte
-            # pieces): plain slicing of the (B, T, group, slot, hs) view -- slots 0..q_per_kv-1 are the group's query heads,
-            # then its key head, then its value head (model.py:397-420) -- with K, V repeated per query head
-            q, k, v = ops.eager_rope_qkv_split(qkv.view(B, T, self.n_query_groups, total_qkv, self.head_size), cos, sin,
-                                               self.rope_n_elem)
-            k, v = (t.repeat_interleave(q_per_kv, dim=1) for t in (k, v))
-        mask = input_pos is None                                   # model.py:462-466, 477-481
-        if self.attn_alg == "linearmax":
-            y = fastmax_hack(q, k, v, p=1, mask=mask)              # model.py:472
-        else:
-            y = fastmax(q, k, v, p=2, mask=mask)                   # model.py:485, minus the .cpu()/.cuda() hops
-        y = y.reshape(B, T, self.head_size * self.n_head)          # model.py:453-455 (no transpose: quirk Q3)
-        return self.proj(y)
+            plan = self.plan(x, input_pos)
+            G, hs, n = self.n_query_groups, self.head_size, self.rope_n_elem
+            q_per_kv = self.n_head // G
+            if plan.qkv == "gemm_epilogue":
+                tables16 = cos.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float16)
+                cos32, sin32 = ops._rope_tables_f32(cos, sin, T, n)
+                q, k, v = self.attn(x, rope=(cos32, sin32, B, T, G, q_per_kv, hs, n, tables16, plan.kv_layout))
+            elif plan.qkv == "hip_pass":
+                # de-interleave + RoPE (+ GQA expand, or group views: see ops.KV_LAYOUTS) in one HIP pass (SURVEY.md 8f row 1)
+                q, k, v = ops.RopeQKVSplit.apply(self.attn(x).view(B, T, G, q_per_kv + 2, hs), cos, sin, n, plan.kv_layout)
+            else:
+                # plain slicing of the (B, T, group, slot, hs) view -- slots 0..q_per_kv-1 are the group's query heads, then its
+                # key head, then its value head (model.py:397-420) -- with K, V repeated per query head
+                q, k, v = ops.eager_rope_qkv_split(self.attn(x).view(B, T, G, q_per_kv + 2, hs), cos, sin, n)
+                k, v = (t.repeat_interleave(q_per_kv, dim=1) for t in (k, v))
+            y = self._attend(q, k, v, plan.operator, input_pos is None, q_per_kv)
+        return self.proj(y.reshape(B, T, self.head_size * self.n_head))      # model.py:453-455 (no transpose: quirk Q3)
 
-    def _grouped_training_route(self, x, dtype, B, q_per_kv) -> bool:
-        """training with grouped-query heads on a linearmax block: K stays at its n_query_groups heads through RoPE and the
-        prologue (fastmax_hack_grouped).  ``dtype``: the QKV projection's output dtype; on the one-kernel route, which takes
-        bf16 in and gives bf16 out, that is x's own"""
-        return (self.attn_alg == "linearmax" and q_per_kv > 1 and torch.is_grad_enabled() and
-                (x.requires_grad or any(p.requires_grad for p in self.attn.parameters())) and
-                grouped_route_supported(x.device, dtype, self.head_size, B * self.n_head))
+    def plan(self, x, input_pos=None) -> AttentionPlan:
+        """The one decision "how does forward(x, cos, sin, input_pos) run", from x's device, dtype, shape and grad state, the
+        instance switches (fused_neighbours, group_views, gemm_rope) and the QKV projection's own plan; nothing is computed.
+          qkv        "gemm_epilogue": projection, de-interleave and RoPE as ONE kernel (nf4_gemm.hip's tile epilogue) -- where the
+                     projection's plan allows it and the K / V layout needs no per-head copies (group views, or one query head per
+                     group); "hip_pass": ops.RopeQKVSplit after the projection; "eager": tensor slicing, for what the pass does
+                     not take (decode with input_pos, rotary widths that are not whole 16-byte pieces)
+          kv_layout  one of ops.KV_LAYOUTS.  Training a linearmax block with grouped-query heads keeps K at its n_query_groups
+                     heads through RoPE and the prologue (statistics and gradient once per key head); group_views: neither K nor
+                     V is ever copied per query head, else the prologue's store writes the copies
+          operator   "fastmax" (p = 2), or the linearmax_plan record of the call as it is launched"""
+        B, T = x.shape[:2]
+        G, hs, n = self.n_query_groups, self.head_size, self.rope_n_elem
+        q_per_kv = self.n_head // G
+        mask = input_pos is None                                   # model.py:462-466, 477-481
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.attn.parameters()))
+        hip_pass = self.fused_neighbours and x.device.type == "cuda" and mask and ops.rope_qkv_supported(x.dtype, hs, n)
+        views = hip_pass and q_per_kv > 1 and self.group_views
+        k_groups = (hip_pass and self.attn_alg == "linearmax" and q_per_kv > 1 and needs_grad and _switches.GROUPED_K
+                    and B * self.n_head <= MAX_HEADS_PER_LAUNCH)
+        if (hip_pass and self.gemm_rope and x.dtype == torch.bfloat16 and isinstance(self.attn, LoRAQKVLinear)
+                and (views or q_per_kv == 1) and self.attn.plan(x, (T, G, q_per_kv, hs, n)).rope):
+            qkv, layout = "gemm_epilogue", (ops.KV_GROUPS if q_per_kv == 1 else ops.K_GROUPS_V_VIEWS if k_groups else ops.KV_VIEWS)
+        elif hip_pass:
+            qkv = "hip_pass"
+            layout = ((ops.K_GROUPS_V_VIEWS if views else ops.K_GROUPS_V_COPIES) if k_groups else
+                      (ops.KV_VIEWS if views else ops.KV_COPIES))
+        else:
+            qkv, layout = "eager", ops.KV_COPIES
+        if self.attn_alg != "linearmax":
+            return AttentionPlan(qkv, layout, "fastmax")
+        heads = (B * G, q_per_kv) if ops.KV_LAYOUTS[layout].v == "views" else (B, self.n_head)
+        return AttentionPlan(qkv, layout, linearmax_plan(x.dtype, *heads, T, T, hs, 1, mask, needs_grad, q_per_kv if k_groups else 1,
+                                                         k_groups and views))
+
+    def _attend(self, q, k, v, operator, mask, q_per_kv):
+        if operator == "fastmax":
+            return fastmax(q, k, v, p=2, mask=mask)                # model.py:485, minus the .cpu()/.cuda() hops
+        if operator.k_layout == "per_head":
+            return linearmax(q, k, v, operator, p=1, mask=mask)      # model.py:472
+        return fastmax_hack_grouped(q, k, v, q_per_kv, p=1, plan=operator)
 
     def attend_cached(self, x, cos, sin, state):
         """the attention of ``forward(..., state=...)`` before the head-mixing reshape: x (B,T,C) -> (B, n_head, T, head_size) =
@@ -137,32 +163,6 @@ class CausalSelfAttention(nn.Module):
         if T == 1 and state.count > 0:
             return state.step_qkv(qkv, cos, sin, self.rope_n_elem)
         return state.extend_qkv(qkv, cos, sin, self.rope_n_elem)
-
-    def _one_kernel_qkv(self, x, input_pos, B, T, q_per_kv) -> bool:
-        """can the qkv projection, the de-interleave and RoPE run as ONE kernel (nf4_gemm.hip's tile epilogue)?  Training-size bf16
-        input on the hand-written GEMM route, whole heads per 256-column tile, and a K / V layout that needs no per-head copies
-        (group views, or one query head per group)"""
-        attn = self.attn
-        if not (self.fused_neighbours and self.gemm_rope and x.device.type == "cuda" and input_pos is None and x.dtype == torch.bfloat16):
-            return False
-        if not isinstance(attn, lora.LoRAQKVLinear) or (q_per_kv > 1 and not self.group_views):
-            return False
-        return (ops.rope_qkv_supported(x.dtype, self.head_size, self.rope_n_elem) and
-                attn.plan(x, (T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem)).rope)
-
-    def _forward_one_kernel_qkv(self, x, cos, sin, B, T, q_per_kv):
-        tables16 = cos.dtype == x.dtype and x.dtype in (torch.bfloat16, torch.float16)
-        cos32, sin32 = ops._rope_tables_f32(cos, sin, T, self.rope_n_elem)
-        grouped = self._grouped_training_route(x, x.dtype, B, q_per_kv)
-        expand = (4 if grouped else 3) if q_per_kv > 1 else 0
-        q, k, v = self.attn(x, rope=(cos32, sin32, B, T, self.n_query_groups, q_per_kv, self.head_size, self.rope_n_elem, tables16, expand))
-        if grouped:
-            y = fastmax_hack_grouped(q, k, v, q_per_kv, p=1)
-        elif self.attn_alg == "linearmax":
-            y = fastmax_hack(q, k, v, p=1, mask=True)
-        else:
-            y = fastmax(q, k, v, p=2, mask=True)
-        return self.proj(y.reshape(B, T, self.head_size * self.n_head))
 
 
 # head shapes of the BASELINE.json configs (lit_gpt/config.py:197-205, 1394-1411, 735-747) and of the reference config with the

@@ -4,21 +4,73 @@ Reference: fastmax_hack.py:5-60.  Masked branch (36-60): mean-centre / max-norm 
 first- or second-order fastmax with normalize_term = 1.  Unmasked branch (6-33): same prologue,
 first order only (``p`` is ignored there), denominator constant N_k (line 21), float32 ``ones``
 promote low-precision inputs to a float32 result.
-The prologue and the attention both run in libfastmax_hip.so; gradients flow through
-``_NormalizeQK`` (the reference gets them from plain autograd over its einsum graph).
+The prologue and the attention both run in libfastmax_hip.so.  Which autograd nodes a call becomes is decided once, by
+``linearmax_plan``; ``fastmax_hack``, ``fastmax_hack_grouped`` and the nodes below only read its record.
 """
+import functools
 import os
+from typing import NamedTuple
 
 import torch
 
 from .. import ops
 from .fastmax import MAX_HEADS_PER_LAUNCH, _KERNEL_DTYPES, fastattention_einops
 
+# A/B switches, read once: 0 runs linearmax with gradients as two autograd nodes instead of one / hands the block's K to the
+# prologue per query head instead of per key head (tests use the routes behind them as references)
+FUSED_TRAINING = os.environ.get("FASTMAX_LINEARMAX_FUSED_TRAIN", "1") != "0"
+GROUPED_K = os.environ.get("FASTMAX_GROUPED_K", "1") != "0"
+
+
+class LinearmaxPlan(NamedTuple):
+    operator: str      # "fused_forward" (one pass over q, k, v, no autograd node), "one_node" (_LinearmaxP1), "two_node" (two
+    #                    _NormalizeQK nodes + fastattention_einops), "unmasked" (two _NormalizeQK nodes + _UnmaskedNk)
+    prologue: str      # where q, k are normalised: "in_scan" (by the scan kernels while they stage their tiles) or "cast" (the
+    #                    kernels of fastmax_normalize.hip, in the input dtype)
+    prologue_bwd: str  # the sides whose prologue backward the scan kernels finish themselves: "both", "q" (grouped heads: the
+    #                    group's dk' are summed by the prologue's own backward pass) or "none" (off the one-node route)
+    k_layout: str      # "per_head", or K at its G key heads: "group_copies" (the prologue's store writes the G * rep normalised
+    #                    copies) / "group_views" (q, v are (B*G, rep, N, D), K is viewed the same way: nothing is copied)
+    slices: int        # batch slices the call is cut into (heads are independent; a launch takes 65535 of them)
+
+
+def linearmax_plan(dtype, B, H, Nq, Nk, D, p=1, mask=True, needs_grad=False, rep=1, views=False, train_supported=None):
+    """The one decision "which nodes and kernels run for this linearmax call", from plain data (no tensor is touched).
+    dtype: of q (anything but bf16 / fp16 computes in fp32); B, H: batch and heads of q AS LAUNCHED ((B*G, rep) beside group
+    views); needs_grad: grad mode is on and one of q, k, v asks for a gradient; rep: query heads per key head when K arrives at
+    its G groups (fastmax_hack_grouped: the training route, masked, whatever needs_grad says), else 1; views: q, v arrive as
+    (B*G, rep, N, D) group views; train_supported: fastmax_hip_linearmax_train_supported's answer (host arithmetic) -- None asks
+    the library, and only where the answer is needed.  Where the inputs live is not an argument: CPU tensors are moved to the
+    device and take the same route.  A plan the library then rejects raises (_lib.check).  Launch-bound calls pay for every host
+    instruction, so the answer is kept per argument tuple; the two things it reads besides its arguments are part of that tuple."""
+    return _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, FUSED_TRAINING, ops._force_path)
+
+
+@functools.lru_cache(maxsize=4096)
+def _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, fused_training, forced_path):
+    """linearmax_plan's rules (forced_path: the kernel family ops.set_forced_path forces, which the library's answer reads)"""
+    if D > ops.MAX_HEAD_SIZE:
+        raise NotImplementedError(f"head size {D} > {ops.MAX_HEAD_SIZE} is not supported by the HIP kernels")
+    kdt = dtype if dtype in _KERNEL_DTYPES else torch.float32
+    k_layout = "per_head" if rep == 1 else ("group_views" if views else "group_copies")
+    slices = 1
+    if rep == 1 and B * H > MAX_HEADS_PER_LAUNCH and B > 1:
+        step = max(1, MAX_HEADS_PER_LAUNCH // H)
+        slices, B = -(-B // step), step
+    # the scan kernels with the prologue inside: first order, masked, D <= 128 in whole 16-byte pieces (what the library's
+    # linearmax_fwd_check comes to once ops._prep has aligned the operands)
+    in_scan = mask and p == 1 and D <= 128 and (D * kdt.itemsize) % 16 == 0 and B * H <= MAX_HEADS_PER_LAUNCH
+    if in_scan and rep == 1 and not needs_grad:
+        return LinearmaxPlan("fused_forward", "in_scan", "none", k_layout, slices)
+    if in_scan and fused_training and k_layout != "group_copies":
+        if ops.linearmax_train_supported(kdt, B, H, Nq, D) if train_supported is None else train_supported:
+            return LinearmaxPlan("one_node", "in_scan", "both" if rep == 1 else "q", k_layout, slices)
+    return LinearmaxPlan("two_node" if mask else "unmasked", "cast", "none", k_layout, slices)
+
 
 class _NormalizeQK(torch.autograd.Function):
     """y = (x - mean_D x) / max_n ||x_n - mean_D x_n||   (fastmax_hack.py:38-43), in x's dtype; forward and backward
-    in libfastmax_hip.so (fastmax_normalize.hip).  Head sizes that are not a whole number of 16-byte pieces take the
-    float32 kernel and the tensor-op backward below."""
+    in libfastmax_hip.so (fastmax_normalize.hip): the plan's "cast" prologue."""
 
     @staticmethod
     def forward(ctx, x, rep=1, view=False):
@@ -26,44 +78,15 @@ class _NormalizeQK(torch.autograd.Function):
         copies (B, G*rep, N, D) written by the prologue's store, or with ``view`` as a stride-0 view (B*G, rep, N, D) of
         the G normalised heads (nothing is copied; the attention kernels' strides do the group indexing).  Either way the
         gradient arrives per query head and the backward pass sums a group while it reads."""
-        r = ops.normalize_cast(x, 1 if view else rep)
+        y, inv = ops.normalize_cast(x, 1 if view else rep)
+        ctx.save_for_backward(x, inv)
         ctx.rep = rep
-        if r is not None:
-            y, inv = r
-            ctx.save_for_backward(x, inv)
-            ctx.fused = True
-            if view and rep > 1:
-                B, G, N, D = x.shape
-                return y.view(B * G, 1, N, D).expand(B * G, rep, N, D)
-            return y
-        if rep != 1:
-            raise NotImplementedError("grouped normalisation needs a head size that is a whole number of 16-byte pieces")
-        y, inv = ops.normalize(x)
-        ctx.save_for_backward(y, inv)
-        ctx.in_dtype = x.dtype
-        ctx.fused = False
-        return y.to(x.dtype)
+        return _group_view(y, rep) if view else y
 
     @staticmethod
     def backward(ctx, gy):
-        if ctx.fused:
-            x, inv = ctx.saved_tensors
-            return ops.normalize_backward(x, gy, inv, ctx.rep), None, None
-        y, inv = ctx.saved_tensors                     # y = xc / M, inv = 1 / M
-        gy = gy.float()
-        gxc = gy * inv[..., None, None]
-        # M = max_n ||xc_n|| is attained at token n*: dM/dxc_{n*} = xc_{n*}/M = y_{n*};  dL/dM = -sum(gy*y)/M
-        dLdM = -(gy * y).sum(dim=(2, 3)) * inv                                    # (B,H)
-        nstar = (y * y).sum(-1).argmax(dim=2)                                      # (B,H)
-        ystar = torch.gather(y, 2, nstar[..., None, None].expand(-1, -1, 1, y.shape[-1]))
-        gxc.scatter_add_(2, nstar[..., None, None].expand(-1, -1, 1, y.shape[-1]), dLdM[..., None, None] * ystar)
-        gx = gxc - gxc.mean(-1, keepdim=True)
-        return gx.to(ctx.in_dtype), None, None
-
-
-FUSED_TRAINING = os.environ.get("FASTMAX_LINEARMAX_FUSED_TRAIN", "1") != "0"
-# the prologue's backward inside the scan kernels: 0 off, 1 the k side (dK/dV kernel), 3 both sides (default)
-FUSED_PROLOGUE_BWD = int(os.environ.get("FASTMAX_LINEARMAX_FUSED_PROLOGUE_BWD", "3"))
+        x, inv = ctx.saved_tensors
+        return ops.normalize_backward(x, gy, inv, ctx.rep), None, None
 
 
 class _LinearmaxP1(torch.autograd.Function):
@@ -75,86 +98,67 @@ class _LinearmaxP1(torch.autograd.Function):
     statistics from the same rows, and the prologue backward sums the group's gradients while it reads them."""
 
     @staticmethod
-    def forward(ctx, q, k, v, rep):
+    def forward(ctx, q, k, v, rep, prologue_bwd):
         q, k, v = (ops._prep(t, t.device) for t in (q, k, v))
-        kv = k
-        if rep > 1:
-            B, G, N, D = k.shape
-            kv = k.view(B * G, 1, N, D).expand(B * G, rep, N, D)
-        r = ops.linearmax_forward_fused(q, kv, v, train=True)
-        if r is None:
-            raise NotImplementedError("fused linearmax training route does not cover this problem")
-        o, g, inv_q, inv_k, states, nstar = r
+        o, g, inv_q, inv_k, states, nstar = ops.linearmax_forward_fused(q, _group_view(k, rep), v, train=True)
         ctx.save_for_backward(q, k, v, o, g, inv_q, inv_k)
-        ctx.states, ctx.rep = states, rep
-        ctx.nstar = nstar if FUSED_PROLOGUE_BWD else None
+        ctx.states, ctx.nstar, ctx.rep = states, nstar, rep
+        ctx.fuse = {"both": 3, "q": 2}[prologue_bwd]          # the C entry point's flags: bit 1 the dQ kernel, bit 0 the dK/dV kernel
         return o
 
     @staticmethod
     def backward(ctx, go):
         q, k, v, o, g, inv_q, inv_k = ctx.saved_tensors
         rep = ctx.rep
-        kv = k
-        if rep > 1:
-            B, G, N, D = k.shape
-            kv = k.view(B * G, 1, N, D).expand(B * G, rep, N, D)
         go = ops._prep(go.to(q.dtype), q.device)
-        # the scan kernels apply the prologue's backward to their own tiles: both sides, or with grouped-query heads the q side
-        # only (the group's dk' are summed by the prologue's backward pass below)
-        fuse = 0 if ctx.nstar is None else (FUSED_PROLOGUE_BWD if rep == 1 else (FUSED_PROLOGUE_BWD & 2))
-        dqn, dkn, dv = ops.linearmax_backward(q, kv, v, o, g, go, inv_q, inv_k, ctx.states, nstar=ctx.nstar, fuse=fuse)
+        # dq leaves the dQ kernel as the gradient wrt the raw q; so does dk unless the group's dk' still have to be summed
+        dq, dk, dv = ops.linearmax_backward(q, _group_view(k, rep), v, o, g, go, inv_q, inv_k, ctx.states, nstar=ctx.nstar,
+                                            fuse=ctx.fuse)
         ctx.states = ctx.nstar = None
-        dq = dqn if fuse & 2 else ops.normalize_backward(q, dqn, inv_q.view(q.shape[0], q.shape[1]), 1)
-        if fuse & 1:
-            dk = dkn
-        elif rep > 1:
+        if not ctx.fuse & 1:
             B, G, N, D = k.shape
             inv_g = inv_k.view(B * G, rep)[:, 0].contiguous().view(B, G)
-            dk = ops.normalize_backward(k, dkn.view(B, G * rep, N, D), inv_g, rep)
-        else:
-            dk = ops.normalize_backward(k, dkn, inv_k.view(k.shape[0], k.shape[1]), 1)
-        return dq, dk, dv, None
+            dk = ops.normalize_backward(k, dk.view(B, G * rep, N, D), inv_g, rep)
+        return dq, dk, dv, None, None
 
 
-def _fused_training_ok(q, k, v, rep=1):
-    """would _LinearmaxP1 serve these tensors?  (device tensors of one kernel dtype, whole 16-byte pieces per row)"""
-    if not FUSED_TRAINING or q.dtype not in _KERNEL_DTYPES or q.device.type != "cuda":
-        return False
-    D = q.shape[-1]
-    if (D * q.element_size()) % 16 or D > 128 or q.shape[0] * q.shape[1] > MAX_HEADS_PER_LAUNCH:
-        return False
-    prob = ops._problem(q, q, q.dtype, q.dtype, 1, True, 1.0, 0.0)
-    import ctypes
-    from .. import _lib
-    return bool(_lib.lib().fastmax_hip_linearmax_train_supported(ctypes.byref(prob)))
+def _group_view(k, rep):
+    """k (B, G, N, D) as the stride-0 view (B*G, rep, N, D) the kernels read beside grouped queries"""
+    if rep == 1:
+        return k
+    B, G, N, D = k.shape
+    return k.view(B * G, 1, N, D).expand(B * G, rep, N, D)
 
 
 def fastmax_hack(q, k, v, p=1, mask=True):
     """linearmax (reference: fastmax_hack.py:5)."""
-    if q.shape[0] * q.shape[1] > MAX_HEADS_PER_LAUNCH and q.shape[0] > 1:
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
+    B, H, Nq, D = q.shape
+    return linearmax(q, k, v, _plan(q.dtype, B, H, Nq, k.shape[2], D, p, mask, needs_grad, 1, False, None, FUSED_TRAINING,
+                                    ops._force_path), p, mask)
+
+
+def linearmax(q, k, v, plan, p=1, mask=True):
+    """fastmax_hack for a caller that holds the call's linearmax_plan record (k_layout "per_head")"""
+    if plan.slices > 1:
         step = max(1, MAX_HEADS_PER_LAUNCH // q.shape[1])          # heads are independent: run the batch in slices
-        return torch.cat([fastmax_hack(q[i:i + step], k[i:i + step], v[i:i + step], p=p, mask=mask)
+        return torch.cat([linearmax(q[i:i + step], k[i:i + step], v[i:i + step], plan._replace(slices=1), p, mask)
                           for i in range(0, q.shape[0], step)], dim=0)
     dev = ops._device() if q.device.type != "cuda" else q.device
     home, in_dtype = q.device, q.dtype
     kdt = in_dtype if in_dtype in _KERNEL_DTYPES else torch.float32
-    qd, kd = (ops._prep(t.to(kdt), dev) for t in (q, k))
-    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
-    if mask and p == 1 and not needs_grad:
+    qd, kd, vd = (ops._prep(t.to(kdt), dev) for t in (q, k, v))
+    if plan.operator == "fused_forward":
         # inference / forward-only: prologue fused into the matrix-core kernel, one pass over Q, K, V
-        o = ops.linearmax_forward_fused(qd, kd, ops._prep(v.to(kdt), dev))
-        if o is not None:
-            return o.to(device=home, dtype=in_dtype)
-    # training (or shapes the fused kernel does not cover): prologue and attention as separate autograd nodes,
-    # both in libfastmax_hip.so; 16-bit inputs keep their dtype between the two, like the reference
-    vd = ops._prep(v.to(kdt), dev)
-    if mask and p == 1 and needs_grad and _fused_training_ok(qd, kd, vd):
-        return _LinearmaxP1.apply(qd, kd, vd, 1).to(device=home, dtype=in_dtype)
-    qn, kn = _NormalizeQK.apply(qd, 1), _NormalizeQK.apply(kd, 1)
-    if not mask:
+        return ops.linearmax_forward_fused(qd, kd, vd).to(device=home, dtype=in_dtype)
+    if plan.operator == "one_node":
+        return _LinearmaxP1.apply(qd, kd, vd, 1, plan.prologue_bwd).to(device=home, dtype=in_dtype)
+    # prologue and attention as separate autograd nodes; 16-bit inputs keep their dtype between the two, like the reference
+    qn, kn = _NormalizeQK.apply(qd), _NormalizeQK.apply(kd)
+    if plan.operator == "unmasked":
         # fastmax_hack.py:6-33: first order whatever p is; constant term N_k; result float32 for
         # low-precision inputs (float32 ones at line 21), float64 stays float64
-        o = _unmasked_first_order(qn, kn, vd, float(k.shape[2]))
+        o = _UnmaskedNk.apply(qn, kn, vd, float(k.shape[2]))
         out_dt = torch.float64 if in_dtype == torch.float64 else torch.float32
     else:
         o = fastattention_einops.apply(qn, kn, vd, True, 1, True, p, 0.0, False)
@@ -162,28 +166,22 @@ def fastmax_hack(q, k, v, p=1, mask=True):
     return o.to(device=home, dtype=out_dt)
 
 
-def fastmax_hack_grouped(q, k_groups, v, rep, p=1):
+def fastmax_hack_grouped(q, k_groups, v, rep, p=1, plan=None):
     """Masked linearmax for grouped-query attention on the training route: k_groups (B,G,N,D) with H = G * rep query heads.
     Same values as fastmax_hack(q, expand(k_groups), v, p, mask=True): the max-norm statistics of identical head copies
     are identical, so the prologue runs once per key head (the reference expands first, model.py:404-411, and normalises
-    every copy, fastmax_hack.py:38-43).  Two layouts:
+    every copy, fastmax_hack.py:38-43).  Two layouts (the plan's k_layout; without ``plan`` it is read off q's shape):
       q, v (B,H,N,D) with v already repeated         -> the prologue's store writes the H normalised copies of K
       q, v (B*G, rep, N, D) (v a stride-0 group view) -> K is normalised at its G heads and handed on as a stride-0 view too:
                                                         no per-query-head copy of K or V exists anywhere"""
-    views = q.shape[0] == k_groups.shape[0] * k_groups.shape[1] and q.shape[1] == rep and rep > 1
-    if views and p == 1 and _fused_training_ok(q, k_groups, v, rep):
-        return _LinearmaxP1.apply(q, k_groups, v, rep).to(q.dtype)
-    qn = _NormalizeQK.apply(q, 1)
-    kn = _NormalizeQK.apply(k_groups, rep, views)
-    o = fastattention_einops.apply(qn, kn, v, True, 1, True, p, 0.0, False)
-    return o.to(q.dtype)
-
-
-def grouped_route_supported(device, dtype, head_size, heads) -> bool:
-    """can fastmax_hack_grouped serve (B * H = heads) heads of this dtype / head size?  (FASTMAX_GROUPED_K=0 turns it off)"""
-    return (os.environ.get("FASTMAX_GROUPED_K", "1") != "0" and device.type == "cuda" and
-            dtype in (torch.bfloat16, torch.float16, torch.float32) and
-            (head_size * torch.empty((), dtype=dtype).element_size()) % 16 == 0 and heads <= MAX_HEADS_PER_LAUNCH)
+    if plan is None:
+        views = rep > 1 and q.shape[:2] == (k_groups.shape[0] * k_groups.shape[1], rep)
+        plan = linearmax_plan(q.dtype, *q.shape[:3], k_groups.shape[2], q.shape[3], p, True, True, rep, views)
+    if plan.operator == "one_node":
+        return _LinearmaxP1.apply(q, k_groups, v, rep, plan.prologue_bwd).to(q.dtype)
+    qn = _NormalizeQK.apply(q)
+    kn = _NormalizeQK.apply(k_groups, rep, plan.k_layout == "group_views")
+    return fastattention_einops.apply(qn, kn, v, True, 1, True, p, 0.0, False).to(q.dtype)
 
 
 class _UnmaskedNk(torch.autograd.Function):
@@ -203,7 +201,3 @@ class _UnmaskedNk(torch.autograd.Function):
         dq, dk, dv = ops.backward(ops._prep(q, q.device), ops._prep(k, q.device), ops._prep(v, q.device), o, g,
                                   ops._prep(go.float(), q.device), 1, False, 1.0)
         return dq, dk, dv, None
-
-
-def _unmasked_first_order(qn, kn, v, g0):
-    return _UnmaskedNk.apply(qn, kn, v, g0)

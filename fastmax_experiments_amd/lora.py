@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import _DT, _stream, rope_qkv_backward
+from .ops import KV_LAYOUTS, _DT, _stream, group_views, rope_qkv_backward
 
 NF4_CODE = torch.tensor([-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
                          -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
@@ -647,8 +647,8 @@ class _QLoRAGemmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, A, ebt, base, plan, rope, drop_p):
         """rope = (cos32, sin32, B, T, G, qpk, hs, rope_n, tables16, expand): the product is an attention sub-layer's qkv
-        projection and leaves the kernel as (q, k, v) -- de-interleaved and rotated, in the layout of ops.RopeQKVSplit's
-        `expand` mode 0 (k, v at their G heads; also mode 1 when qpk == 1), 3 or 4 (stride-0 group views) -- instead of y"""
+        projection and leaves the kernel as (q, k, v) -- de-interleaved and rotated, in one of the ops.KV_LAYOUTS that copy
+        nothing: KV_GROUPS (k, v at their G heads), KV_VIEWS or K_GROUPS_V_VIEWS (stride-0 group views) -- instead of y"""
         N, K = base.out_features, base.in_features
         R, RP = A.shape[0], ebt.shape[0]
         bias = _bias32(base)
@@ -666,11 +666,8 @@ class _QLoRAGemmFn(torch.autograd.Function):
         ctx.base, ctx.rope, ctx.rank, ctx.a_dtype = base, rope, R, A.dtype
         if rope is not None:
             cos32, sin32, B, T, G, qpk, hs, rope_n, tables16, expand = rope
-            q, k, v = hip_gemm_rope(x2, _weight_operand(base, False), bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n, tables16)
-            if expand in (3, 4):                                      # ops.RopeQKVSplit's group views: nothing is copied
-                kv = lambda t: t.view(B * G, 1, T, hs).expand(B * G, qpk, T, hs)
-                return q.view(B * G, qpk, T, hs), (kv(k) if expand == 3 else k), kv(v)
-            return q, k, v
+            return group_views(*hip_gemm_rope(x2, _weight_operand(base, False), bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n,
+                                              tables16), KV_LAYOUTS[expand])
         if plan.route == "gemm_fused":
             return hip_gemm(x2, base.weight.data, scales_of(base), bias, ea, eb, N)
         return hip_gemm(x2, _weight_operand(base, False), None, bias, ea, eb, N)
@@ -681,11 +678,10 @@ class _QLoRAGemmFn(torch.autograd.Function):
         N, K = ctx.base.out_features, ctx.base.in_features
         if ctx.rope is not None:
             # gradients of q (B, G qpk, T, hs), k, v (B, G, T, hs): inverse rotation + re-interleave in one pass, then as before.
-            # Modes 3 / 4: the gradients of the stride-0 views arrive dense, one per query head, and the pass sums a group
-            # while it reads them -- exactly ops.RopeQKVSplit.backward
+            # The gradients of stride-0 views arrive dense, one per query head, and the pass sums a group while it reads them --
+            # exactly ops.RopeQKVSplit.backward
             cos32, sin32, B, T, G, qpk, hs, rope_n, _, expand = ctx.rope
-            dy = rope_qkv_backward(dy, more[0], more[1], cos32, sin32, B, T, G, qpk, hs, rope_n,
-                                   {0: 0, 1: 0, 3: 1, 4: 2}[expand]).view(B * T, N)
+            dy = rope_qkv_backward(dy, more[0], more[1], cos32, sin32, B, T, G, qpk, hs, rope_n, KV_LAYOUTS[expand].bwd).view(B * T, N)
         dy = dy.contiguous()
         dx = dA = d_ebt = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:

@@ -6,6 +6,7 @@ the hot path runs in libfastmax_hip.so.
 import ctypes
 import os
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -60,20 +61,17 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _call(name, dev, args, ws=None, tail=(), not_covered=()):
+def _call(name, dev, args, ws=None, tail=()):
     """``name(*args[, workspace, its size], *tail, stream)`` on ``dev``'s current stream, with ``ws`` bytes of fresh workspace
-    when a size is given.  -> (True, the workspace tensor or None), or (False, None) when the library answers with one of the
-    codes in ``not_covered``; any other code but 0 raises."""
+    when a size is given.  -> the workspace tensor or None; any code but 0 raises."""
     wsb, wsargs = None, ()
     if ws is not None:
         wsb, wsp = _ws(ws, dev)
         wsargs = (wsp, ws)
     with torch.cuda.device(dev):
         rc = getattr(_lib.lib(), name)(*args, *wsargs, *tail, _stream(dev))
-    if rc in not_covered:
-        return False, None
     _lib.check(rc, name)
-    return True, wsb
+    return wsb
 
 
 def _problem(q, k, in_dt, out_dt, p, causal, nt, g0):
@@ -131,8 +129,8 @@ def forward(q, k, v, p, causal, nt, g0, out_dtype, need_g=True, keep_states=Fals
     prob = _problem(q, k, q.dtype, out_dtype, p, causal, nt, g0)
     o = torch.empty((B, H, Nq, D), dtype=out_dtype, device=dev)
     g = torch.empty((B, H, Nq), dtype=torch.float32, device=dev) if need_g else None
-    _, wsb = _call("fastmax_hip_forward", dev, (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), _ptr(g)),
-                   ws=L.fastmax_hip_forward_workspace(ctypes.byref(prob)))
+    wsb = _call("fastmax_hip_forward", dev, (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), _ptr(g)),
+                ws=L.fastmax_hip_forward_workspace(ctypes.byref(prob)))
     return (o, g, _kept_states(prob, q, k, v, o, wsb)) if keep_states else (o, g)
 
 
@@ -172,8 +170,7 @@ def normalize(x):
 
 
 def normalize_cast(x, rep=1):
-    """linearmax prologue written in x's own dtype (training route): -> (y like x, contiguous; inv_norm (B,H) float32),
-    or None when the head size is not a whole number of 16-byte pieces (caller falls back to normalize()).
+    """linearmax prologue written in x's own dtype (training route): -> (y like x, contiguous; inv_norm (B,H) float32).
     rep > 1 (grouped-query attention): x holds the G key heads, y the G * rep query-head copies (B, G * rep, N, D)."""
     L = _lib.lib()
     dev = x.device
@@ -184,10 +181,10 @@ def normalize_cast(x, rep=1):
     ws = max(L.fastmax_hip_normalize_workspace(B, H), 4 * B * H * ((N + 255) // 256))
     args = (*_qkv(x), _DT[x.dtype], y.data_ptr(), inv.data_ptr(), B, H)
     if rep == 1:
-        ok, _ = _call("fastmax_hip_normalize_cast", dev, args + (N, D), ws=ws, not_covered=(_lib.E_BAD_SHAPE,))
+        _call("fastmax_hip_normalize_cast", dev, args + (N, D), ws=ws)
     else:
-        ok, _ = _call("fastmax_hip_normalize_cast_expand", dev, args + (rep, N, D), ws=ws, not_covered=(_lib.E_BAD_SHAPE,))
-    return (y, inv) if ok else None
+        _call("fastmax_hip_normalize_cast_expand", dev, args + (rep, N, D), ws=ws)
+    return y, inv
 
 
 def normalize_backward(x, gy, inv, rep=1):
@@ -230,55 +227,51 @@ def normalize_stats_pair(q, k):
     return qi, ki
 
 
+def linearmax_train_supported(dtype, B, H, N, D) -> bool:
+    """the library's host-side answer (nothing is launched, no device is needed): does the linear-time backward behind
+    linearmax_forward_fused(train=True) cover this masked first-order problem?"""
+    prob = _lib.Problem(B, H, N, N, D, _DT[dtype], _DT[dtype], 1, 1, 1.0, 0.5, 0.0, _force_path)
+    return bool(_lib.lib().fastmax_hip_linearmax_train_supported(ctypes.byref(prob)))
+
+
 def linearmax_forward_fused(q, k, v, return_stats=False, train=False):
-    """Masked first-order linearmax with the prologue fused into the matrix-core kernel.
-    Returns None when the shape / dtype is not covered (the caller then uses the unfused route).
+    """Masked first-order linearmax with the prologue fused into the matrix-core kernel; which calls it covers is
+    fastmax_hack.linearmax_plan's to say (a call it does not cover raises).
     ``train``: -> (o, g, inv_q, inv_k, states, k_nstar) for linearmax_backward (states = the forward's workspace when it holds
     the sequence split's prefix states, else None; nstar (2, B*H) = per head the row of q / of k that attains the max-norm)."""
     L = _lib.lib()
     dev = q.device
     B, H, N, D = q.shape
-    if q.dtype not in _DT or D > 128:
-        return None
     prob = _problem(q, k, q.dtype, q.dtype, 1, True, 1.0, 0.0)
-    if B * H > 65535:
-        return None
-    if train and not L.fastmax_hip_linearmax_train_supported(ctypes.byref(prob)):
-        return None
     # statistics + scan in one entry point (with the sequence split the statistics ride on the split's state pass)
     stats = torch.empty((2, B * H), dtype=torch.float32, device=dev)
     nstar = torch.full((2, B * H), -1, dtype=torch.int32, device=dev) if train else None
     o = torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
     g = torch.empty((B, H, N), dtype=torch.float32, device=dev) if train else None
     nq, nk = (nstar[0].data_ptr(), nstar[1].data_ptr()) if train else (None, None)
-    ok, wsb = _call("fastmax_hip_linearmax_forward_auto", dev,
-                    (ctypes.byref(prob), *_qkv(q, k, v), stats[0].data_ptr(), stats[1].data_ptr(), nq, nk, o.data_ptr(), _ptr(g)),
-                    ws=L.fastmax_hip_linearmax_forward_auto_workspace(ctypes.byref(prob)),
-                    not_covered=(_lib.E_BAD_SHAPE, _lib.E_ALIGNMENT))          # not covered by the fused kernel
-    if not ok:
-        return None
+    wsb = _call("fastmax_hip_linearmax_forward_auto", dev,
+                (ctypes.byref(prob), *_qkv(q, k, v), stats[0].data_ptr(), stats[1].data_ptr(), nq, nk, o.data_ptr(), _ptr(g)),
+                ws=L.fastmax_hip_linearmax_forward_auto_workspace(ctypes.byref(prob)))
     if train:
         return o, g, stats[0], stats[1], _kept_states(prob, q, k, v, o, wsb), nstar
     return (o, stats[0], stats[1]) if return_stats else o
 
 
-def linearmax_backward(q, k, v, o, g, grad_o, inv_q, inv_k, states=None, nstar=None, fuse=0):
-    """backward of linearmax_forward_fused(train=True): q, k RAW, the scans apply the prologue while staging.
-    -> (dq_n, dk_n, dv): gradients wrt the NORMALISED q, k (finish with normalize_backward) and wrt v.  With ``nstar`` (from
-    the forward) and ``fuse`` bit 0 the dK/dV kernel applies the prologue's backward itself and dk_n is the gradient wrt the raw
-    k; bit 1 (with bit 0): the dQ kernel does the same for dq_n."""
+def linearmax_backward(q, k, v, o, g, grad_o, inv_q, inv_k, states, nstar, fuse):
+    """backward of linearmax_forward_fused(train=True): q, k RAW, the scans apply the prologue while staging; states, nstar: from
+    that forward.  -> (dq, dk, dv).  ``fuse`` bit 1: the dQ kernel applies the prologue's backward itself and dq is the gradient
+    wrt the raw q; bit 0: the dK/dV kernel does the same for dk -- without it dk is the gradient wrt the NORMALISED k (finish
+    with normalize_backward)."""
     L = _lib.lib()
     dev = q.device
     prob = _problem(q, k, q.dtype, o.dtype, 1, True, 1.0, 0.0)
     dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
     dk = torch.empty(q.shape, dtype=q.dtype, device=dev)
     dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
-    nq, nk = (None, None) if nstar is None else (nstar[0].data_ptr(), nstar[1].data_ptr())
     _call("fastmax_hip_linearmax_backward", dev,
-          (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), g.data_ptr(), *_qkv(grad_o), inv_q.data_ptr(), inv_k.data_ptr(), nq, nk,
-           dq.data_ptr(), dk.data_ptr(), dv.data_ptr()),
-          ws=L.fastmax_hip_backward_workspace(ctypes.byref(prob)),
-          tail=(_ptr(states), 0 if states is None else states.numel(), 0 if nstar is None else fuse))
+          (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), g.data_ptr(), *_qkv(grad_o), inv_q.data_ptr(), inv_k.data_ptr(),
+           nstar[0].data_ptr(), nstar[1].data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()),
+          ws=L.fastmax_hip_backward_workspace(ctypes.byref(prob)), tail=(_ptr(states), 0 if states is None else states.numel(), fuse))
     return dq, dk, dv
 
 
@@ -360,21 +353,32 @@ def rope_qkv_backward(gq, gk, gv, cos32, sin32, B, T, G, qpk, hs, rope_n, kern_e
     return gqkv
 
 
+class KVLayout(NamedTuple):
+    """what the key / value heads look like to the attention that follows the QKV split (H = G * q_per_kv query heads)"""
+    k: str            # "groups" (B,G,T,hs), "copies" (B,H,T,hs) written by the kernel, or "views": nothing is copied, q comes back
+    v: str            # as (B*G, q_per_kv, T, hs) beside views of the G-head tensors with head stride 0, shaped the same -- (batch,
+    #                   group) becomes the batch axis and the kernels' own strides do the group indexing
+    fwd: int          # the split kernel's `expand`: what it materialises (0 nothing, 1 k and v, 2 v)
+    bwd: int          # the gradient kernel's `expand`: what arrives per query head and is summed over its group while it is read
+    #                   (1 k and v, 2 v) -- the dense gradients of views are laid out (B*G, qpk, T, hs) = (B, H, T, hs), like copies'
+
+
+KV_GROUPS, KV_COPIES, K_GROUPS_V_COPIES, KV_VIEWS, K_GROUPS_V_VIEWS = range(5)
+KV_LAYOUTS = {KV_GROUPS: KVLayout("groups", "groups", 0, 0),
+              KV_COPIES: KVLayout("copies", "copies", 1, 1),                 # the reference's expand + reshape, model.py:404-420
+              KV_VIEWS: KVLayout("views", "views", 0, 1),
+              # K left at its groups for the linearmax prologue, which normalises per key head
+              K_GROUPS_V_COPIES: KVLayout("groups", "copies", 2, 2), K_GROUPS_V_VIEWS: KVLayout("groups", "views", 0, 2)}
+
+
 class RopeQKVSplit(torch.autograd.Function):
     """qkv (B,T,G,q_per_kv+2,hs) -> q (B,H,T,hs), k, v (B,H,T,hs): de-interleave + RoPE + GQA expand in one HIP pass
     (fastmax_rope.hip; lit_gpt/model.py:397-425), and the mirror pass for the gradient."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, rope_n_elem, expand=1):
-        """expand: what the key / value heads look like to the attention that follows (H = G * q_per_kv query heads):
-          0  k, v stay at their G heads (B,G,T,hs)
-          1  k, v COPIED for the query heads of their group (B,H,T,hs) -- the reference's expand + reshape, model.py:404-420
-          2  k stays (B,G,T,hs), v copied
-          3  nothing is copied: q comes back as (B*G, q_per_kv, T, hs) and k, v as views of the G-head tensors with head
-             stride 0, shaped the same -- (batch, group) becomes the batch axis and the kernels' own strides do the
-             group indexing, so every query head of a group reads the same K, V rows; the gradients then arrive per
-             query head and the backward pass sums them over the group while it reads them
-          4  k stays (B,G,T,hs) (for the linearmax prologue, which normalises per key head), q and v as in 3"""
+    def forward(ctx, qkv, cos, sin, rope_n_elem, expand=KV_COPIES):
+        """expand: one of the KV_LAYOUTS above"""
+        layout = KV_LAYOUTS[int(expand)]
         B, T, G, total, hs = qkv.shape
         qpk = total - 2
         qkv = qkv.contiguous()
@@ -382,28 +386,28 @@ class RopeQKVSplit(torch.autograd.Function):
         # dtype before the sum -- the kernel reproduces those roundings (tables travel as exact float32 copies)
         tables16 = 16 if (cos.dtype == qkv.dtype and qkv.dtype in (torch.bfloat16, torch.float16)) else 0
         cos, sin = _rope_tables_f32(cos, sin, T, rope_n_elem)
-        k_copies, v_copies = expand == 1, expand in (1, 2)
-        kern_expand = 1 if (k_copies and v_copies) else (2 if v_copies else 0)          # what the forward pass materialises
         q = torch.empty((B, G * qpk, T, hs), dtype=qkv.dtype, device=qkv.device)
-        k = torch.empty((B, G * qpk if k_copies else G, T, hs), dtype=qkv.dtype, device=qkv.device)
-        v = torch.empty((B, G * qpk if v_copies else G, T, hs), dtype=qkv.dtype, device=qkv.device)
+        k = torch.empty((B, G * qpk if layout.k == "copies" else G, T, hs), dtype=qkv.dtype, device=qkv.device)
+        v = torch.empty((B, G * qpk if layout.v == "copies" else G, T, hs), dtype=qkv.dtype, device=qkv.device)
         _call("fastmax_hip_rope_qkv_split", qkv.device,
               (qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), B, T, G, qpk, hs, rope_n_elem,
-               kern_expand | tables16, _DT[qkv.dtype]))
+               layout.fwd | tables16, _DT[qkv.dtype]))
         ctx.save_for_backward(cos, sin)
-        ctx.dims = (B, T, G, qpk, hs, rope_n_elem, int(expand))
-        if expand in (3, 4):
-            def group_view(t):
-                return t.view(B * G, 1, T, hs).expand(B * G, qpk, T, hs)
-            return q.view(B * G, qpk, T, hs), (group_view(k) if expand == 3 else k), group_view(v)
-        return q, k, v
+        ctx.dims = (B, T, G, qpk, hs, rope_n_elem, layout.bwd)
+        return group_views(q, k, v, layout)
 
     @staticmethod
     def backward(ctx, gq, gk, gv):
         cos, sin = ctx.saved_tensors
-        B, T, G, qpk, hs, rope_n_elem, expand = ctx.dims
-        # modes 3 / 4: gradients of the stride-0 views arrive dense, one per query head, laid out (B*G, qpk, T, hs) =
-        # (B, H, T, hs): exactly what the kernel's group-summing read expects for copied heads
-        kern_expand = {0: 0, 1: 1, 2: 2, 3: 1, 4: 2}[expand]
-        gqkv = rope_qkv_backward(gq, gk, gv, cos, sin, B, T, G, qpk, hs, rope_n_elem, kern_expand)
-        return gqkv, None, None, None, None
+        return rope_qkv_backward(gq, gk, gv, cos, sin, *ctx.dims), None, None, None, None
+
+
+def group_views(q, k, v, layout):
+    """q (B,H,T,hs), k, v (B,G,T,hs) as ``layout`` hands them on: with "views", q as (B*G, qpk, T, hs) beside stride-0 views"""
+    if layout.v != "views":
+        return q, k, v
+    (B, G, T, hs), qpk = v.shape, q.shape[1] // v.shape[1]
+
+    def view(t):
+        return t.view(B * G, 1, T, hs).expand(B * G, qpk, T, hs)
+    return q.view(B * G, qpk, T, hs), (view(k) if layout.k == "views" else k), view(v)

@@ -251,6 +251,7 @@ def test_grouped_query_prologue_matches_expand_then_normalise(rep, T):
 def test_block_grouped_route_matches_the_expanded_route(monkeypatch):
     """CausalSelfAttention (linearmax, grouped-query heads, training): the route that keeps K at its groups through the prologue
     against the same block with that route disabled -- output and gradients"""
+    import importlib
     import fastmax_experiments_amd.attention_block as ab
     torch.manual_seed(22)
     blk = ab.CausalSelfAttention(256, 8, n_query_groups=2, attn_alg="linearmax").to(torch.bfloat16)
@@ -263,7 +264,8 @@ def test_block_grouped_route_matches_the_expanded_route(monkeypatch):
     res = []
     for grouped in (True, False):
         if not grouped:
-            monkeypatch.setattr(ab, "grouped_route_supported", lambda *a: False)
+            # the module, not the function its package exports under the same name
+            monkeypatch.setattr(importlib.import_module("fastmax_experiments_amd.attention_mechanisms.fastmax_hack"), "GROUPED_K", False)
         x = x0.clone().requires_grad_(True)
         y = blk(x, cos, sin)
         y.backward(gy)
@@ -528,7 +530,7 @@ def test_one_kernel_qkv_projection_matches_the_separate_passes(config, T, alg, t
     for one_kernel in (True, False):
         blk.gemm_rope = one_kernel
         xa = x.clone().requires_grad_(True)
-        assert blk._one_kernel_qkv(xa, None, B, T, blk.n_head // blk.n_query_groups) == one_kernel
+        assert (blk.plan(xa, None).qkv == "gemm_epilogue") == one_kernel
         y = blk(xa, cos, sin)
         y.backward(gy)
         res.append((y.detach().clone(), xa.grad.clone(), blk.attn.lora_A.grad.clone(), blk.attn.lora_B.grad.clone()))
@@ -536,3 +538,24 @@ def test_one_kernel_qkv_projection_matches_the_separate_passes(config, T, alg, t
     blk.gemm_rope = True
     for a, b in zip(*res):
         assert torch.equal(a, b)
+
+
+def _attention_parity():
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import attention_parity
+    return attention_parity
+
+
+@pytest.mark.parametrize("name", list(_attention_parity().CASES))
+def test_attention_routes_give_the_recorded_bits(name):
+    """tests/golden/attention_parity.json: digests of the output and of every gradient, recorded (tools/attention_parity.py)
+    from linearmax and the attention sub-layer as they were before the route plans existed -- every linearmax operator, both
+    grouped layouts, and the block training and under no_grad.  Every case reproduced its own digests when it was recorded:
+    the same kernels on the same operand values give the same bits"""
+    import json
+    parity = _attention_parity()
+    with open(parity.GOLDEN) as f:
+        want = json.load(f)[name]
+    assert parity.run_case(name) == want

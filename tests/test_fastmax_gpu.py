@@ -848,7 +848,7 @@ def test_grouped_linearmax_training_route_without_normalised_copies():
 @pytest.mark.parametrize("shape", [(2, 3, 300, 64), (1, 2, 1000, 128), (1, 5, 17, 16), (1, 2, 260, 40), (2, 8, 513, 32), (1, 2, 300, 256),
                                    (1, 3, 130, 192)])
 def test_linearmax_prologue_forward_backward_kernels(shape, dt, tol):
-    """_NormalizeQK (fastmax_normalize.hip; D=40 in 16-bit takes the float32 kernel + tensor-op backward) against float64
+    """_NormalizeQK (fastmax_normalize.hip; D=40 in 16-bit is not whole 16-byte pieces: element-wise loads) against float64
     autograd over the reference's own formulation (fastmax_hack.py:38-43)"""
     from fastmax_experiments_amd.attention_mechanisms.fastmax_hack import _NormalizeQK
     g = torch.Generator().manual_seed(shape[2])
