@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
-header (OPTIM_HEADER) has the table OPTIM_ABI and the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, set on
-the same handle.
+header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI and the
+NeoX block's (NEOX_HEADER) the table NEOX_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -141,6 +141,20 @@ NEXT_TOKEN_ABI = {
     "fastmax_hip_sample": (ci, [vp, i64, vp, ci, ci, ci, cf, i64, i64, vp]),
     "fastmax_hip_topk_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, vp]),
 }
+# the NeoX (pythia) block's side header (the LayerNorm pair with the three-way residual add, the ungated GELU, their backward
+# passes): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_neox_cpu.py checks each row
+# against the prototype.
+NEOX_HEADER = "fastmax_hip_neox.h"
+NEOX_ACT_GELU = 0                               # enum fastmax_neox_act
+NEOX_ABI = {
+    "fastmax_hip_layernorm_forward": (ci, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, ci, ci, cf,
+                                           ci, ci, vp]),
+    "fastmax_hip_layernorm_backward_workspace": (sz, [ci, ci, ci, ci, ci]),
+    "fastmax_hip_layernorm_backward": (ci, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, ci, ci, ci,
+                                            ci, vp, sz, vp]),
+    "fastmax_hip_act_forward": (ci, [vp, i64, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_act_backward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -154,7 +168,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

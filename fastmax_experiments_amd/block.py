@@ -24,8 +24,10 @@ from .attention_block import CONFIG_SHAPES, CausalSelfAttention
 from .lora import LoRALinear
 
 # intermediate_size of the CONFIG_SHAPES entries (lit_gpt/config.py).  Sizes only: the pythia configs name LayerNorm and
-# GptNeoxMLP there, which Block refuses; their widths serve tests and the step with RMSNorm and the gated MLP
-CONFIG_INTERMEDIATE = {"pythia-14m": 512, "tiny-llama-1.1b": 5632, "Llama-2-7b-hf": 11008, "pythia-1b": 8192, "Gemma-2b": 16384}
+# GptNeoxMLP there, which Block refuses and neox_block.NeoXBlock builds; here their widths also serve tests and the step with
+# RMSNorm and the gated MLP
+CONFIG_INTERMEDIATE = {"pythia-14m": 512, "tiny-llama-1.1b": 5632, "Llama-2-7b-hf": 11008, "pythia-1b": 8192, "Gemma-2b": 16384,
+                       "pythia-70m": 2048}
 
 _ACT = {"silu": _lib.ACT_SILU, "gelu": _lib.ACT_GELU}
 

@@ -26,15 +26,17 @@ from . import dp
 class AttentionStack(nn.Module):
     """n_layer x (x + CausalSelfAttention(x)) with QLoRA linears, then the lm-head loss of finetune/lora.py:216-219.
     ``block="full"``: n_layer whole decoder blocks (block.py: RMSNorm, attention, RMSNorm, gated MLP at the config's
-    intermediate_size, both residual adds) in place of the bare attention sub-layers."""
+    intermediate_size, both residual adds) in place of the bare attention sub-layers.  ``block="neox"``: n_layer whole
+    parallel-residual blocks (neox_block.py: the LayerNorm pair, attention, the GELU MLP, the three-way add), what the pythia
+    configs are."""
 
     def __init__(self, config: str, n_layer: int, attn_alg: str, vocab: int = 32000, r: int = 8, alpha: int = 16,
                  lora_dropout: float = 0.05, block: str = "attention"):
         """r, alpha, lora_dropout: the reference's fine-tune defaults (finetune/lora.py:40-42)"""
         super().__init__()
         from .attention_block import CONFIG_SHAPES, CausalSelfAttention
-        if block not in ("attention", "full"):
-            raise ValueError(f"block should be 'attention' or 'full', got {block!r}")
+        if block not in ("attention", "full", "neox"):
+            raise ValueError(f"block should be 'attention', 'full' or 'neox', got {block!r}")
         shape = CONFIG_SHAPES[config]
         self.n_embd = shape["n_embd"]
         self.block = block
@@ -42,14 +44,18 @@ class AttentionStack(nn.Module):
             from .block import Block
             self.blocks = nn.ModuleList(Block.from_config(config, attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout)
                                         for _ in range(n_layer))
+        elif block == "neox":
+            from .neox_block import NeoXBlock
+            self.blocks = nn.ModuleList(NeoXBlock.from_config(config, attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout)
+                                        for _ in range(n_layer))
         else:
             self.blocks = nn.ModuleList(CausalSelfAttention(attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout, **shape) for _ in range(n_layer))
         for b in self.blocks:
-            attn = b.attn if block == "full" else b
+            attn = b if block == "attention" else b.attn
             nn.init.normal_(attn.attn.lora_B, std=0.02)           # a non-zero branch, so every LoRA gradient is exercised
         g = torch.Generator().manual_seed(1234)
         self.lm_head = nn.Parameter(torch.randn(vocab, self.n_embd, generator=g) * 0.02, requires_grad=False)
-        self.rope_n_elem = (self.blocks[0].attn if block == "full" else self.blocks[0]).rope_n_elem
+        self.rope_n_elem = (self.blocks[0] if block == "attention" else self.blocks[0].attn).rope_n_elem
 
     def prepare(self, device, quantize: bool = True):
         if quantize:
@@ -57,16 +63,20 @@ class AttentionStack(nn.Module):
                 b.quantize_base()
         self.to(device)
         self.lm_head.data = self.lm_head.data.to(torch.bfloat16)
-        if self.block == "full":
+        if self.block != "attention":
             for b in self.blocks:                                 # the norms run in the activations' dtype ("bf16-true")
                 b.norm_1.to(torch.bfloat16)
-                b.norm_2.to(torch.bfloat16)
+                if b.norm_2 is not None:
+                    b.norm_2.to(torch.bfloat16)
         return self
 
     def forward(self, x, cos, sin):
         if self.block == "full":
             from .block import run_blocks
             return run_blocks(self.blocks, x, cos, sin)
+        if self.block == "neox":
+            from .neox_block import run_neox_blocks
+            return run_neox_blocks(self.blocks, x, cos, sin)
         for b in self.blocks:
             x = x + b(x, cos, sin)
         return x

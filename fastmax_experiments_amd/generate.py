@@ -6,8 +6,8 @@ token.  Here (csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, boun
     last_logits    the head over the LAST position only; the weight is read once for up to 8 rows
     Sampler        exact top-k (ties: the lowest indices are kept) and a draw from softmax(logits / temperature) as the argmax of
                    logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device
-    NextTokenHead  ``ln_f`` (the RMSNorm kernel on the B last rows) + ``lm_head`` + the sampler
-    generate       prompt -> tokens through decoder blocks on their decode state caches
+    NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler
+    generate       prompt -> tokens through decoder blocks (``Block`` or ``NeoXBlock``) on their decode state caches
 What differs from the reference: logits are float32 by default (``dtype=`` gives the reference's), and the random stream is the
 sampler's own seeded one instead of torch's generator, so a (seed, draw) pair reproduces a token on any batch.  There is no CPU
 path through the kernels; ``NextTokenHead.fused = False`` selects the tensor-op restatement for A/B runs.
@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .block import BlockStack, RMSNorm, rms_norm_forward, run_blocks
+from .neox_block import LayerNorm, NeoXBlock, NeoXStack, layer_norm_forward, run_neox_blocks
 
 _MASK64 = (1 << 64) - 1
 
@@ -121,15 +122,21 @@ def _sample_tensor_ops(logits: torch.Tensor, temperature: float, top_k) -> torch
 
 class NextTokenHead(nn.Module):
     """``ln_f`` + ``lm_head`` (the reference's names, so its state-dict keys load) + the sampler.  ``vocab_size`` rows of the
-    ``padded_vocab_size`` rows of the weight are scored; the default is all of them, which is what the reference samples over."""
+    ``padded_vocab_size`` rows of the weight are scored; the default is all of them, which is what the reference samples over.
+    ``norm_class``: "RMSNorm", or "LayerNorm" (the pythia models; state-dict keys ``ln_f.weight`` and ``ln_f.bias``)."""
 
     def __init__(self, n_embd: int, padded_vocab_size: int, vocab_size: int = None, norm_eps: float = 1e-5,
-                 add_unit_offset: bool = False) -> None:
+                 add_unit_offset: bool = False, norm_class: str = "RMSNorm") -> None:
         super().__init__()
         vocab_size = padded_vocab_size if vocab_size is None else vocab_size
         if not 1 <= vocab_size <= padded_vocab_size:
             raise ValueError(f"vocab_size should lie in 1 .. {padded_vocab_size}, got {vocab_size}")
-        self.ln_f = RMSNorm(n_embd, eps=norm_eps, add_unit_offset=add_unit_offset)
+        if norm_class not in ("RMSNorm", "LayerNorm"):
+            raise ValueError(f"norm_class should be 'RMSNorm' or 'LayerNorm', got {norm_class!r}")
+        if norm_class == "LayerNorm" and add_unit_offset:
+            raise ValueError("add_unit_offset belongs to RMSNorm")
+        self.ln_f = (LayerNorm(n_embd, eps=norm_eps) if norm_class == "LayerNorm"
+                     else RMSNorm(n_embd, eps=norm_eps, add_unit_offset=add_unit_offset))
         self.lm_head = nn.Linear(n_embd, padded_vocab_size, bias=False)
         self.vocab_size = vocab_size
         self.fused = True                     # False: the tensor-op restatement (whole (B, T, V) head, topk + softmax + multinomial)
@@ -143,7 +150,10 @@ class NextTokenHead(nn.Module):
             y = self.lm_head(n)
             return (y[:, -1] if x.dim() == 3 else y)[:, :self.vocab_size].to(dtype)
         last = x[:, -1] if x.dim() == 3 else x
-        _, n, _ = rms_norm_forward(last, None, self.ln_f.weight.detach(), self.ln_f.eps, self.ln_f.add_unit_offset)
+        if isinstance(self.ln_f, LayerNorm):
+            _, n, _, _, _ = layer_norm_forward(last, self.ln_f.weight.detach(), self.ln_f.bias.detach(), self.ln_f.eps)
+        else:
+            _, n, _ = rms_norm_forward(last, None, self.ln_f.weight.detach(), self.ln_f.eps, self.ln_f.add_unit_offset)
         return last_logits(n, self.lm_head.weight.detach()[:self.vocab_size], dtype)
 
     def forward(self, x: torch.Tensor, sampler: Sampler, temperature: float = 1.0, top_k=None) -> torch.Tensor:
@@ -160,7 +170,8 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
              temperature: float = 1.0, top_k=None, eos_id=None, sampler: Sampler = None) -> torch.Tensor:
     """prompt (B, T) int64 -> (B, n) tokens, the prompt included, n <= max_returned_tokens.
 
-    ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block``, ``states`` one EMPTY decode state
+    ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block`` (a ``NeoXStack`` or a sequence of
+    ``NeoXBlock`` for the parallel-residual form; one kind per call), ``states`` one EMPTY decode state
     cache per block (``FastmaxDecodeState(p=2)`` / ``LinearmaxDecodeState``), ``cos`` / ``sin`` the rope cache with a row for
     every position fed.  The prompt goes through the blocks in one call, then one token per call with the rope rows of its
     position.  Nothing is read back per token unless ``eos_id`` is given; then the loop ends once every row has produced it."""
@@ -172,7 +183,11 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     if cos.shape[0] < max_returned_tokens - 1 or sin.shape[0] < max_returned_tokens - 1:
         raise ValueError(f"generate: the rope cache has {cos.shape[0]} rows, {max_returned_tokens - 1} positions are fed")
     _check_sampling(temperature, top_k)
-    layers = blocks.blocks if isinstance(blocks, BlockStack) else blocks
+    layers = blocks.blocks if isinstance(blocks, (BlockStack, NeoXStack)) else blocks
+    neox = [isinstance(b, NeoXBlock) for b in layers]
+    if any(neox) and not all(neox):
+        raise ValueError("generate: the blocks mix NeoXBlock with another kind; a sequence holds one kind")
+    run = run_neox_blocks if any(neox) else run_blocks
     if len(states) != len(layers):
         raise ValueError(f"generate: {len(layers)} blocks need as many decode state caches, got {len(states)}")
     sampler = Sampler() if sampler is None else sampler
@@ -180,7 +195,7 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     pos = torch.arange(max_returned_tokens, device=dev)
     out = torch.empty((B, max_returned_tokens), dtype=torch.int64, device=dev)
     out[:, :T] = prompt
-    h = run_blocks(layers, F.embedding(prompt, wte), cos[:T], sin[:T], pos[:T], states)
+    h = run(layers, F.embedding(prompt, wte), cos[:T], sin[:T], pos[:T], states)
     n, done = T, None
     while True:
         token = head(h, sampler, temperature, top_k)
@@ -194,5 +209,5 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
         if n == max_returned_tokens:
             break
         t = n - 1                                                      # the position of the token just produced
-        h = run_blocks(layers, F.embedding(token.view(B, 1), wte), cos[t:t + 1], sin[t:t + 1], pos[t:t + 1], states)
+        h = run(layers, F.embedding(token.view(B, 1), wte), cos[t:t + 1], sin[t:t + 1], pos[t:t + 1], states)
     return out[:, :n]
