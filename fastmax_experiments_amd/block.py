@@ -104,15 +104,15 @@ def rms_norm_backward(dy, s, weight, rstd, ds_in=None, add_unit_offset: bool = F
     return ds.view(s.shape), dw
 
 
-def _gated_operands(I: int, *tensors):
-    out = []
-    for t in tensors:
-        _need_device(t, "gated_act")
+def _act_operands(what: str, I: int, *tensors):
+    """the operands of an element-wise operator (``what`` names it in the messages) as (M, I) rows"""
+    for t in tensors[1:]:
         if t.shape != tensors[0].shape or t.dtype != tensors[0].dtype:
-            raise ValueError(f"gated_act: operands should agree in shape and dtype, got {tuple(t.shape)} {t.dtype} "
+            raise ValueError(f"{what}: operands should agree in shape and dtype, got {tuple(t.shape)} {t.dtype} "
                              f"and {tuple(tensors[0].shape)} {tensors[0].dtype}")
-        out.append(_rows(t, I))
-    return out
+    for t in tensors:
+        _need_device(t, what)
+    return [_rows(t, I) for t in tensors]
 
 
 def gated_act_forward(a, b, act: str = "silu"):
@@ -120,7 +120,7 @@ def gated_act_forward(a, b, act: str = "silu"):
     I = a.shape[-1]
     if I == 0 or a.numel() == 0:
         raise ValueError(f"gated_act: empty input of shape {tuple(a.shape)}")
-    a2, b2 = _gated_operands(I, a, b)
+    a2, b2 = _act_operands("gated_act", I, a, b)
     y = torch.empty((a2.shape[0], I), dtype=a.dtype, device=a.device)
     ops._call("fastmax_hip_gated_act_forward", a.device,
               (a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), y.data_ptr(), y.stride(0), a2.shape[0], I, _ACT[act],
@@ -131,7 +131,7 @@ def gated_act_forward(a, b, act: str = "silu"):
 def gated_act_backward(a, b, dy, act: str = "silu"):
     """-> (da, db) in one pass over a, b, dy; act is recomputed"""
     I = a.shape[-1]
-    a2, b2, dy2 = _gated_operands(I, a, b, dy)
+    a2, b2, dy2 = _act_operands("gated_act", I, a, b, dy)
     da, db = (torch.empty((a2.shape[0], I), dtype=a.dtype, device=a.device) for _ in range(2))
     ops._call("fastmax_hip_gated_act_backward", a.device,
               (a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), dy2.data_ptr(), dy2.stride(0), da.data_ptr(),
@@ -271,7 +271,35 @@ class GemmaMLP(LLaMAMLP):
 _MLP_CLASSES = {"LLaMAMLP": LLaMAMLP, "GemmaMLP": GemmaMLP}
 
 
-class Block(nn.Module):
+class DecoderBlock(nn.Module):
+    """What the two block forms share.  A subclass builds ``norm_1``, ``attn``, ``norm_2`` (or None) and ``mlp``, starts
+    ``_fused`` at its own default, and names in ``run_sequence`` the function that runs a sequence of its kind."""
+    run_sequence = None
+
+    @classmethod
+    def from_config(cls, config: str, **kw):
+        """a block at the head and MLP shapes of a CONFIG_SHAPES entry"""
+        return cls(intermediate_size=kw.pop("intermediate_size", CONFIG_INTERMEDIATE[config]), **CONFIG_SHAPES[config], **kw)
+
+    @property
+    def fused_neighbours(self) -> bool:
+        return self._fused
+
+    @fused_neighbours.setter
+    def fused_neighbours(self, on: bool) -> None:
+        """the norm and MLP kernels on or off; the attention sub-layer's own switch (``attn.fused_neighbours``) is separate"""
+        self._fused = bool(on)
+        for m in (self.norm_1, self.norm_2, self.mlp):
+            if m is not None:
+                m.fused_neighbours = self._fused
+
+    def quantize_base(self, double_quant: bool = False):
+        self.attn.quantize_base(double_quant)
+        self.mlp.quantize_base(double_quant)
+        return self
+
+
+class Block(DecoderBlock):
     """One decoder block in the sequential-residual form (model.py:356-360).  Members ``norm_1``, ``attn``, ``norm_2``,
     ``mlp`` as in the reference, so its state dict keys carry over (``attn.attn.linear.weight``, ``mlp.fc_1.linear.weight``...)."""
 
@@ -305,26 +333,6 @@ class Block(nn.Module):
         self.mlp = _MLP_CLASSES[mlp_name](n_embd, intermediate_size, bias=bias, r=r, alpha=alpha, dropout=dropout, to_mlp=to_mlp)
         self._fused = True
 
-    @classmethod
-    def from_config(cls, config: str, **kw) -> "Block":
-        """a block at the head and MLP shapes of a CONFIG_SHAPES entry"""
-        return cls(intermediate_size=kw.pop("intermediate_size", CONFIG_INTERMEDIATE[config]), **CONFIG_SHAPES[config], **kw)
-
-    @property
-    def fused_neighbours(self) -> bool:
-        return self._fused
-
-    @fused_neighbours.setter
-    def fused_neighbours(self, on: bool) -> None:
-        """the kernels of this file on or off; the attention sub-layer's own switch (``attn.fused_neighbours``) is separate"""
-        self._fused = bool(on)
-        self.norm_1.fused_neighbours = self.norm_2.fused_neighbours = self.mlp.fused_neighbours = self._fused
-
-    def quantize_base(self, double_quant: bool = False):
-        self.attn.quantize_base(double_quant)
-        self.mlp.quantize_base(double_quant)
-        return self
-
     def run_open(self, x, n_1, cos, sin, input_pos=None, state=None):
         """everything after ``norm_1`` up to, but without, the last add: -> (m, s) with the block's output m + s"""
         h = self.attn(n_1, cos, sin, input_pos, state)
@@ -348,6 +356,9 @@ def run_blocks(blocks, x, cos, sin, input_pos=None, states=None):
             x, n_1 = rms_norm_add(m, s, blk.norm_1)
         m, s = blk.run_open(x, n_1, cos, sin, input_pos, None if states is None else states[i])
     return m + s
+
+
+Block.run_sequence = staticmethod(run_blocks)
 
 
 class BlockStack(nn.Module):

@@ -9,60 +9,16 @@
 //   anything else       (C not whole pieces, misaligned addresses, pieces > 2048): scalar path, one workgroup per row, the row
 //                       is read twice
 // On the piece paths the row is read once and stays in registers between the statistics and the scaling.
-// Reductions: the 64 lanes of a wave by xor-butterfly (every lane ends with the same bits), then the four waves through LDS,
-// added in wave order by every thread.  No atomics anywhere.
 // Backward: a workgroup walks a fixed block of rows (DW_ROWS when dweight is wanted) and keeps its columns' dweight sums in
-// registers; they leave as one row of partials per workgroup, and rmsnorm_dweight_sum_kernel adds the partial rows per column
-// in block order.
-#include "fastmax_common.h"
+// registers; they leave as one row of partials per workgroup, and partial_row_sum_kernel (row_kernels.h, with the helpers and
+// reductions both files share) adds the partial rows per column in block order.
+#include "row_kernels.h"
 #include "../../include/fastmax_hip_block.h"
 
 namespace fastmax {
 
-typedef unsigned int bu32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DW_ROWS = 16;          // rows per workgroup of the backward pass when dweight is wanted: fixed, so the sums are too
 constexpr int MAX_NP = 8;            // pieces per thread on the one-workgroup-per-row path
-
-// E elements of type U (16 or 32 bytes) <-> float registers, as 16-byte accesses
-template <typename U, int E> __device__ __forceinline__ void ld_vec(const U* p, float (&x)[E]) {
-    constexpr int PER = 16 / sizeof(U), NV = E / PER;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        bu32x4 raw = *reinterpret_cast<const bu32x4*>(p + v * PER);
-        const U* pv = reinterpret_cast<const U*>(&raw);
-#pragma unroll
-        for (int e = 0; e < PER; ++e) x[v * PER + e] = to_float(pv[e]);
-    }
-}
-template <typename U, int E> __device__ __forceinline__ void st_vec(U* p, const float (&x)[E]) {
-    constexpr int PER = 16 / sizeof(U), NV = E / PER;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        bu32x4 raw;
-        U* pv = reinterpret_cast<U*>(&raw);
-#pragma unroll
-        for (int e = 0; e < PER; ++e) pv[e] = from_float<U>(x[v * PER + e]);
-        *reinterpret_cast<bu32x4*>(p + v * PER) = raw;
-    }
-}
-template <typename U> __device__ __forceinline__ float round_to(float f) { return to_float(from_float<U>(f)); }
-// a * b rounded on its own: the sum that follows must not contract it into a fused multiply-add (hipcc contracts by default),
-// or the float32 backward with ds_in would not be the result without ds_in plus ds_in
-__device__ __forceinline__ float mul_unfused(float a, float b) {
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return p;
-}
-
-// sum over the threads that share a row: a wave (WAVE_ROW) or the whole 256-thread workgroup (red: 4 floats of LDS)
-template <bool WAVE_ROW> __device__ __forceinline__ float row_sum(float x, float* red) {
-    x = wave_sum(x);
-    if constexpr (WAVE_ROW) return x;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 struct NormFwd {
     const void *x, *r, *w;
@@ -294,33 +250,17 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_scalar_kernel(NormBwd p) {
     }
 }
 
-// dweight[c] = sum over the row blocks of part[blk][c], in block order: a workgroup takes a slab of 64 columns, its four
-// waves a quarter of the blocks each (contiguous, in order), and the four quarter sums are added in wave order
-__global__ __launch_bounds__(256) void rmsnorm_dweight_sum_kernel(const float* part, float* dweight, int nblk, int C) {
-    __shared__ float q[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    const int per = (nblk + 3) / 4;
-    const int b0 = wave * per, b1 = min(nblk, b0 + per);
-    float acc = 0.f;
-    if (c < C)
-        for (int b = b0; b < b1; ++b) acc += part[(int64_t)b * C + c];
-    q[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && c < C) dweight[c] = ((q[0][lane] + q[1][lane]) + q[2][lane]) + q[3][lane];
-}
-
 // ---- gated activation ---------------------------------------------------------------------------------------------------
 template <int ACT> __device__ __forceinline__ float act_f(float a) {
     if constexpr (ACT == FASTMAX_ACT_SILU) return a / (1.0f + expf(-a));
-    else return 0.5f * a * (1.0f + erff(a * 0.70710678118654752440f));
+    else return gelu_f(a);
 }
 template <int ACT> __device__ __forceinline__ float act_prime(float a) {
     if constexpr (ACT == FASTMAX_ACT_SILU) {
         const float sg = 1.0f / (1.0f + expf(-a));
         return sg * (1.0f + a * (1.0f - sg));
     } else {
-        return 0.5f * (1.0f + erff(a * 0.70710678118654752440f)) + a * expf(-0.5f * a * a) * 0.39894228040143267794f;
+        return gelu_prime(a);
     }
 }
 
@@ -380,22 +320,6 @@ __global__ __launch_bounds__(256) void gated_act_kernel(GatedArgs p) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static inline int elem_size(int dtype) { return dtype == FASTMAX_F32 ? 4 : 2; }
-static inline bool aligned16(const void* ptr, int64_t stride, int es) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ((stride * es) & 15) == 0;
-}
-
-// pieces per thread on the piece paths: 0 = one wave per row, 1 / 2 / 4 / 8 = one workgroup per row, -1 = scalar path
-static int norm_shape(int C, int dtype) {
-    const int e = 16 / elem_size(dtype);
-    if (C % e) return -1;
-    const int pieces = C / e;
-    if (pieces <= 64) return 0;
-    for (int np = 1; np <= MAX_NP; np *= 2)
-        if (pieces <= 256 * np) return np;
-    return -1;
-}
-
 template <typename T, typename W>
 static void launch_norm_fwd(const NormFwd& p, int shape, hipStream_t st) {
     const dim3 rows((unsigned)p.M), quads((unsigned)((p.M + 3) / 4)), blk(256);
@@ -427,24 +351,6 @@ static void launch_norm_bwd(const NormBwd& p, int shape, unsigned nblk, hipStrea
     else launch_norm_bwd_dw<T, W, false>(p, shape, nblk, st);
 }
 
-// (T, W) pairs: the weight has the activation dtype or is float32
-#define NORM_DISPATCH(FN, ...)                                                                       \
-    do {                                                                                             \
-        if (dtype == FASTMAX_F32) FN<float, float>(__VA_ARGS__);                                     \
-        else if (dtype == FASTMAX_BF16 && weight_dtype == FASTMAX_F32) FN<bf16_t, float>(__VA_ARGS__); \
-        else if (dtype == FASTMAX_BF16) FN<bf16_t, bf16_t>(__VA_ARGS__);                             \
-        else if (weight_dtype == FASTMAX_F32) FN<f16_t, float>(__VA_ARGS__);                         \
-        else FN<f16_t, f16_t>(__VA_ARGS__);                                                          \
-    } while (0)
-
-static int norm_check(int M, int C, int dtype, int weight_dtype) {
-    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
-    if (weight_dtype != dtype && weight_dtype != FASTMAX_F32) return FASTMAX_E_BAD_DTYPE;
-    if (M <= 0 || C <= 0) return FASTMAX_E_BAD_SHAPE;
-    return 0;
-}
-static inline bool elem_aligned(const void* ptr, int es) { return (reinterpret_cast<uintptr_t>(ptr) & (es - 1)) == 0; }
-
 template <typename T, int ACT>
 static void launch_gated_act(const GatedArgs& p, bool vec, bool bwd, unsigned blocks, hipStream_t st) {
     const dim3 grid(blocks), blk(256);
@@ -458,19 +364,12 @@ static int gated_act(const GatedArgs& p, bool bwd, int act, int dtype, hipStream
     if (!p.a || !p.b || (bwd ? (!p.dy || !p.da || !p.db) : !p.y)) return FASTMAX_E_NULL;
     if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
     if (p.M <= 0 || p.I <= 0 || (act != FASTMAX_ACT_SILU && act != FASTMAX_ACT_GELU)) return FASTMAX_E_BAD_SHAPE;
-    const int es = elem_size(dtype), e = 16 / es;
     const void* ptrs[5] = {p.a, p.b, bwd ? p.dy : p.y, bwd ? p.da : p.y, bwd ? p.db : p.y};
     const int64_t strides[5] = {p.as, p.bs, bwd ? p.dys : p.ys, bwd ? p.das : p.ys, bwd ? p.dbs : p.ys};
-    bool vec = p.I % e == 0;
-    for (int i = 0; i < 5; ++i) {
-        if (strides[i] < p.I) return FASTMAX_E_BAD_SHAPE;
-        if (!elem_aligned(ptrs[i], es)) return FASTMAX_E_ALIGNMENT;
-        vec = vec && aligned16(ptrs[i], strides[i], es);
-    }
-    const int64_t units = (int64_t)p.M * (vec ? p.I / e : p.I);
-    const int64_t blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffff) return FASTMAX_E_BAD_SHAPE;
-    const unsigned nb = (unsigned)blocks;
+    bool vec;
+    unsigned nb;
+    const int rc = elementwise_geometry(5, ptrs, strides, p.M, p.I, dtype, &vec, &nb);
+    if (rc) return rc;
 #define GATED_T(T)                                                                   \
     do {                                                                             \
         if (act == FASTMAX_ACT_SILU) launch_gated_act<T, FASTMAX_ACT_SILU>(p, vec, bwd, nb, st); \
@@ -500,7 +399,7 @@ int fastmax_hip_rmsnorm_forward(const void* x, int64_t x_stride, const void* r, 
     if (!elem_aligned(x, es) || !elem_aligned(weight, ws) || !elem_aligned(y, ws) || !elem_aligned(rstd, 4) ||
         (r && (!elem_aligned(r, es) || !elem_aligned(s_out, es))))
         return FASTMAX_E_ALIGNMENT;
-    int shape = norm_shape(C, dtype);
+    int shape = norm_shape(C, dtype, MAX_NP);
     if (!aligned16(x, x_stride, es) || !aligned16(y, y_stride, ws) || !aligned16(weight, 0, ws) ||
         (r && (!aligned16(r, r_stride, es) || !aligned16(s_out, s_stride, es))))
         shape = -1;
@@ -533,7 +432,7 @@ int fastmax_hip_rmsnorm_backward(const void* dy, int64_t dy_stride, const void* 
         if (workspace_bytes < need) return FASTMAX_E_WORKSPACE;
         if (reinterpret_cast<uintptr_t>(workspace) & 15) return FASTMAX_E_ALIGNMENT;
     }
-    int shape = norm_shape(C, dtype);
+    int shape = norm_shape(C, dtype, MAX_NP);
     if (!aligned16(dy, dy_stride, ws) || !aligned16(s, s_stride, es) || !aligned16(weight, 0, ws) ||
         !aligned16(ds, ds_stride, es) || (ds_in && !aligned16(ds_in, ds_in_stride, es)))
         shape = -1;
@@ -547,7 +446,7 @@ int fastmax_hip_rmsnorm_backward(const void* dy, int64_t dy_stride, const void* 
     NORM_DISPATCH(launch_norm_bwd, p, shape, nblk, st);
     int err = (int)hipGetLastError();
     if (err || !dweight) return err;
-    hipLaunchKernelGGL(rmsnorm_dweight_sum_kernel, dim3((unsigned)((C + 63) / 64)), dim3(256), 0, st, p.part, dweight, (int)nblk, C);
+    launch_partial_row_sum<1>(p.part, {{dweight}}, (int)nblk, C, st);
     return (int)hipGetLastError();
 }
 

@@ -12,79 +12,23 @@
 //   anything else       (C not whole pieces, misaligned addresses, pieces > 1024): scalar path, one workgroup per row, the row
 //                       is read three times
 // On the piece paths the row is read once and stays in registers: the mean, then the deviations from it, then the scaling.
-// Reductions: the 64 lanes of a wave by xor-butterfly (every lane ends with the same bits), then the four waves through LDS,
-// added in wave order by every thread.  No atomics anywhere.
 // Backward: a workgroup walks a fixed block of rows (PG_ROWS when a parameter gradient is wanted) and keeps its columns' sums in
-// registers; they leave as NS rows of partials per workgroup (dw1, db1[, dw2, db2]), and param_grad_sum_kernel adds the partial
-// rows per column in block order.
-#include "fastmax_common.h"
+// registers; they leave as NS rows of partials per workgroup (dw1, db1[, dw2, db2]), and partial_row_sum_kernel (row_kernels.h,
+// with the helpers and reductions both files share) adds the partial rows per column in block order.
+#include "row_kernels.h"
 #include "../../include/fastmax_hip_neox.h"
 
 namespace fastmax {
 namespace neox {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PG_ROWS = 16;          // rows per workgroup of the backward pass when parameter gradients are wanted: fixed, so the sums are too
 constexpr int MAX_NP = 4;            // pieces per thread on the one-workgroup-per-row path
 
-// E elements of type U (16 or 32 bytes) <-> float registers, as 16-byte accesses
-template <typename U, int E> __device__ __forceinline__ void ld_vec(const U* p, float (&x)[E]) {
-    constexpr int PER = 16 / sizeof(U), NV = E / PER;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        u32x4 raw = *reinterpret_cast<const u32x4*>(p + v * PER);
-        const U* pv = reinterpret_cast<const U*>(&raw);
-#pragma unroll
-        for (int e = 0; e < PER; ++e) x[v * PER + e] = to_float(pv[e]);
-    }
-}
-template <typename U, int E> __device__ __forceinline__ void st_vec(U* p, const float (&x)[E]) {
-    constexpr int PER = 16 / sizeof(U), NV = E / PER;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        u32x4 raw;
-        U* pv = reinterpret_cast<U*>(&raw);
-#pragma unroll
-        for (int e = 0; e < PER; ++e) pv[e] = from_float<U>(x[v * PER + e]);
-        *reinterpret_cast<u32x4*>(p + v * PER) = raw;
-    }
-}
-template <typename U> __device__ __forceinline__ float round_to(float f) { return to_float(from_float<U>(f)); }
-// a * b rounded on its own: the sum that follows must not contract it into a fused multiply-add (hipcc contracts by default),
-// or the float32 backward with ds_in would not be the result without ds_in plus ds_in
-__device__ __forceinline__ float mul_unfused(float a, float b) {
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return p;
-}
 // the residual stream: x, round(x + r1), or round(round(r1 + r2) + x) -- the block's mlp + h + x, left to right
 template <typename T> __device__ __forceinline__ float stream_sum(float x, float r1, float r2, bool has1, bool has2) {
     if (!has1) return x;
     if (!has2) return round_to<T>(x + r1);
     return round_to<T>(round_to<T>(r1 + r2) + x);
-}
-
-// sum over the threads that share a row: a wave (WAVE_ROW) or the whole 256-thread workgroup (red: 4 floats of LDS)
-template <bool WAVE_ROW> __device__ __forceinline__ float row_sum(float x, float* red) {
-    x = wave_sum(x);
-    if constexpr (WAVE_ROW) return x;
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-// two sums behind one barrier (red: 2 x 4 floats)
-template <bool WAVE_ROW> __device__ __forceinline__ void row_sum2(float& a, float& b, float (*red)[4]) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    if constexpr (WAVE_ROW) return;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    a = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-    b = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
 }
 
 struct LnFwd {
@@ -392,33 +336,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_scalar_kernel(LnBwd p) {
     }
 }
 
-// out_k[c] = sum over the row blocks of part[blk][k][c], in block order: a workgroup takes a slab of 64 columns of one of the
-// ns partial rows (blockIdx.y), its four waves a quarter of the blocks each (contiguous, in order), and the four quarter sums
-// are added in wave order.  A null out_k is skipped.
-__global__ __launch_bounds__(256) void param_grad_sum_kernel(const float* part, float* o0, float* o1, float* o2, float* o3,
-                                                             int nblk, int C, int ns) {
-    __shared__ float q[4][64];
-    const int k = blockIdx.y;
-    float* out = k == 0 ? o0 : k == 1 ? o1 : k == 2 ? o2 : o3;
-    if (!out) return;                                      // the whole workgroup: nothing below is reached by a part of it
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    const int per = (nblk + 3) / 4;
-    const int b0 = wave * per, b1 = min(nblk, b0 + per);
-    float acc = 0.f;
-    if (c < C)
-        for (int b = b0; b < b1; ++b) acc += part[((int64_t)b * ns + k) * C + c];
-    q[wave][lane] = acc;
-    __syncthreads();
-    if (wave == 0 && c < C) out[c] = ((q[0][lane] + q[1][lane]) + q[2][lane]) + q[3][lane];
-}
-
 // ---- ungated activation -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gelu_f(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_prime(float a) {
-    return 0.5f * (1.0f + erff(a * 0.70710678118654752440f)) + a * expf(-0.5f * a * a) * 0.39894228040143267794f;
-}
-
 struct ActArgs {
     const void *a, *dy;
     void* out;                   // y (forward) or da (backward)
@@ -456,23 +374,6 @@ __global__ __launch_bounds__(256) void act_kernel(ActArgs p) {
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static inline int elem_size(int dtype) { return dtype == FASTMAX_F32 ? 4 : 2; }
-static inline bool aligned16(const void* ptr, int64_t stride, int es) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ((stride * es) & 15) == 0;
-}
-static inline bool elem_aligned(const void* ptr, int es) { return (reinterpret_cast<uintptr_t>(ptr) & (es - 1)) == 0; }
-
-// pieces per thread on the piece paths: 0 = one wave per row, 1 / 2 / 4 = one workgroup per row, -1 = scalar path
-static int norm_shape(int C, int dtype) {
-    const int e = 16 / elem_size(dtype);
-    if (C % e) return -1;
-    const int pieces = C / e;
-    if (pieces <= 64) return 0;
-    for (int np = 1; np <= MAX_NP; np *= 2)
-        if (pieces <= 256 * np) return np;
-    return -1;
-}
-
 template <typename T, typename W>
 static void launch_ln_fwd(const LnFwd& p, int shape, hipStream_t st) {
     const dim3 rows((unsigned)p.M), quads((unsigned)((p.M + 3) / 4)), blk(256);
@@ -503,23 +404,6 @@ static void launch_ln_bwd(const LnBwd& p, int shape, unsigned nblk, hipStream_t 
     else launch_ln_bwd_ns<T, W, 0>(p, shape, nblk, st);
 }
 
-// (T, W) pairs: the parameters have the activation dtype or are float32
-#define LN_DISPATCH(FN, ...)                                                                         \
-    do {                                                                                             \
-        if (dtype == FASTMAX_F32) FN<float, float>(__VA_ARGS__);                                     \
-        else if (dtype == FASTMAX_BF16 && weight_dtype == FASTMAX_F32) FN<bf16_t, float>(__VA_ARGS__); \
-        else if (dtype == FASTMAX_BF16) FN<bf16_t, bf16_t>(__VA_ARGS__);                             \
-        else if (weight_dtype == FASTMAX_F32) FN<f16_t, float>(__VA_ARGS__);                         \
-        else FN<f16_t, f16_t>(__VA_ARGS__);                                                          \
-    } while (0)
-
-static int norm_check(int M, int C, int dtype, int weight_dtype) {
-    if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
-    if (weight_dtype != dtype && weight_dtype != FASTMAX_F32) return FASTMAX_E_BAD_DTYPE;
-    if (M <= 0 || C <= 0) return FASTMAX_E_BAD_SHAPE;
-    return 0;
-}
-
 template <typename T>
 static void launch_act(const ActArgs& p, bool vec, bool bwd, unsigned blocks, hipStream_t st) {
     const dim3 grid(blocks), blk(256);
@@ -533,19 +417,12 @@ static int act_call(const ActArgs& p, bool bwd, int act, int dtype, hipStream_t 
     if (!p.a || !p.out || (bwd && !p.dy)) return FASTMAX_E_NULL;
     if (dtype < 0 || dtype > FASTMAX_F16) return FASTMAX_E_BAD_DTYPE;
     if (p.M <= 0 || p.I <= 0 || act != FASTMAX_NEOX_ACT_GELU) return FASTMAX_E_BAD_SHAPE;
-    const int es = elem_size(dtype), e = 16 / es;
     const void* ptrs[3] = {p.a, p.out, bwd ? p.dy : p.a};
     const int64_t strides[3] = {p.as, p.os, bwd ? p.dys : p.as};
-    bool vec = p.I % e == 0;
-    for (int i = 0; i < 3; ++i) {
-        if (strides[i] < p.I) return FASTMAX_E_BAD_SHAPE;
-        if (!elem_aligned(ptrs[i], es)) return FASTMAX_E_ALIGNMENT;
-        vec = vec && aligned16(ptrs[i], strides[i], es);
-    }
-    const int64_t units = (int64_t)p.M * (vec ? p.I / e : p.I);
-    const int64_t blocks = (units + 255) / 256;
-    if (blocks > 0x7fffffff) return FASTMAX_E_BAD_SHAPE;
-    const unsigned nb = (unsigned)blocks;
+    bool vec;
+    unsigned nb;
+    const int rc = elementwise_geometry(3, ptrs, strides, p.M, p.I, dtype, &vec, &nb);
+    if (rc) return rc;
     if (dtype == FASTMAX_F32) launch_act<float>(p, vec, bwd, nb, st);
     else if (dtype == FASTMAX_BF16) launch_act<bf16_t>(p, vec, bwd, nb, st);
     else launch_act<f16_t>(p, vec, bwd, nb, st);
@@ -574,7 +451,7 @@ int fastmax_hip_layernorm_forward(const void* x, int64_t x_stride, const void* r
         !elem_aligned(b2, ws) || !elem_aligned(mean, 4) || !elem_aligned(rstd, 4) || !elem_aligned(r1, es) ||
         !elem_aligned(r2, es) || (r1 && !elem_aligned(s_out, es)) || (w2 && !elem_aligned(y2, es)))
         return FASTMAX_E_ALIGNMENT;
-    int shape = norm_shape(C, dtype);
+    int shape = norm_shape(C, dtype, MAX_NP);
     if (!aligned16(x, x_stride, es) || !aligned16(y1, y1_stride, es) || !aligned16(w1, 0, ws) || !aligned16(b1, 0, ws) ||
         !aligned16(w2, 0, ws) || !aligned16(b2, 0, ws) || (r1 && (!aligned16(r1, r1_stride, es) || !aligned16(s_out, s_stride, es))) ||
         (r2 && !aligned16(r2, r2_stride, es)) || (w2 && !aligned16(y2, y2_stride, es)))
@@ -582,7 +459,7 @@ int fastmax_hip_layernorm_forward(const void* x, int64_t x_stride, const void* r
     LnFwd p{x, r1, r2, w1, b1, w2, w2 ? b2 : nullptr, r1 ? s_out : nullptr, y1, w2 ? y2 : nullptr, mean, rstd,
             x_stride, r1_stride, r2_stride, s_stride, y1_stride, y2_stride, M, C, eps};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    LN_DISPATCH(launch_ln_fwd, p, shape, st);
+    NORM_DISPATCH(launch_ln_fwd, p, shape, st);
     return (int)hipGetLastError();
 }
 
@@ -614,7 +491,7 @@ int fastmax_hip_layernorm_backward(const void* dy1, int64_t dy1_stride, const vo
         if (workspace_bytes < need) return FASTMAX_E_WORKSPACE;
         if (reinterpret_cast<uintptr_t>(workspace) & 15) return FASTMAX_E_ALIGNMENT;
     }
-    int shape = norm_shape(C, dtype);
+    int shape = norm_shape(C, dtype, MAX_NP);
     if (!aligned16(dy1, dy1_stride, es) || !aligned16(s, s_stride, es) || !aligned16(w1, 0, ws) || !aligned16(ds, ds_stride, es) ||
         (pair && (!aligned16(dy2, dy2_stride, es) || !aligned16(w2, 0, ws))) || (ds_in && !aligned16(ds_in, ds_in_stride, es)))
         shape = -1;
@@ -626,11 +503,11 @@ int fastmax_hip_layernorm_backward(const void* dy1, int64_t dy1_stride, const vo
     LnBwd p{dy1, dy2, s, w1, w2, ds_in, mean, rstd, ds, want ? reinterpret_cast<float*>(workspace) : nullptr,
             dy1_stride, dy2_stride, s_stride, ds_in_stride, ds_stride, M, C, rpb, ns};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    LN_DISPATCH(launch_ln_bwd, p, shape, nblk, st);
+    NORM_DISPATCH(launch_ln_bwd, p, shape, nblk, st);
     int err = (int)hipGetLastError();
     if (err || !want) return err;
-    hipLaunchKernelGGL(param_grad_sum_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)ns), dim3(256), 0, st, p.part, dw1, db1,
-                       dw2, db2, (int)nblk, C, ns);
+    if (pair) launch_partial_row_sum<4>(p.part, {{dw1, db1, dw2, db2}}, (int)nblk, C, st);
+    else launch_partial_row_sum<2>(p.part, {{dw1, db1}}, (int)nblk, C, st);
     return (int)hipGetLastError();
 }
 

@@ -71,12 +71,8 @@ class AttentionStack(nn.Module):
         return self
 
     def forward(self, x, cos, sin):
-        if self.block == "full":
-            from .block import run_blocks
-            return run_blocks(self.blocks, x, cos, sin)
-        if self.block == "neox":
-            from .neox_block import run_neox_blocks
-            return run_neox_blocks(self.blocks, x, cos, sin)
+        if self.block != "attention":
+            return type(self.blocks[0]).run_sequence(self.blocks, x, cos, sin)
         for b in self.blocks:
             x = x + b(x, cos, sin)
         return x

@@ -17,8 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .block import BlockStack, RMSNorm, rms_norm_forward, run_blocks
-from .neox_block import LayerNorm, NeoXBlock, NeoXStack, layer_norm_forward, run_neox_blocks
+from .block import BlockStack, RMSNorm, rms_norm_forward
+from .neox_block import LayerNorm, NeoXStack, layer_norm_forward
 
 _MASK64 = (1 << 64) - 1
 
@@ -184,12 +184,12 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
         raise ValueError(f"generate: the rope cache has {cos.shape[0]} rows, {max_returned_tokens - 1} positions are fed")
     _check_sampling(temperature, top_k)
     layers = blocks.blocks if isinstance(blocks, (BlockStack, NeoXStack)) else blocks
-    neox = [isinstance(b, NeoXBlock) for b in layers]
-    if any(neox) and not all(neox):
+    runs = {type(b).run_sequence for b in layers}                      # a block's class names what runs a sequence of its kind
+    if len(runs) > 1:
         raise ValueError("generate: the blocks mix NeoXBlock with another kind; a sequence holds one kind")
-    run = run_neox_blocks if any(neox) else run_blocks
     if len(states) != len(layers):
         raise ValueError(f"generate: {len(layers)} blocks need as many decode state caches, got {len(states)}")
+    (run,) = runs
     sampler = Sampler() if sampler is None else sampler
     dev = prompt.device
     pos = torch.arange(max_returned_tokens, device=dev)

@@ -28,8 +28,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .attention_block import CONFIG_SHAPES, CausalSelfAttention
-from .block import CONFIG_INTERMEDIATE, _need_device, _rows
+from .attention_block import CausalSelfAttention
+from .block import DecoderBlock, _act_operands, _need_device, _rows
 from .lora import LoRALinear
 
 FUSED_NEIGHBOURS_DEFAULT = False          # what ``fused_neighbours`` of a newly built module starts as
@@ -109,22 +109,12 @@ def layer_norm_backward(dy1, s, weight, mean, rstd, dy2=None, weight2=None, ds_i
     return (ds.view(s.shape), *grads)
 
 
-def _act_operands(I: int, *tensors):
-    for t in tensors[1:]:
-        if t.shape != tensors[0].shape or t.dtype != tensors[0].dtype:
-            raise ValueError(f"gelu: operands should agree in shape and dtype, got {tuple(t.shape)} {t.dtype} "
-                             f"and {tuple(tensors[0].shape)} {tensors[0].dtype}")
-    for t in tensors:
-        _need_device(t, "gelu")
-    return [_rows(t, I) for t in tensors]
-
-
 def gelu_forward(a):
     """exact GELU a (1 + erf(a / sqrt 2)) / 2, rounded to a's dtype; a (..., I), any row stride"""
     I = a.shape[-1] if a.dim() else 0
     if I == 0 or a.numel() == 0:
         raise ValueError(f"gelu: empty input of shape {tuple(a.shape)}")
-    (a2,) = _act_operands(I, a)
+    (a2,) = _act_operands("gelu", I, a)
     y = torch.empty((a2.shape[0], I), dtype=a.dtype, device=a.device)
     ops._call("fastmax_hip_act_forward", a.device,
               (a2.data_ptr(), a2.stride(0), y.data_ptr(), I, a2.shape[0], I, _lib.NEOX_ACT_GELU, ops._DT[a.dtype]))
@@ -136,7 +126,7 @@ def gelu_backward(a, dy):
     I = a.shape[-1] if a.dim() else 0
     if I == 0 or a.numel() == 0:
         raise ValueError(f"gelu: empty input of shape {tuple(a.shape)}")
-    a2, dy2 = _act_operands(I, a, dy)
+    a2, dy2 = _act_operands("gelu", I, a, dy)
     da = torch.empty((a2.shape[0], I), dtype=a.dtype, device=a.device)
     ops._call("fastmax_hip_act_backward", a.device,
               (a2.data_ptr(), a2.stride(0), dy2.data_ptr(), dy2.stride(0), da.data_ptr(), I, a2.shape[0], I, _lib.NEOX_ACT_GELU,
@@ -263,7 +253,7 @@ class GptNeoxMLP(nn.Module):
         return self.proj(gelu(a) if self.fused_neighbours else F.gelu(a))
 
 
-class NeoXBlock(nn.Module):
+class NeoXBlock(DecoderBlock):
     """One decoder block in the parallel-residual form (model.py:350-352).  Members ``norm_1``, ``attn``, ``norm_2``, ``mlp``
     as in the reference, so its state dict keys carry over (``norm_1.bias``, ``attn.attn.linear.weight``,
     ``mlp.fc.linear.weight`` ...); ``norm_2`` is absent with ``shared_attention_norm``."""
@@ -285,28 +275,6 @@ class NeoXBlock(nn.Module):
                               gelu_approximate=gelu_approximate)
         self._fused = FUSED_NEIGHBOURS_DEFAULT
 
-    @classmethod
-    def from_config(cls, config: str, **kw) -> "NeoXBlock":
-        """a block at the head and MLP shapes of a CONFIG_SHAPES entry"""
-        return cls(intermediate_size=kw.pop("intermediate_size", CONFIG_INTERMEDIATE[config]), **CONFIG_SHAPES[config], **kw)
-
-    @property
-    def fused_neighbours(self) -> bool:
-        return self._fused
-
-    @fused_neighbours.setter
-    def fused_neighbours(self, on: bool) -> None:
-        """the kernels of this file on or off; the attention sub-layer's own switch (``attn.fused_neighbours``) is separate"""
-        self._fused = bool(on)
-        self.norm_1.fused_neighbours = self.mlp.fused_neighbours = self._fused
-        if self.norm_2 is not None:
-            self.norm_2.fused_neighbours = self._fused
-
-    def quantize_base(self, double_quant: bool = False):
-        self.attn.quantize_base(double_quant)
-        self.mlp.quantize_base(double_quant)
-        return self
-
     def run_open(self, n_1, n_2, cos, sin, input_pos=None, state=None):
         """both branches after the norms, without the three-way add: -> (m, h) with the block's output m + h + x"""
         h = self.attn(n_1, cos, sin, input_pos, state)
@@ -327,6 +295,9 @@ def run_neox_blocks(blocks, x, cos, sin, input_pos=None, states=None):
         x, n_1, n_2 = layer_norm_pair(x, blk.norm_1, blk.norm_2, m, h)
         m, h = blk.run_open(n_1, n_2, cos, sin, input_pos, None if states is None else states[i])
     return m + h + x
+
+
+NeoXBlock.run_sequence = staticmethod(run_neox_blocks)
 
 
 class NeoXStack(nn.Module):

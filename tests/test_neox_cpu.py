@@ -422,3 +422,22 @@ def test_attention_stack_builds_neox_blocks_and_generate_refuses_a_mix():
     with pytest.raises(ValueError, match="mix"):
         generate.generate(torch.zeros(40, 64), mix, head, [None, None], torch.zeros(2, 3, dtype=torch.int64), 6,
                           cos=torch.zeros(8, 4), sin=torch.zeros(8, 4))
+
+
+def test_the_two_block_forms_share_a_base_and_name_their_runner():
+    from fastmax_experiments_amd import block, neox_block
+    from fastmax_experiments_amd.block import Block, DecoderBlock
+    from fastmax_experiments_amd.neox_block import NeoXBlock
+    assert issubclass(Block, DecoderBlock) and issubclass(NeoXBlock, DecoderBlock)
+    assert Block.run_sequence is block.run_blocks and NeoXBlock.run_sequence is neox_block.run_neox_blocks
+    for name in ("from_config", "quantize_base", "fused_neighbours"):      # held once, by the base
+        assert name in vars(DecoderBlock) and name not in vars(Block) and name not in vars(NeoXBlock)
+    b = Block(n_embd=64, n_head=4, intermediate_size=176)
+    assert b.fused_neighbours is True and b.run_sequence is block.run_blocks
+    n = NeoXBlock(shared_attention_norm=True, **SMALL)
+    assert n.norm_2 is None and n.fused_neighbours is neox_block.FUSED_NEIGHBOURS_DEFAULT
+    for on in (True, False):
+        n.fused_neighbours = on                                            # walks norm_1 and mlp; the absent norm_2 is passed over
+        assert n.fused_neighbours is on and n.norm_1.fused_neighbours is on and n.mlp.fused_neighbours is on
+        b.fused_neighbours = on
+        assert b.norm_1.fused_neighbours is on and b.norm_2.fused_neighbours is on and b.mlp.fused_neighbours is on
