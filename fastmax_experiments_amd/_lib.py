@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
-header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI and the
-NeoX block's (NEOX_HEADER) the table NEOX_ABI, set on the same handle.
+header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
+NeoX block's (NEOX_HEADER) the table NEOX_ABI and the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -155,6 +155,16 @@ NEOX_ABI = {
     "fastmax_hip_act_forward": (ci, [vp, i64, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_act_backward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
 }
+# the decode cursor's side header (position, draw number and output column of a generation loop in device memory: the feed at the
+# start of a step, the sampler at its end): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
+# tests/test_cursor_cpu.py checks each row against the prototype.
+CURSOR_HEADER = "fastmax_hip_cursor.h"
+CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
+CURSOR_ABI = {
+    "fastmax_hip_cursor_bytes": (sz, []),
+    "fastmax_hip_cursor_feed": (ci, [vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, vp, vp, i64, i64, vp, vp, ci, ci, vp]),
+    "fastmax_hip_sample_cursor": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, vp]),
+}
 
 _lib = None
 
@@ -168,7 +178,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

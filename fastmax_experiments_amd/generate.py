@@ -8,6 +8,9 @@ token.  Here (csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, boun
                    logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device
     NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler
     generate       prompt -> tokens through decoder blocks (``Block`` or ``NeoXBlock``) on their decode state caches
+    DecodeCursor, GraphedDecoder   the same loop as ONE graph replay per token: position, draw number and output column live in a
+                   device record (csrc/decode_cursor.hip, include/fastmax_hip_cursor.h, ``_lib.CURSOR_ABI``) that the step's first
+                   and last kernel read and advance, so every replay takes the same arguments
 What differs from the reference: logits are float32 by default (``dtype=`` gives the reference's), and the random stream is the
 sampler's own seeded one instead of torch's generator, so a (seed, draw) pair reproduces a token on any batch.  There is no CPU
 path through the kernels; ``NextTokenHead.fused = False`` selects the tensor-op restatement for A/B runs.
@@ -16,7 +19,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from .block import BlockStack, RMSNorm, rms_norm_forward
 from .neox_block import LayerNorm, NeoXStack, layer_norm_forward
 
@@ -165,16 +168,7 @@ class NextTokenHead(nn.Module):
         return sampler.sample(logits, temperature, top_k)
 
 
-@torch.no_grad()
-def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: torch.Tensor, max_returned_tokens: int, *, cos, sin,
-             temperature: float = 1.0, top_k=None, eos_id=None, sampler: Sampler = None) -> torch.Tensor:
-    """prompt (B, T) int64 -> (B, n) tokens, the prompt included, n <= max_returned_tokens.
-
-    ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block`` (a ``NeoXStack`` or a sequence of
-    ``NeoXBlock`` for the parallel-residual form; one kind per call), ``states`` one EMPTY decode state
-    cache per block (``FastmaxDecodeState(p=2)`` / ``LinearmaxDecodeState``), ``cos`` / ``sin`` the rope cache with a row for
-    every position fed.  The prompt goes through the blocks in one call, then one token per call with the rope rows of its
-    position.  Nothing is read back per token unless ``eos_id`` is given; then the loop ends once every row has produced it."""
+def _check_prompt(prompt, max_returned_tokens, cos, sin):
     if prompt.dim() != 2 or prompt.dtype != torch.int64:
         raise ValueError(f"generate: prompt should be (B, T) int64, got {tuple(prompt.shape)} {prompt.dtype}")
     B, T = prompt.shape
@@ -182,7 +176,11 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
         raise ValueError(f"generate: max_returned_tokens ({max_returned_tokens}) should exceed the prompt's length ({T} >= 1)")
     if cos.shape[0] < max_returned_tokens - 1 or sin.shape[0] < max_returned_tokens - 1:
         raise ValueError(f"generate: the rope cache has {cos.shape[0]} rows, {max_returned_tokens - 1} positions are fed")
-    _check_sampling(temperature, top_k)
+    return B, T
+
+
+def _layers_and_run(blocks, states):
+    """the blocks as a sequence and what runs a sequence of their kind over the decode state caches"""
     layers = blocks.blocks if isinstance(blocks, (BlockStack, NeoXStack)) else blocks
     runs = {type(b).run_sequence for b in layers}                      # a block's class names what runs a sequence of its kind
     if len(runs) > 1:
@@ -190,6 +188,237 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     if len(states) != len(layers):
         raise ValueError(f"generate: {len(layers)} blocks need as many decode state caches, got {len(states)}")
     (run,) = runs
+    return layers, run
+
+
+class DecodeCursor:
+    """The device record of include/fastmax_hip_cursor.h (csrc/decode_cursor.hip): the position of the next token to feed, the
+    sampler's seed and draw number and a sticky overflow flag, advanced by the kernels themselves.  ``feed`` starts a decode step
+    and ``sample`` ends it; both take the same arguments every token, so a step between them can be recorded as a graph."""
+
+    def __init__(self, device) -> None:
+        self.words = torch.zeros(_lib.lib().fastmax_hip_cursor_bytes() // 8, dtype=torch.int64, device=device)
+        _need_device(self.words, "DecodeCursor")
+
+    def arm(self, pos: int, draw: int, seed: int) -> None:
+        """the next feed takes position ``pos``; the sample after it is draw number ``draw`` under ``seed`` and fills column
+        ``pos + 1``.  One small copy; the overflow flag is cleared."""
+        if pos < 0:
+            raise ValueError(f"DecodeCursor.arm: pos should be >= 0, got {pos}")
+        host = torch.zeros(self.words.numel(), dtype=torch.int64)
+        host[_lib.CURSOR_POS], host[_lib.CURSOR_NEXT] = int(pos), -1
+        host[_lib.CURSOR_DRAW_BASE], host[_lib.CURSOR_SEED] = _signed64(int(draw) - (int(pos) + 1)), _signed64(int(seed))
+        self.words.copy_(host)
+
+    def read(self) -> dict:
+        """the record on the host (this synchronises): pos, next, overflow"""
+        w = self.words.tolist()
+        return dict(pos=w[_lib.CURSOR_POS], next=w[_lib.CURSOR_NEXT], overflow=bool(w[_lib.CURSOR_OVERFLOW]))
+
+    def feed(self, tok, wte, x, cos, sin, cos_row, sin_row) -> None:
+        """x[b] = wte[tok[b]]; cos_row, sin_row (1, n) = the first n columns of row ``pos`` of cos, sin.  tok (B,) int64,
+        wte (N, C), x (B, C) in wte's dtype, cos and sin (R, >= n) with shared strides; everything with unit stride along a row."""
+        if tok.dim() != 1 or tok.dtype != torch.int64 or not tok.is_contiguous():
+            raise ValueError(f"DecodeCursor.feed: tok should be (B,) int64, got {tuple(tok.shape)} {tok.dtype}")
+        B = tok.shape[0]
+        if wte.dim() != 2 or tuple(x.shape) != (B, wte.shape[1]) or B < 1 or x.stride(1) != 1 or wte.stride(1) != 1:
+            raise ValueError(f"DecodeCursor.feed: wte (N, C) and x ({B}, C) with unit stride along C, got {tuple(wte.shape)}, {tuple(x.shape)}")
+        if x.dtype != wte.dtype or wte.dtype not in ops._DT:
+            raise TypeError(f"DecodeCursor.feed: x and wte should share float32, bfloat16 or float16, got {x.dtype} and {wte.dtype}")
+        n = cos_row.shape[-1]
+        if (cos.dim() != 2 or cos.shape != sin.shape or cos.stride() != sin.stride() or cos.stride(1) != 1 or cos.shape[1] < n
+                or cos_row.numel() != n or sin_row.numel() != n or not (cos_row.is_contiguous() and sin_row.is_contiguous())):
+            raise ValueError(f"DecodeCursor.feed: cos, sin (R, >= n) alike and one-row buffers of n columns, got {tuple(cos.shape)}, "
+                             f"{tuple(sin.shape)}, {tuple(cos_row.shape)}, {tuple(sin_row.shape)}")
+        if len({cos.dtype, sin.dtype, cos_row.dtype, sin_row.dtype}) != 1 or cos.dtype not in ops._DT:
+            raise TypeError(f"DecodeCursor.feed: the rope cache and its row buffers should share one dtype, got {cos.dtype}, {cos_row.dtype}")
+        ops._call("fastmax_hip_cursor_feed", self.words.device,
+                  (self.words.data_ptr(), tok.data_ptr(), wte.data_ptr(), wte.stride(0), wte.shape[0], x.data_ptr(), x.stride(0), B,
+                   wte.shape[1], ops._DT[wte.dtype], cos.data_ptr(), sin.data_ptr(), cos.stride(0), cos.shape[0], cos_row.data_ptr(),
+                   sin_row.data_ptr(), n, ops._DT[cos.dtype]))
+
+    def sample(self, logits, tok, out, done=None, eos_id=None, temperature: float = 1.0, top_k=None) -> None:
+        """``Sampler(seed).sample`` at the cursor's draw number: the tokens go to tok (B,) and to column ``next`` of out (B, L)
+        int64, ``token == eos_id`` is ORed into done (B,) uint8, and the cursor moves on by one."""
+        _check_sampling(temperature, top_k)
+        rows = _logit_rows(logits, "DecodeCursor.sample")
+        B, V = rows.shape
+        if tuple(tok.shape) != (B,) or tok.dtype != torch.int64 or not tok.is_contiguous():
+            raise ValueError(f"DecodeCursor.sample: tok should be ({B},) int64, got {tuple(tok.shape)} {tok.dtype}")
+        if out.dim() != 2 or out.shape[0] != B or out.dtype != torch.int64 or out.stride(1) != 1:
+            raise ValueError(f"DecodeCursor.sample: out should be ({B}, L) int64, got {tuple(out.shape)} {out.dtype}")
+        if eos_id is not None and (done is None or tuple(done.shape) != (B,) or done.dtype != torch.uint8 or not done.is_contiguous()):
+            raise ValueError(f"DecodeCursor.sample: eos_id needs done ({B},) uint8")
+        ops._call("fastmax_hip_sample_cursor", rows.device,
+                  (rows.data_ptr(), rows.stride(0), self.words.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0), out.shape[1],
+                   ops._ptr(done), -1 if eos_id is None else int(eos_id), B, V, 0 if top_k is None else min(int(top_k), V),
+                   float(temperature)))
+
+
+class GraphedDecoder:
+    """``generate`` with one graph replay per token after the first.
+
+    Owns the static buffers of a decode step (the token, its embedding, the rope row of its position, the output and the eos
+    flags), the ``DecodeCursor`` and ONE recorded graph of a whole step: feed -> the blocks on their state caches -> the head ->
+    the cursor's sampler.  The graph is recorded on first use, on the states as the first prompt left them, and serves every later
+    prompt, prompt length, ``max_returned_tokens <= max_len`` and seed: what differs between them sits in device memory.
+    ``temperature``, ``top_k`` and ``eos_id`` are recorded by value.  Takes what ``generate`` takes, except a first-order
+    ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, and ``head.fused = False``, whose sampler
+    reads torch's generator on the host.
+
+    ``captures``: graphs recorded so far (1 after the first call); ``replays``: graph launches so far, one per generated token
+    after each call's first; ``poll``: with ``eos_id``, ``done`` is read back every ``poll`` replays instead of every token."""
+
+    poll = 16
+
+    def __init__(self, wte: torch.Tensor, blocks, head: NextTokenHead, states, *, cos, sin, max_len: int, temperature: float = 1.0,
+                 top_k=None, eos_id=None) -> None:
+        from .decode import FastmaxDecodeState
+        _check_sampling(temperature, top_k)
+        self._layers, self._run = _layers_and_run(blocks, states)
+        if not len(states):
+            raise ValueError("GraphedDecoder: no blocks")
+        for s in states:
+            if isinstance(s, FastmaxDecodeState) and s.p != 2:
+                raise NotImplementedError("GraphedDecoder: a first-order FastmaxDecodeState passes its token count to the step kernel "
+                                          "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
+                                          "LinearmaxDecodeState")
+        if not head.fused:
+            raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator, whose state a recorded graph "
+                             "does not advance; the graphed route needs the HIP sampler")
+        if wte.dim() != 2 or wte.dtype not in ops._DT:
+            raise ValueError(f"GraphedDecoder: wte should be (rows, C) in float32, bfloat16 or float16, got {tuple(wte.shape)} {wte.dtype}")
+        if cos.dim() != 2 or cos.shape != sin.shape or cos.dtype != sin.dtype or cos.dtype not in ops._DT:
+            raise ValueError(f"GraphedDecoder: cos and sin should be one (rows, n) shape and dtype, got {tuple(cos.shape)}, {tuple(sin.shape)}")
+        if max_len < 2 or cos.shape[0] < max_len - 1:
+            raise ValueError(f"GraphedDecoder: max_len ({max_len}) should be >= 2 and the rope cache ({cos.shape[0]} rows) hold "
+                             f"max_len - 1 positions")
+        _need_device(wte, "GraphedDecoder")
+        self.given = dict(wte=wte, blocks=blocks, head=head, states=states, cos=cos, sin=sin)
+        self.wte, self.head, self.states = _unit_rows(wte.detach()), head, list(states)
+        self.cos, self.sin = cos.contiguous(), sin.contiguous()
+        self.max_len, self.temperature, self.top_k, self.eos_id = int(max_len), float(temperature), top_k, eos_id
+        dev, B, C = wte.device, states[0].B, wte.shape[1]
+        self.B = B
+        self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.x = torch.zeros((B, C), dtype=wte.dtype, device=dev)
+        self.cos_row, self.sin_row = (torch.zeros((1, cos.shape[1]), dtype=cos.dtype, device=dev) for _ in range(2))
+        self.out = torch.zeros((B, self.max_len), dtype=torch.int64, device=dev)
+        self.done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self._pos = torch.zeros(1, dtype=torch.int64, device=dev)          # the blocks never read input_pos on a state cache
+        self.cursor = DecodeCursor(dev)
+        self._graph, self._stream = None, None
+        self.captures = self.replays = 0
+
+    def _step(self) -> None:
+        B, C = self.x.shape
+        self.cursor.feed(self.tok, self.wte, self.x, self.cos, self.sin, self.cos_row, self.sin_row)
+        h = self._run(self._layers, self.x.view(B, 1, C), self.cos_row, self.sin_row, self._pos, self.states)
+        self.cursor.sample(self.head.logits(h), self.tok, self.out, self.done, self.eos_id, self.temperature, self.top_k)
+
+    def _capture(self) -> None:
+        """Record ``_step`` on the states as they are (non-empty: the blocks pick the single-token route from ``count > 0``).
+        Two eager steps on a side stream first, so that every lazy initialisation of the step's own shapes happens outside the
+        recording; then the recording on that same stream, one straight chain.  The warm-up advances the states and the recording
+        the host's counts: both are put back."""
+        dev = self.tok.device
+        saved = [(s.state.clone(), s.count) for s in self.states]
+        self.tok.zero_()
+        self.cursor.arm(0, 0, 0)
+        self._stream = torch.cuda.Stream(device=dev)
+        self._stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self._stream):
+            for _ in range(2):
+                self._step()
+        self._stream.synchronize()
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph, stream=self._stream):
+            self._step()
+        torch.cuda.current_stream(dev).wait_stream(self._stream)
+        for s, (state, count) in zip(self.states, saved):
+            s.state.copy_(state)
+            s.count = count
+        self.captures += 1
+
+    @torch.no_grad()
+    def generate(self, prompt: torch.Tensor, max_returned_tokens: int, sampler: Sampler = None) -> torch.Tensor:
+        """``generate(...)`` of the module, token for token: prompt (B, T) int64 -> (B, n), the prompt included.  The prompt and the
+        first draw run eagerly, every further token is one replay.  Afterwards every ``state.count`` and ``sampler.draws`` are what
+        the eager loop leaves; with ``eos_id`` the state caches themselves may have run up to ``poll - 1`` tokens past that."""
+        B, T = _check_prompt(prompt, max_returned_tokens, self.cos, self.sin)
+        if B != self.B or max_returned_tokens > self.max_len:
+            raise ValueError(f"GraphedDecoder: built for batch {self.B} and max_len {self.max_len}, got batch {B} and "
+                             f"max_returned_tokens {max_returned_tokens}")
+        if not self.head.fused:
+            raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator; the graphed route needs the HIP sampler")
+        _need_device(prompt, "GraphedDecoder.generate")
+        sampler = Sampler() if sampler is None else sampler
+        eos = self.eos_id
+        pos = torch.arange(T, device=prompt.device)
+        h = self._run(self._layers, F.embedding(prompt, self.wte), self.cos[:T], self.sin[:T], pos, self.states)
+        first_draw = sampler.draws
+        token = self.head(h, sampler, self.temperature, self.top_k)
+        if self._graph is None:
+            self._capture()
+        self.out[:, :T] = prompt
+        self.out[:, T] = token
+        self.tok.copy_(token)
+        if eos is None:
+            self.done.zero_()
+        else:
+            self.done.copy_(token == eos)
+        self.cursor.arm(T, first_draw + 1, sampler.seed)
+        steps, ran = max_returned_tokens - T - 1, 0
+        finished = eos is not None and bool(self.done.all())
+        while ran < steps and not finished:
+            k = steps - ran if eos is None else min(max(1, int(self.poll)), steps - ran)
+            for _ in range(k):
+                self._graph.replay()
+            ran += k
+            self.replays += k
+            finished = eos is not None and bool(self.done.all())
+        n = T + 1 + ran
+        if eos is not None:
+            if self.cursor.read()["overflow"]:
+                raise RuntimeError("GraphedDecoder: the decode cursor reports an overflow (a position outside the rope cache or a "
+                                   "token outside the embedding table)")
+            # what the eager loop returns: the first length at which every row has produced eos_id
+            every = (self.out[:, T:n] == eos).to(torch.uint8).cummax(dim=1).values.all(dim=0)
+            at = torch.nonzero(every).flatten()[:1].tolist()
+            if at:
+                n = T + 1 + at[0]
+        for s in self.states:
+            s.count = n - 1                                                # the tokens the eager loop has fed
+        sampler.draws = first_draw + n - T
+        return self.out[:, :n].clone()
+
+    def serves(self, wte, blocks, head, states, cos, sin, temperature, top_k, eos_id) -> bool:
+        """whether ``generate(...)`` with these arguments is the loop this decoder recorded"""
+        g = self.given
+        same = (wte is g["wte"] and blocks is g["blocks"] and head is g["head"] and cos is g["cos"] and sin is g["sin"]
+                and len(states) == len(self.states) and all(a is b for a, b in zip(states, self.states)))
+        return same and float(temperature) == self.temperature and top_k == self.top_k and eos_id == self.eos_id
+
+
+@torch.no_grad()
+def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: torch.Tensor, max_returned_tokens: int, *, cos, sin,
+             temperature: float = 1.0, top_k=None, eos_id=None, sampler: Sampler = None, graphed: GraphedDecoder = None) -> torch.Tensor:
+    """prompt (B, T) int64 -> (B, n) tokens, the prompt included, n <= max_returned_tokens.
+
+    ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block`` (a ``NeoXStack`` or a sequence of
+    ``NeoXBlock`` for the parallel-residual form; one kind per call), ``states`` one EMPTY decode state
+    cache per block (``FastmaxDecodeState(p=2)`` / ``LinearmaxDecodeState``), ``cos`` / ``sin`` the rope cache with a row for
+    every position fed.  The prompt goes through the blocks in one call, then one token per call with the rope rows of its
+    position.  Nothing is read back per token unless ``eos_id`` is given; then the loop ends once every row has produced it.
+    ``graphed``: a ``GraphedDecoder`` built from these same arguments runs the loop as one graph replay per token; the default is
+    the loop below."""
+    if graphed is not None:
+        if not graphed.serves(wte, blocks, head, states, cos, sin, temperature, top_k, eos_id):
+            raise ValueError("generate: graphed was built from other tensors, blocks, states or sampling settings than this call's")
+        return graphed.generate(prompt, max_returned_tokens, sampler)
+    B, T = _check_prompt(prompt, max_returned_tokens, cos, sin)
+    _check_sampling(temperature, top_k)
+    layers, run = _layers_and_run(blocks, states)
     sampler = Sampler() if sampler is None else sampler
     dev = prompt.device
     pos = torch.arange(max_returned_tokens, device=dev)
