@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
 header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
-NeoX block's (NEOX_HEADER) the table NEOX_ABI and the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, set on the same handle.
+NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI and top-p sampling's
+(NUCLEUS_HEADER) the table NUCLEUS_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -165,6 +166,16 @@ CURSOR_ABI = {
     "fastmax_hip_cursor_feed": (ci, [vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, vp, vp, i64, i64, vp, vp, ci, ci, vp]),
     "fastmax_hip_sample_cursor": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, vp]),
 }
+# top-p (nucleus) sampling's side header (the filter behind the top-k in the sampler of the next-token head and of the decode
+# cursor, and the mask that exposes its kept set): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
+# tests/test_nucleus_cpu.py checks each row against the prototype.
+NUCLEUS_HEADER = "fastmax_hip_nucleus.h"
+NUCLEUS_MAX_V = 1 << 22                         # the largest V the fixed-point mass admits
+NUCLEUS_ABI = {
+    "fastmax_hip_sample_nucleus": (ci, [vp, i64, vp, ci, ci, ci, cf, cf, i64, i64, vp]),
+    "fastmax_hip_nucleus_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
+    "fastmax_hip_sample_cursor_nucleus": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
+}
 
 _lib = None
 
@@ -178,7 +189,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

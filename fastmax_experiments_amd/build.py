@@ -17,7 +17,8 @@ SOURCES = ["fastmax_api.hip", "fastmax_generic.hip", "fastmax_normalize.hip", "f
 # csrc's own headers, then the public ones (relative to csrc, like the sources)
 HEADERS = (["fastmax_common.h", "fastmax_mfma_common.h", "fastmax_mfma32_common.h", "fastmax_decode_p2_step.h", "row_kernels.h", "next_token_sample.h"] +
            [os.path.join("..", "..", "include", h)
-            for h in _lib.HEADERS + (_lib.OPTIM_HEADER, _lib.NEXT_TOKEN_HEADER, _lib.NEOX_HEADER, _lib.CURSOR_HEADER)])
+            for h in _lib.HEADERS + (_lib.OPTIM_HEADER, _lib.NEXT_TOKEN_HEADER, _lib.NEOX_HEADER, _lib.CURSOR_HEADER,
+                                   _lib.NUCLEUS_HEADER)])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc"]
 # per-source flags.  The p=2 tile kernels interleave their per-score vector work with MFMAs: packed-f32 instructions
 # (v_pk_fma_f32 / v_pk_add_f32, which the SLP vectoriser forms from adjacent scalar operations) cost 3-4x their issue slot

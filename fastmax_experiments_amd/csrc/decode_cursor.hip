@@ -8,11 +8,13 @@
 //                        writes `next`, and no workgroup reads it.
 //   sample_kernel<CursorDraw>   next_token_sample.h with the stream's key and draw number read from the cursor.  Every workgroup
 //                        reads `next`, `draw_base` and `seed`; thread 0 of each stores its token, and pos = next (the same value
-//                        from every workgroup).  No workgroup reads `pos`.
+//                        from every workgroup).  No workgroup reads `pos`.  sample_kernel<Nucleus<CursorDraw>> is the same with
+//                        the top-p filter behind the top-k (include/fastmax_hip_nucleus.h).
 // `overflow` is only ever written, with 1.  All stores are plain vector stores.
 #include "fastmax_common.h"
 #include "next_token_sample.h"
 #include "../../include/fastmax_hip_cursor.h"
+#include "../../include/fastmax_hip_nucleus.h"
 
 namespace fastmax {
 
@@ -75,6 +77,7 @@ __global__ __launch_bounds__(FEED_THREADS) void cursor_feed_kernel(FeedArgs a) {
 
 // the stream from the cursor; the token also goes to column `next` of out, the eos flag to done, and the cursor moves on
 struct CursorDraw {
+    static constexpr bool nucleus = false;
     int64_t* cursor;
     int64_t* out;
     int64_t ldo, L;
@@ -159,6 +162,20 @@ int fastmax_hip_sample_cursor(const float* logits, int64_t ld, void* cursor, int
     const CursorDraw from{reinterpret_cast<int64_t*>(cursor), out, ldo, L, reinterpret_cast<unsigned char*>(done), eos_id};
     hipLaunchKernelGGL(sample_kernel<CursorDraw>, dim3((unsigned)B), dim3(SEL_THREADS), 0, reinterpret_cast<hipStream_t>(stream), logits, ld,
                        tok, V, top_k, temperature, from);
+    return (int)hipGetLastError();
+}
+
+int fastmax_hip_sample_cursor_nucleus(const float* logits, int64_t ld, void* cursor, int64_t* tok, int64_t* out, int64_t ldo, int64_t L,
+                                      void* done, int64_t eos_id, int B, int V, int top_k, float temperature, float top_p,
+                                      void* stream) {
+    if (!logits || !cursor || !tok || !out || (eos_id >= 0 && !done)) return FASTMAX_E_NULL;
+    if (B <= 0 || V <= 0 || V > NUCLEUS_MAX_V || L <= 0 || ld < V || ldo < L || top_k < 0 ||
+        !(temperature >= 0.f && temperature <= 3.4028234e38f) || !nucleus_share(top_p))
+        return FASTMAX_E_BAD_SHAPE;
+    if (!aligned_to(logits, 4) || !aligned_to(cursor, 8) || !aligned_to(tok, 8) || !aligned_to(out, 8)) return FASTMAX_E_ALIGNMENT;
+    const Nucleus<CursorDraw> from{{reinterpret_cast<int64_t*>(cursor), out, ldo, L, reinterpret_cast<unsigned char*>(done), eos_id}, top_p};
+    hipLaunchKernelGGL(sample_kernel<Nucleus<CursorDraw>>, dim3((unsigned)B), dim3(SEL_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                       logits, ld, tok, V, top_k, temperature, from);
     return (int)hipGetLastError();
 }
 

@@ -5,7 +5,9 @@ The last stretch of the reference's loop (generate/base.py:30-47 after lit_gpt/m
 token.  Here (csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, bound by ``_lib.NEXT_TOKEN_ABI``):
     last_logits    the head over the LAST position only; the weight is read once for up to 8 rows
     Sampler        exact top-k (ties: the lowest indices are kept) and a draw from softmax(logits / temperature) as the argmax of
-                   logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device
+                   logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device.
+                   ``top_p`` adds the nucleus filter behind the top-k, inside the same kernel (include/fastmax_hip_nucleus.h,
+                   ``_lib.NUCLEUS_ABI``): the shortest prefix of the kept entries, largest first, whose softmax mass reaches top_p
     NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler
     generate       prompt -> tokens through decoder blocks (``Block`` or ``NeoXBlock``) on their decode state caches
     DecodeCursor, GraphedDecoder   the same loop as ONE graph replay per token: position, draw number and output column live in a
@@ -62,11 +64,19 @@ def last_logits(x: torch.Tensor, weight: torch.Tensor, dtype=torch.float32) -> t
     return out
 
 
-def _check_sampling(temperature, top_k):
+def _check_sampling(temperature, top_k, top_p=None):
     if not (temperature >= 0.0) or temperature == float("inf"):
         raise ValueError(f"temperature should be a finite number >= 0, got {temperature}")
     if top_k is not None and (int(top_k) != top_k or top_k < 1):
         raise ValueError(f"top_k should be None or an integer >= 1, got {top_k}")
+    if top_p is not None and not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p should be None or a number in (0, 1], got {top_p}")
+
+
+def _nucleus(top_p):
+    """the top_p the nucleus entry points receive, or None where there is no nucleus filter (None or 1.0): those calls go to
+    the entry points without one and keep their bits"""
+    return None if top_p is None or float(top_p) == 1.0 else float(top_p)
 
 
 def _logit_rows(logits: torch.Tensor, what: str) -> torch.Tensor:
@@ -88,37 +98,60 @@ class Sampler:
         self.seed = int(seed) & _MASK64
         self.draws = 0
 
-    def sample(self, logits: torch.Tensor, temperature: float = 1.0, top_k=None) -> torch.Tensor:
-        """logits (B, V) -> (B,) int64 tokens on the device; nothing is read back.  ``temperature == 0`` is the argmax."""
-        _check_sampling(temperature, top_k)
+    def sample(self, logits: torch.Tensor, temperature: float = 1.0, top_k=None, top_p=None) -> torch.Tensor:
+        """logits (B, V) -> (B,) int64 tokens on the device; nothing is read back.  ``temperature == 0`` is the argmax (and
+        ``top_p`` is ignored).  ``top_p`` in (0, 1): after temperature and top-k, only the smallest set of the largest entries
+        whose softmax mass reaches top_p is drawn from (at least one); None or 1.0: no such filter."""
+        _check_sampling(temperature, top_k, top_p)
         rows = _logit_rows(logits, "Sampler.sample")
         B, V = rows.shape
         tokens = torch.empty(B, dtype=torch.int64, device=rows.device)
-        ops._call("fastmax_hip_sample", rows.device,
-                  (rows.data_ptr(), rows.stride(0), tokens.data_ptr(), B, V, 0 if top_k is None else min(int(top_k), V),
-                   float(temperature), _signed64(self.seed), _signed64(self.draws)))
+        k, p = 0 if top_k is None else min(int(top_k), V), _nucleus(top_p)
+        if p is None:
+            ops._call("fastmax_hip_sample", rows.device,
+                      (rows.data_ptr(), rows.stride(0), tokens.data_ptr(), B, V, k, float(temperature), _signed64(self.seed),
+                       _signed64(self.draws)))
+        else:
+            ops._call("fastmax_hip_sample_nucleus", rows.device,
+                      (rows.data_ptr(), rows.stride(0), tokens.data_ptr(), B, V, k, p, float(temperature), _signed64(self.seed),
+                       _signed64(self.draws)))
         self.draws += 1
         return tokens
 
-    def keep_mask(self, logits: torch.Tensor, top_k) -> torch.Tensor:
-        """bool (B, V): the entries ``sample`` would choose among.  Exactly ``top_k`` per row (all of them for None or
-        ``top_k >= V``): those above the k-th largest value and, of those equal to it, the lowest indices."""
-        _check_sampling(0.0, top_k)
+    def keep_mask(self, logits: torch.Tensor, top_k, top_p=None, temperature: float = 1.0) -> torch.Tensor:
+        """bool (B, V): the entries ``sample`` would choose among.  Without ``top_p`` exactly ``top_k`` per row (all of them for
+        None or ``top_k >= V``): those above the k-th largest value and, of those equal to it, the lowest indices.  With ``top_p``
+        the nucleus of those at ``temperature``: a prefix of them, largest first, lowest index first among equals."""
+        _check_sampling(temperature, top_k, top_p)
         rows = _logit_rows(logits, "Sampler.keep_mask")
         B, V = rows.shape
         mask = torch.empty((B, V), dtype=torch.uint8, device=rows.device)
-        ops._call("fastmax_hip_topk_mask", rows.device,
-                  (rows.data_ptr(), rows.stride(0), mask.data_ptr(), mask.stride(0), B, V, 0 if top_k is None else min(int(top_k), V)))
+        k, p = 0 if top_k is None else min(int(top_k), V), _nucleus(top_p)
+        if p is None:
+            ops._call("fastmax_hip_topk_mask", rows.device, (rows.data_ptr(), rows.stride(0), mask.data_ptr(), mask.stride(0), B, V, k))
+        else:
+            ops._call("fastmax_hip_nucleus_mask", rows.device,
+                      (rows.data_ptr(), rows.stride(0), mask.data_ptr(), mask.stride(0), B, V, k, p, float(temperature)))
         return mask.bool()
 
 
-def _sample_tensor_ops(logits: torch.Tensor, temperature: float, top_k) -> torch.Tensor:
-    """generate/base.py:30-41 for a batch of rows, drawing from torch's generator"""
+def _nucleus_keep(probs: torch.Tensor, top_p: float) -> torch.Tensor:
+    """bool like probs: largest first (a stable sort: the lowest index first among equals), an entry stays while the mass
+    before it is < top_p"""
+    p, order = torch.sort(probs, dim=-1, descending=True, stable=True)
+    return torch.zeros_like(probs, dtype=torch.bool).scatter_(-1, order, p.cumsum(-1) - p < top_p)
+
+
+def _sample_tensor_ops(logits: torch.Tensor, temperature: float, top_k, top_p=None) -> torch.Tensor:
+    """generate/base.py:30-41 for a batch of rows, drawing from torch's generator; top-p as upstream lit-gpt applies it, after
+    temperature and top-k"""
     if top_k is not None:
         v, i = torch.topk(logits, min(int(top_k), logits.size(-1)))
         logits = torch.full_like(logits, float("-inf")).scatter_(-1, i, v)
     if temperature > 0.0:
         probs = torch.softmax(logits / temperature, dim=-1)
+        if _nucleus(top_p) is not None:
+            probs = probs * _nucleus_keep(probs, float(top_p))
         return torch.multinomial(probs, num_samples=1).squeeze(-1)
     return torch.argmax(logits, dim=-1)
 
@@ -159,13 +192,13 @@ class NextTokenHead(nn.Module):
             _, n, _ = rms_norm_forward(last, None, self.ln_f.weight.detach(), self.ln_f.eps, self.ln_f.add_unit_offset)
         return last_logits(n, self.lm_head.weight.detach()[:self.vocab_size], dtype)
 
-    def forward(self, x: torch.Tensor, sampler: Sampler, temperature: float = 1.0, top_k=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, sampler: Sampler, temperature: float = 1.0, top_k=None, top_p=None) -> torch.Tensor:
         """-> (B,) int64 tokens"""
-        _check_sampling(temperature, top_k)
+        _check_sampling(temperature, top_k, top_p)
         logits = self.logits(x)
         if not self.fused:
-            return _sample_tensor_ops(logits, temperature, top_k)
-        return sampler.sample(logits, temperature, top_k)
+            return _sample_tensor_ops(logits, temperature, top_k, top_p)
+        return sampler.sample(logits, temperature, top_k, top_p)
 
 
 def _check_prompt(prompt, max_returned_tokens, cos, sin):
@@ -237,10 +270,10 @@ class DecodeCursor:
                    wte.shape[1], ops._DT[wte.dtype], cos.data_ptr(), sin.data_ptr(), cos.stride(0), cos.shape[0], cos_row.data_ptr(),
                    sin_row.data_ptr(), n, ops._DT[cos.dtype]))
 
-    def sample(self, logits, tok, out, done=None, eos_id=None, temperature: float = 1.0, top_k=None) -> None:
+    def sample(self, logits, tok, out, done=None, eos_id=None, temperature: float = 1.0, top_k=None, top_p=None) -> None:
         """``Sampler(seed).sample`` at the cursor's draw number: the tokens go to tok (B,) and to column ``next`` of out (B, L)
         int64, ``token == eos_id`` is ORed into done (B,) uint8, and the cursor moves on by one."""
-        _check_sampling(temperature, top_k)
+        _check_sampling(temperature, top_k, top_p)
         rows = _logit_rows(logits, "DecodeCursor.sample")
         B, V = rows.shape
         if tuple(tok.shape) != (B,) or tok.dtype != torch.int64 or not tok.is_contiguous():
@@ -249,10 +282,14 @@ class DecodeCursor:
             raise ValueError(f"DecodeCursor.sample: out should be ({B}, L) int64, got {tuple(out.shape)} {out.dtype}")
         if eos_id is not None and (done is None or tuple(done.shape) != (B,) or done.dtype != torch.uint8 or not done.is_contiguous()):
             raise ValueError(f"DecodeCursor.sample: eos_id needs done ({B},) uint8")
-        ops._call("fastmax_hip_sample_cursor", rows.device,
-                  (rows.data_ptr(), rows.stride(0), self.words.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0), out.shape[1],
-                   ops._ptr(done), -1 if eos_id is None else int(eos_id), B, V, 0 if top_k is None else min(int(top_k), V),
-                   float(temperature)))
+        args = (rows.data_ptr(), rows.stride(0), self.words.data_ptr(), tok.data_ptr(), out.data_ptr(), out.stride(0), out.shape[1],
+                ops._ptr(done), -1 if eos_id is None else int(eos_id), B, V, 0 if top_k is None else min(int(top_k), V),
+                float(temperature))
+        p = _nucleus(top_p)
+        if p is None:
+            ops._call("fastmax_hip_sample_cursor", rows.device, args)
+        else:
+            ops._call("fastmax_hip_sample_cursor_nucleus", rows.device, args + (p,))
 
 
 class GraphedDecoder:
@@ -262,7 +299,7 @@ class GraphedDecoder:
     flags), the ``DecodeCursor`` and ONE recorded graph of a whole step: feed -> the blocks on their state caches -> the head ->
     the cursor's sampler.  The graph is recorded on first use, on the states as the first prompt left them, and serves every later
     prompt, prompt length, ``max_returned_tokens <= max_len`` and seed: what differs between them sits in device memory.
-    ``temperature``, ``top_k`` and ``eos_id`` are recorded by value.  Takes what ``generate`` takes, except a first-order
+    ``temperature``, ``top_k``, ``top_p`` and ``eos_id`` are recorded by value.  Takes what ``generate`` takes, except a first-order
     ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, and ``head.fused = False``, whose sampler
     reads torch's generator on the host.
 
@@ -272,9 +309,9 @@ class GraphedDecoder:
     poll = 16
 
     def __init__(self, wte: torch.Tensor, blocks, head: NextTokenHead, states, *, cos, sin, max_len: int, temperature: float = 1.0,
-                 top_k=None, eos_id=None) -> None:
+                 top_k=None, eos_id=None, top_p=None) -> None:
         from .decode import FastmaxDecodeState
-        _check_sampling(temperature, top_k)
+        _check_sampling(temperature, top_k, top_p)
         self._layers, self._run = _layers_and_run(blocks, states)
         if not len(states):
             raise ValueError("GraphedDecoder: no blocks")
@@ -298,6 +335,7 @@ class GraphedDecoder:
         self.wte, self.head, self.states = _unit_rows(wte.detach()), head, list(states)
         self.cos, self.sin = cos.contiguous(), sin.contiguous()
         self.max_len, self.temperature, self.top_k, self.eos_id = int(max_len), float(temperature), top_k, eos_id
+        self.top_p = _nucleus(top_p)
         dev, B, C = wte.device, states[0].B, wte.shape[1]
         self.B = B
         self.tok = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -314,7 +352,7 @@ class GraphedDecoder:
         B, C = self.x.shape
         self.cursor.feed(self.tok, self.wte, self.x, self.cos, self.sin, self.cos_row, self.sin_row)
         h = self._run(self._layers, self.x.view(B, 1, C), self.cos_row, self.sin_row, self._pos, self.states)
-        self.cursor.sample(self.head.logits(h), self.tok, self.out, self.done, self.eos_id, self.temperature, self.top_k)
+        self.cursor.sample(self.head.logits(h), self.tok, self.out, self.done, self.eos_id, self.temperature, self.top_k, self.top_p)
 
     def _capture(self) -> None:
         """Record ``_step`` on the states as they are (non-empty: the blocks pick the single-token route from ``count > 0``).
@@ -357,7 +395,7 @@ class GraphedDecoder:
         pos = torch.arange(T, device=prompt.device)
         h = self._run(self._layers, F.embedding(prompt, self.wte), self.cos[:T], self.sin[:T], pos, self.states)
         first_draw = sampler.draws
-        token = self.head(h, sampler, self.temperature, self.top_k)
+        token = self.head(h, sampler, self.temperature, self.top_k, self.top_p)
         if self._graph is None:
             self._capture()
         self.out[:, :T] = prompt
@@ -392,17 +430,19 @@ class GraphedDecoder:
         sampler.draws = first_draw + n - T
         return self.out[:, :n].clone()
 
-    def serves(self, wte, blocks, head, states, cos, sin, temperature, top_k, eos_id) -> bool:
+    def serves(self, wte, blocks, head, states, cos, sin, temperature, top_k, eos_id, top_p=None) -> bool:
         """whether ``generate(...)`` with these arguments is the loop this decoder recorded"""
         g = self.given
         same = (wte is g["wte"] and blocks is g["blocks"] and head is g["head"] and cos is g["cos"] and sin is g["sin"]
                 and len(states) == len(self.states) and all(a is b for a, b in zip(states, self.states)))
-        return same and float(temperature) == self.temperature and top_k == self.top_k and eos_id == self.eos_id
+        return (same and float(temperature) == self.temperature and top_k == self.top_k and eos_id == self.eos_id
+                and _nucleus(top_p) == self.top_p)
 
 
 @torch.no_grad()
 def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: torch.Tensor, max_returned_tokens: int, *, cos, sin,
-             temperature: float = 1.0, top_k=None, eos_id=None, sampler: Sampler = None, graphed: GraphedDecoder = None) -> torch.Tensor:
+             temperature: float = 1.0, top_k=None, eos_id=None, sampler: Sampler = None, graphed: GraphedDecoder = None,
+             top_p=None) -> torch.Tensor:
     """prompt (B, T) int64 -> (B, n) tokens, the prompt included, n <= max_returned_tokens.
 
     ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block`` (a ``NeoXStack`` or a sequence of
@@ -411,13 +451,13 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     every position fed.  The prompt goes through the blocks in one call, then one token per call with the rope rows of its
     position.  Nothing is read back per token unless ``eos_id`` is given; then the loop ends once every row has produced it.
     ``graphed``: a ``GraphedDecoder`` built from these same arguments runs the loop as one graph replay per token; the default is
-    the loop below."""
+    the loop below.  ``top_p``: nucleus sampling behind the top-k (``Sampler.sample``)."""
     if graphed is not None:
-        if not graphed.serves(wte, blocks, head, states, cos, sin, temperature, top_k, eos_id):
+        if not graphed.serves(wte, blocks, head, states, cos, sin, temperature, top_k, eos_id, top_p):
             raise ValueError("generate: graphed was built from other tensors, blocks, states or sampling settings than this call's")
         return graphed.generate(prompt, max_returned_tokens, sampler)
     B, T = _check_prompt(prompt, max_returned_tokens, cos, sin)
-    _check_sampling(temperature, top_k)
+    _check_sampling(temperature, top_k, top_p)
     layers, run = _layers_and_run(blocks, states)
     sampler = Sampler() if sampler is None else sampler
     dev = prompt.device
@@ -427,7 +467,7 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     h = run(layers, F.embedding(prompt, wte), cos[:T], sin[:T], pos[:T], states)
     n, done = T, None
     while True:
-        token = head(h, sampler, temperature, top_k)
+        token = head(h, sampler, temperature, top_k, top_p)
         out[:, n] = token
         n += 1
         if eos_id is not None:

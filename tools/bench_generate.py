@@ -2,7 +2,7 @@
 """Wall time per generated token on an MI355X: the eager loop of generate() against GraphedDecoder (one graph replay per token).
 
     python tools/bench_generate.py [--prompt 128] [--new 128] [--reps 5] [--cases tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m]
-                                   [--llama-blocks 32] [--out profiles/r15_graphed_generate.md]
+                                   [--llama-blocks 32] [--top-p 0.9] [--out profiles/r15_graphed_generate.md]
 
 Shapes: tiny-llama-1.1b (22 blocks) and Llama-2-7b-hf (--llama-blocks of its 32) as BlockStack, pythia-70m as a 6-block NeoXStack;
 bf16, NF4 base, LoRA on q and v; batch 1 and 8; both decode state caches.  The blocks of a stack are copies of one randomly
@@ -12,7 +12,10 @@ What is timed: a host clock around a whole generate() call that ends in a device
 prompt and the first draw, which both loops run the same eager way) and once for prompt + new; per token = the difference over
 new - 1.  A round times both lengths of both arms, eager then graphed; `--reps` rounds in one process; the table gives each arm's
 median and its spread (lowest .. highest).  The graph is recorded, and both arms are run once, before the first round.  Both
-arms draw under the same seed and the tool stops if their tokens differ.  No time here is a pass criterion."""
+arms draw under the same seed and the tool stops if their tokens differ.  No time here is a pass criterion.
+
+`--top-p P` adds a third arm, the graphed loop with nucleus sampling behind the top-k (a second GraphedDecoder and its own states),
+timed in the same rounds; its tokens are checked against the eager loop's under the same top_p once, before the rounds."""
 import argparse
 import copy
 import os
@@ -27,6 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 VOCAB = {"tiny-llama-1.1b": 32000, "Llama-2-7b-hf": 32000, "pythia-70m": 50304}
 HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
           "whole call, eager | graphed |\n|---|---|---|---|---|---|---|---|---|")
+TOP_P_HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
+                "whole call, eager | graphed | graphed with top_p, per token | with / without top_p |\n|---|---|---|---|---|---|---|---|---|---|---|")
 
 
 def make_stack(config, n, alg):
@@ -90,9 +95,25 @@ def case(config, stack, alg, B, args):
         return decoder.generate(prompt, n, Sampler(7))
 
     arms = {"eager": eager, "graphed": graphed}
+    if args.top_p is not None:
+        p_states = make_states(config, alg, B, n_blocks)
+        p_decoder = GraphedDecoder(wte, stack, head, p_states, max_len=total, top_p=args.top_p, **kw)
+
+        def graphed_top_p(n):
+            for s in p_states:
+                s.reset()
+            return p_decoder.generate(prompt, n, Sampler(7))
+
+        arms["graphed top_p"] = graphed_top_p
     first = {k: fn(total) for k, fn in arms.items()}                      # warm-up of every shape; the capture
     if not torch.equal(first["eager"], first["graphed"]):
         raise SystemExit(f"{config} {alg} B={B}: the graphed tokens differ from the eager loop's")
+    if args.top_p is not None:
+        for s in eager_states:
+            s.reset()
+        if not torch.equal(first["graphed top_p"], generate(wte, stack, head, eager_states, prompt, total, sampler=Sampler(7),
+                                                            top_p=args.top_p, **kw)):
+            raise SystemExit(f"{config} {alg} B={B}: the graphed tokens with top_p differ from the eager loop's")
     per_token = {k: [] for k in arms}
     whole = {k: [] for k in arms}
     for _ in range(args.reps):
@@ -105,8 +126,12 @@ def case(config, stack, alg, B, args):
             whole[k].append(long)
     assert decoder.captures == 1
     ratio = statistics.median(per_token["eager"]) / statistics.median(per_token["graphed"])
-    return (f"| {config} | {n_blocks} | {alg} | {B} | {fmt(per_token['eager'])} | {fmt(per_token['graphed'])} | {ratio:.2f}x | "
+    line = (f"| {config} | {n_blocks} | {alg} | {B} | {fmt(per_token['eager'])} | {fmt(per_token['graphed'])} | {ratio:.2f}x | "
             f"{statistics.median(whole['eager']):.1f} ms | {statistics.median(whole['graphed']):.1f} ms |")
+    if args.top_p is not None:
+        with_p = statistics.median(per_token["graphed top_p"]) / statistics.median(per_token["graphed"])
+        line += f" {fmt(per_token['graphed top_p'])} | {with_p:.3f}x |"
+    return line
 
 
 def main():
@@ -117,6 +142,7 @@ def main():
     ap.add_argument("--cases", default="tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m")
     ap.add_argument("--llama-blocks", type=int, default=32)
     ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--top-p", type=float, default=None, help="also time the graphed loop with this top_p behind the top-k")
     ap.add_argument("--out", default=None, help="also write the table to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -124,7 +150,8 @@ def main():
     if args.new < 2:
         raise SystemExit("--new should be at least 2: the first token is not a decode step")
     n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6}
-    lines = [f"{args.new} tokens after a {args.prompt}-token prompt, bf16, NF4 base; {args.reps} rounds, the arms alternating.\n", HEADER]
+    lines = [f"{args.new} tokens after a {args.prompt}-token prompt, bf16, NF4 base; {args.reps} rounds, the arms alternating.\n",
+             HEADER if args.top_p is None else TOP_P_HEADER]
     print("\n".join(lines), flush=True)
     for config in args.cases.split(","):
         for alg in ("fastmax", "linearmax"):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the next-token head on an MI355X: norm + last-row logits + sample in HIP beside the tensor-op route.
 
-    python tools/bench_next_token.py [--iters 50] [--rounds 5] [--out profiles/r12_next_token.md]
+    python tools/bench_next_token.py [--iters 50] [--rounds 5] [--tables head,sampler] [--top-p 0.9] [--out profiles/r12_next_token.md]
 
 Sizes (n_embd, vocab): TinyLlama (2048, 32000), Llama-2-7B (4096, 32000), pythia-14m (128, 50304), each at B = 1 and 8, bf16,
 top_k 200, temperature 0.8, on the hidden state of ONE new token, (B, 1, C).
@@ -10,7 +10,12 @@ top_k 200, temperature 0.8, on the hidden state of ONE new token, (B, 1, C).
 The two routes alternate round by round in one process; per route the median and the spread of the rounds are printed.  Every
 call takes the next of several heads whose weights together exceed 512 MiB, so that no call finds its weight in the 256 MiB
 last-level cache.  Then each kernel alone the same way, with the logits pass's bytes V * C * e over its time beside the 8 TB/s
-peak.  Times are device events around `--iters` calls after a warm-up; no time here is a pass criterion."""
+peak.  Times are device events around `--iters` calls after a warm-up; no time here is a pass criterion.
+
+The sampler table (top-p): the sampler alone on float32 logits (B, V) drawn once (normal, standard deviation 3), V = 32000 and
+50304, B = 1 and 8, top_k None and 200, temperature 0.8.  Four arms alternate round by round: the top-k-only sampler kernel, the
+same kernel with the nucleus filter (`--top-p`), and the tensor-op restatement (`_sample_tensor_ops`: topk + scatter_ + softmax
+[+ sort + cumsum] + multinomial) without and with top-p."""
 import argparse
 import os
 import statistics
@@ -82,6 +87,31 @@ def case(config, B, args):
     return lines
 
 
+def sampler_case(V, B, top_k, args):
+    from fastmax_experiments_amd.generate import Sampler, _sample_tensor_ops
+    logits = (torch.randn(B, V, generator=torch.Generator().manual_seed(V + B)) * 3).cuda()
+    sampler, p = Sampler(77), args.top_p
+    arms = {
+        "top-k": lambda i: sampler.sample(logits, TEMPERATURE, top_k),
+        "top-k + top-p": lambda i: sampler.sample(logits, TEMPERATURE, top_k, top_p=p),
+        "tensor-op": lambda i: _sample_tensor_ops(logits, TEMPERATURE, top_k),
+        "tensor-op + top-p": lambda i: _sample_tensor_ops(logits, TEMPERATURE, top_k, p),
+    }
+    times = {k: [] for k in arms}
+    for _ in range(args.rounds):
+        for k, fn in arms.items():
+            times[k].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    kept = sampler.keep_mask(logits, top_k, top_p=p, temperature=TEMPERATURE).sum(1)
+    cells = " | ".join(f"{med[k]:.1f} ({min(times[k]):.1f} .. {max(times[k]):.1f})" for k in arms)
+    return (f"| {V} | {B} | {top_k} | {cells} | {med['top-k + top-p'] - med['top-k']:+.1f} | "
+            f"{med['top-k + top-p'] / med['top-k']:.2f}x | {med['tensor-op + top-p'] / med['top-k + top-p']:.1f}x | "
+            f"{int(kept.min())} .. {int(kept.max())} |")
+
+
+SAMPLER_HEADER = """| V | B | top_k | top-k kernel µs / call (rounds) | top-k + top-p kernel | tensor-op top-k | tensor-op top-k + top-p | nucleus costs µs | kernel, with / without | tensor-op / kernel, with top-p | kept per row |
+|---|---|---|---|---|---|---|---|---|---|---|"""
+
 HEADER = """| config | B | fused µs / token (rounds) | tensor-op µs / token (rounds) | tensor-op / fused | norm µs | logits µs | sample µs | weight MB | logits TB/s | of 8 TB/s |
 |---|---|---|---|---|---|---|---|---|---|---|"""
 
@@ -90,21 +120,34 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--tables", default="head,sampler", help="which tables to measure: head, sampler or both")
+    ap.add_argument("--top-p", type=float, default=0.9, help="the sampler table's top_p")
+    ap.add_argument("--out", default=None, help="also write the tables to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_next_token.py measures on an MI355X; there is no device here")
-    rows = []
-    for config in SIZES:
-        for B in (1, 8):
-            rows += case(config, B, args)
-            print(rows[-1], flush=True)
-    table = "\n".join([HEADER] + rows)
-    print(table)
+    tables = []
+    if "head" in args.tables.split(","):
+        rows = []
+        for config in SIZES:
+            for B in (1, 8):
+                rows += case(config, B, args)
+                print(rows[-1], flush=True)
+        tables.append(f"bf16, top_k {TOP_K}, temperature {TEMPERATURE}, {args.iters} calls per round, {args.rounds} rounds, median "
+                      "(min .. max)\n\n" + "\n".join([HEADER] + rows))
+    if "sampler" in args.tables.split(","):
+        rows = []
+        for V in (32000, 50304):
+            for B in (1, 8):
+                for top_k in (None, TOP_K):
+                    rows.append(sampler_case(V, B, top_k, args))
+                    print(rows[-1], flush=True)
+        tables.append(f"the sampler alone, float32 logits, temperature {TEMPERATURE}, top_p {args.top_p}, {args.iters} calls per round, "
+                      f"{args.rounds} rounds, the four arms alternating, median (min .. max)\n\n" + "\n".join([SAMPLER_HEADER] + rows))
+    print("\n\n".join(tables))
     if args.out:
         with open(args.out, "w") as f:
-            f.write(f"bf16, top_k {TOP_K}, temperature {TEMPERATURE}, {args.iters} calls per round, {args.rounds} rounds, median "
-                    f"(min .. max)\n\n{table}\n")
+            f.write("\n\n".join(tables) + "\n")
 
 
 if __name__ == "__main__":
