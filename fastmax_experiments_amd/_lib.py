@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
 header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
-NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI and top-p sampling's
-(NUCLEUS_HEADER) the table NUCLEUS_ABI, set on the same handle.
+NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, top-p sampling's
+(NUCLEUS_HEADER) the table NUCLEUS_ABI and the mixture-of-experts MLP's (MOE_HEADER) the table MOE_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -176,6 +176,20 @@ NUCLEUS_ABI = {
     "fastmax_hip_nucleus_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
     "fastmax_hip_sample_cursor_nucleus": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
 }
+# the mixture-of-experts MLP's side header (top-k routing with the stable dispatch, gather, combine and their backward passes):
+# same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_moe_cpu.py checks each row against
+# the prototype.
+MOE_HEADER = "fastmax_hip_moe.h"
+MOE_MAX_EXPERTS, MOE_MAX_PER_TOKEN = 64, 8      # FASTMAX_MOE_MAX_EXPERTS, FASTMAX_MOE_MAX_PER_TOKEN
+MOE_ABI = {
+    "fastmax_hip_moe_route_workspace": (sz, [ci, ci]),
+    "fastmax_hip_moe_route": (ci, [vp, i64, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+    "fastmax_hip_moe_gather": (ci, [vp, i64, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_moe_combine": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_moe_combine_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, ci, ci, ci, ci, vp]),
+    "fastmax_hip_moe_gather_backward": (ci, [vp, i64, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_moe_route_backward": (ci, [vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -189,7 +203,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

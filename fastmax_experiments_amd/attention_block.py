@@ -174,4 +174,5 @@ CONFIG_SHAPES = {
     "pythia-1b": dict(n_embd=2048, n_head=8, n_query_groups=8, head_size=256, rotary_percentage=0.25, bias=True),
     "Gemma-2b": dict(n_embd=2048, n_head=8, n_query_groups=1, head_size=256, rotary_percentage=1.0, bias=False),   # config.py:796-811 (multi-query)
     "pythia-70m": dict(n_embd=512, n_head=8, n_query_groups=8, head_size=64, rotary_percentage=0.25, bias=True),   # config.py:216-225, defaults 30-91
+    "Mixtral-8x7B-v0.1": dict(n_embd=4096, n_head=32, n_query_groups=8, head_size=128, rotary_percentage=1.0, bias=False),   # config.py:1344-1362
 }

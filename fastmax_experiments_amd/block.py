@@ -5,6 +5,7 @@ The reference's ``Block.forward`` (lit_gpt/model.py:340-361), sequential-residua
     x = mlp(norm_2(x)) + x
 with ``RMSNorm`` (lit_gpt/rmsnorm.py:20-31) and ``LLaMAMLP`` / ``GemmaMLP`` (model.py:622-641, LoRA wiring lora.py:661-709).
 ``CausalSelfAttention`` is attention_block.py's; the three MLP linears are ``LoRALinear`` (NF4 base after ``quantize_base``).
+``mlp_class="LLaMAMoE"`` puts moe.py's mixture of ``LLaMAMLP`` experts in the MLP's place.
 What this file adds runs in csrc/block_neighbours.hip (C ABI: include/fastmax_hip_block.h, bound by ``_lib.ABI``):
     rms_norm / rms_norm_add    the norm, optionally with the residual add in front of it as ONE pass that also writes the sum
     gated_act                  act(fc_1(x)) * fc_2(x), forward and a one-pass backward that recomputes act
@@ -27,7 +28,10 @@ from .lora import LoRALinear
 # GptNeoxMLP there, which Block refuses and neox_block.NeoXBlock builds; here their widths also serve tests and the step with
 # RMSNorm and the gated MLP
 CONFIG_INTERMEDIATE = {"pythia-14m": 512, "tiny-llama-1.1b": 5632, "Llama-2-7b-hf": 11008, "pythia-1b": 8192, "Gemma-2b": 16384,
-                       "pythia-70m": 2048}
+                       "pythia-70m": 2048, "Mixtral-8x7B-v0.1": 14336}
+# what the mixture-of-experts configs add to Block's arguments (config.py:1344-1362); kept out of CONFIG_SHAPES, whose entries
+# are CausalSelfAttention's arguments
+CONFIG_MOE = {"Mixtral-8x7B-v0.1": dict(mlp_class="LLaMAMoE", n_expert=8, n_expert_per_token=2)}
 
 _ACT = {"silu": _lib.ACT_SILU, "gelu": _lib.ACT_GELU}
 
@@ -279,6 +283,7 @@ class DecoderBlock(nn.Module):
     @classmethod
     def from_config(cls, config: str, **kw):
         """a block at the head and MLP shapes of a CONFIG_SHAPES entry"""
+        kw = {**CONFIG_MOE.get(config, {}), **kw}
         return cls(intermediate_size=kw.pop("intermediate_size", CONFIG_INTERMEDIATE[config]), **CONFIG_SHAPES[config], **kw)
 
     @property
@@ -308,7 +313,7 @@ class Block(DecoderBlock):
                  mlp_class="LLaMAMLP", norm_class="RMSNorm", parallel_residual: bool = False, shared_attention_norm: bool = False,
                  attn_alg: str = "fastmax", r: int = 8, alpha: int = 16, dropout: float = 0.0, to_query: bool = True,
                  to_key: bool = False, to_value: bool = True, to_projection: bool = False, to_mlp: bool = False,
-                 add_unit_offset: bool = False) -> None:
+                 add_unit_offset: bool = False, n_expert: int = 0, n_expert_per_token: int = 0) -> None:
         super().__init__()
         if parallel_residual:
             raise NotImplementedError("Block: parallel_residual=True (x = mlp(norm_2(x)) + attn(norm_1(x)) + x, the pythia form) "
@@ -320,9 +325,9 @@ class Block(DecoderBlock):
         if norm_name != "RMSNorm":
             raise NotImplementedError(f"Block: norm class {norm_name} is not built; only RMSNorm has kernels (LayerNorm is missing)")
         mlp_name = mlp_class if isinstance(mlp_class, str) else getattr(mlp_class, "__name__", str(mlp_class))
-        if mlp_name not in _MLP_CLASSES:
-            raise NotImplementedError(f"Block: MLP class {mlp_name} is not built; only LLaMAMLP and GemmaMLP (gated) are "
-                                      "(GptNeoxMLP and LLaMAMoE are missing)")
+        if mlp_name not in _MLP_CLASSES and mlp_name != "LLaMAMoE":
+            raise NotImplementedError(f"Block: MLP class {mlp_name} is not built; only LLaMAMLP, GemmaMLP (gated) and LLaMAMoE "
+                                      "are (GptNeoxMLP is neox_block.NeoXBlock's)")
         if intermediate_size is None:
             raise ValueError("Block needs intermediate_size")
         self.norm_1 = RMSNorm(n_embd, eps=norm_eps, add_unit_offset=add_unit_offset)
@@ -330,7 +335,12 @@ class Block(DecoderBlock):
                                         rotary_percentage=rotary_percentage, attn_alg=attn_alg, r=r, alpha=alpha, dropout=dropout,
                                         to_query=to_query, to_key=to_key, to_value=to_value, to_projection=to_projection)
         self.norm_2 = RMSNorm(n_embd, eps=norm_eps, add_unit_offset=add_unit_offset)
-        self.mlp = _MLP_CLASSES[mlp_name](n_embd, intermediate_size, bias=bias, r=r, alpha=alpha, dropout=dropout, to_mlp=to_mlp)
+        mlp_kw = dict(bias=bias, r=r, alpha=alpha, dropout=dropout, to_mlp=to_mlp)
+        if mlp_name == "LLaMAMoE":
+            from .moe import LLaMAMoE                                # moe.py builds its experts from this file's LLaMAMLP
+            self.mlp = LLaMAMoE(n_embd, intermediate_size, n_expert, n_expert_per_token, **mlp_kw)
+        else:
+            self.mlp = _MLP_CLASSES[mlp_name](n_embd, intermediate_size, **mlp_kw)
         self._fused = True
 
     def run_open(self, x, n_1, cos, sin, input_pos=None, state=None):

@@ -300,8 +300,8 @@ class GraphedDecoder:
     the cursor's sampler.  The graph is recorded on first use, on the states as the first prompt left them, and serves every later
     prompt, prompt length, ``max_returned_tokens <= max_len`` and seed: what differs between them sits in device memory.
     ``temperature``, ``top_k``, ``top_p`` and ``eos_id`` are recorded by value.  Takes what ``generate`` takes, except a first-order
-    ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, and ``head.fused = False``, whose sampler
-    reads torch's generator on the host.
+    ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, blocks whose MLP is a ``moe.LLaMAMoE``, which
+    reads its experts' row counts back in every layer, and ``head.fused = False``, whose sampler reads torch's generator on the host.
 
     ``captures``: graphs recorded so far (1 after the first call); ``replays``: graph launches so far, one per generated token
     after each call's first; ``poll``: with ``eos_id``, ``done`` is read back every ``poll`` replays instead of every token."""
@@ -320,6 +320,10 @@ class GraphedDecoder:
                 raise NotImplementedError("GraphedDecoder: a first-order FastmaxDecodeState passes its token count to the step kernel "
                                           "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
                                           "LinearmaxDecodeState")
+        from .moe import LLaMAMoE
+        if any(isinstance(getattr(b, "mlp", None), LLaMAMoE) for b in self._layers):
+            raise NotImplementedError("GraphedDecoder: an LLaMAMoE reads its experts' row counts back from the device in every "
+                                      "layer, which a recorded graph cannot do; generate() runs these blocks eagerly")
         if not head.fused:
             raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator, whose state a recorded graph "
                              "does not advance; the graphed route needs the HIP sampler")
