@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
 header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
 NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, top-p sampling's
-(NUCLEUS_HEADER) the table NUCLEUS_ABI and the mixture-of-experts MLP's (MOE_HEADER) the table MOE_ABI, set on the same handle.
+(NUCLEUS_HEADER) the table NUCLEUS_ABI, the mixture-of-experts MLP's (MOE_HEADER) the table MOE_ABI and its decode-size expert
+kernels' (MOE_DECODE_HEADER) the table MOE_DECODE_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -190,6 +191,16 @@ MOE_ABI = {
     "fastmax_hip_moe_gather_backward": (ci, [vp, i64, vp, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_moe_route_backward": (ci, [vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
 }
+# the decode-size expert kernels' side header (the experts' gated MLPs at M <= 16 tokens on the route kernel's device-side row
+# counts, their NF4 operands from a device table): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
+# tests/test_moe_decode_cpu.py checks each row against the prototype.
+MOE_DECODE_HEADER = "fastmax_hip_moe_decode.h"
+MOE_DECODE_MAX_ROWS = 16                        # FASTMAX_MOE_DECODE_MAX_ROWS
+MOE_DECODE_ABI = {
+    "fastmax_hip_moe_expert_entry_bytes": (sz, []),
+    "fastmax_hip_moe_experts_up": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_moe_experts_down": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -203,7 +214,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI, MOE_DECODE_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

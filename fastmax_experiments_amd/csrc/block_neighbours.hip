@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_scalar_kernel(NormBwd p) {
 
 // ---- gated activation ---------------------------------------------------------------------------------------------------
 template <int ACT> __device__ __forceinline__ float act_f(float a) {
-    if constexpr (ACT == FASTMAX_ACT_SILU) return a / (1.0f + expf(-a));
+    if constexpr (ACT == FASTMAX_ACT_SILU) return silu_f(a);
     else return gelu_f(a);
 }
 template <int ACT> __device__ __forceinline__ float act_prime(float a) {

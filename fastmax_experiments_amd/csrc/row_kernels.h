@@ -95,7 +95,8 @@ static inline void launch_partial_row_sum(const float* part, PartialSums<NS> out
     hipLaunchKernelGGL(partial_row_sum_kernel<NS>, dim3((unsigned)((C + 63) / 64), (unsigned)NS), dim3(256), 0, st, part, out, nblk, C);
 }
 
-// exact GELU a (1 + erf(a / sqrt 2)) / 2 and its derivative
+// SiLU a / (1 + exp(-a)); exact GELU a (1 + erf(a / sqrt 2)) / 2 and its derivative
+__device__ __forceinline__ float silu_f(float a) { return a / (1.0f + expf(-a)); }
 __device__ __forceinline__ float gelu_f(float a) { return 0.5f * a * (1.0f + erff(a * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_prime(float a) {
     return 0.5f * (1.0f + erff(a * 0.70710678118654752440f)) + a * expf(-0.5f * a * a) * 0.39894228040143267794f;

@@ -300,8 +300,11 @@ class GraphedDecoder:
     the cursor's sampler.  The graph is recorded on first use, on the states as the first prompt left them, and serves every later
     prompt, prompt length, ``max_returned_tokens <= max_len`` and seed: what differs between them sits in device memory.
     ``temperature``, ``top_k``, ``top_p`` and ``eos_id`` are recorded by value.  Takes what ``generate`` takes, except a first-order
-    ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, blocks whose MLP is a ``moe.LLaMAMoE``, which
-    reads its experts' row counts back in every layer, and ``head.fused = False``, whose sampler reads torch's generator on the host.
+    ``FastmaxDecodeState``, whose step receives the token count as a kernel argument, blocks whose MLP is a ``moe.LLaMAMoE`` that
+    would read its experts' row counts back in every layer, and ``head.fused = False``, whose sampler reads torch's generator on
+    the host.  An ``LLaMAMoE`` is taken with ``device_routed`` set on every one of them (quantized experts) and a batch of at most
+    16 in bfloat16 or float32: its decode step then runs on device-side row counts; the two eager warm-up steps before the
+    recording build each layer's expert table, which cannot be built inside it.  The prompt (B T > 16 rows) runs on the eager route.
 
     ``captures``: graphs recorded so far (1 after the first call); ``replays``: graph launches so far, one per generated token
     after each call's first; ``poll``: with ``eos_id``, ``done`` is read back every ``poll`` replays instead of every token."""
@@ -321,9 +324,15 @@ class GraphedDecoder:
                                           "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
                                           "LinearmaxDecodeState")
         from .moe import LLaMAMoE
-        if any(isinstance(getattr(b, "mlp", None), LLaMAMoE) for b in self._layers):
+        moes = [b.mlp for b in self._layers if isinstance(getattr(b, "mlp", None), LLaMAMoE)]
+        if moes and not all(m.device_routed and m.fused_neighbours for m in moes):
             raise NotImplementedError("GraphedDecoder: an LLaMAMoE reads its experts' row counts back from the device in every "
-                                      "layer, which a recorded graph cannot do; generate() runs these blocks eagerly")
+                                      "layer, which a recorded graph cannot do; generate() runs these blocks eagerly; set "
+                                      "`mlp.device_routed = True` on quantized experts")
+        if moes and (states[0].B > _lib.MOE_DECODE_MAX_ROWS or wte.dtype not in (torch.bfloat16, torch.float32)):
+            raise NotImplementedError(f"GraphedDecoder: a device-routed LLaMAMoE takes at most {_lib.MOE_DECODE_MAX_ROWS} rows in "
+                                      f"bfloat16 or float32 without reading its experts' row counts back, got batch {states[0].B} "
+                                      f"in {wte.dtype}")
         if not head.fused:
             raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator, whose state a recorded graph "
                              "does not advance; the graphed route needs the HIP sampler")

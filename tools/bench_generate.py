@@ -3,10 +3,13 @@
 
     python tools/bench_generate.py [--prompt 128] [--new 128] [--reps 5] [--cases tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m]
                                    [--llama-blocks 32] [--top-p 0.9] [--out profiles/r15_graphed_generate.md]
+    python tools/bench_generate.py --cases Mixtral-8x7B-v0.1 [--mixtral-blocks 4] [--algs fastmax]
 
 Shapes: tiny-llama-1.1b (22 blocks) and Llama-2-7b-hf (--llama-blocks of its 32) as BlockStack, pythia-70m as a 6-block NeoXStack;
 bf16, NF4 base, LoRA on q and v; batch 1 and 8; both decode state caches.  The blocks of a stack are copies of one randomly
-initialised block: the times do not depend on the values.
+initialised block: the times do not depend on the values.  Mixtral-8x7B-v0.1 (--mixtral-blocks of its 32) is a BlockStack
+whose MLPs are ``moe.LLaMAMoE``: its eager arm runs with ``device_routed`` off (the route that reads the experts' row counts back
+per layer), its graphed arm needs it on, and a third arm is the eager loop with it on.
 
 What is timed: a host clock around a whole generate() call that ends in a device synchronise, once for prompt + 1 tokens (the
 prompt and the first draw, which both loops run the same eager way) and once for prompt + new; per token = the difference over
@@ -27,14 +30,40 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-VOCAB = {"tiny-llama-1.1b": 32000, "Llama-2-7b-hf": 32000, "pythia-70m": 50304}
+MIXTRAL = "Mixtral-8x7B-v0.1"
+VOCAB = {"tiny-llama-1.1b": 32000, "Llama-2-7b-hf": 32000, "pythia-70m": 50304, MIXTRAL: 32000}
 HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
           "whole call, eager | graphed |\n|---|---|---|---|---|---|---|---|---|")
 TOP_P_HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
                 "whole call, eager | graphed | graphed with top_p, per token | with / without top_p |\n|---|---|---|---|---|---|---|---|---|---|---|")
 
 
+MOE_HEADER = ("| config | blocks | decode cache | batch | eager (device_routed off), per token: median (lowest .. highest) | graphed | "
+              "eager / graphed | whole call, eager | graphed | eager with device_routed on, per token | eager off / on |\n"
+              "|---|---|---|---|---|---|---|---|---|---|---|")
+
+
+def make_mixtral_stack(n, alg):
+    """a block at the Mixtral width made on the device, expert by expert, quantized as it is made (the dense weights of all
+    experts never coexist); n copies"""
+    from fastmax_experiments_amd.block import CONFIG_MOE, Block, BlockStack, LLaMAMLP
+    torch.manual_seed(0)
+    E, k = CONFIG_MOE[MIXTRAL]["n_expert"], CONFIG_MOE[MIXTRAL]["n_expert_per_token"]
+    with torch.device("cuda"):
+        blk = Block.from_config(MIXTRAL, attn_alg=alg, n_expert=1, n_expert_per_token=1).to(torch.bfloat16).quantize_base()
+        torch.nn.init.normal_(blk.attn.attn.lora_B, std=0.02)
+        mlp = blk.mlp
+        experts = list(mlp.experts)
+        for _ in range(E - 1):
+            experts.append(LLaMAMLP(mlp.n_embd, mlp.intermediate_size).to(torch.bfloat16).quantize_base())
+        mlp.gate = type(mlp.gate)(mlp.n_embd, E, bias=False).to(torch.bfloat16)
+    mlp.experts, mlp.n_expert, mlp.n_expert_per_token = torch.nn.ModuleList(experts), E, k
+    return BlockStack([copy.deepcopy(blk).eval() for _ in range(n)])
+
+
 def make_stack(config, n, alg):
+    if config == MIXTRAL:
+        return make_mixtral_stack(n, alg)
     from fastmax_experiments_amd.block import Block, BlockStack
     from fastmax_experiments_amd.neox_block import NeoXBlock, NeoXStack
     neox = config.startswith("pythia")
@@ -73,7 +102,13 @@ def fmt(v, unit="ms"):
 def case(config, stack, alg, B, args):
     from fastmax_experiments_amd.attention_block import CONFIG_SHAPES, build_rope_cache
     from fastmax_experiments_amd.generate import GraphedDecoder, NextTokenHead, Sampler, generate
+    from fastmax_experiments_amd.moe import LLaMAMoE
     C, V = CONFIG_SHAPES[config]["n_embd"], VOCAB[config]
+    moes = [b.mlp for b in stack.blocks if isinstance(getattr(b, "mlp", None), LLaMAMoE)]
+
+    def routed(on):
+        for m in moes:
+            m.device_routed = on
     T, total, n_blocks = args.prompt, args.prompt + args.new, len(stack.blocks)
     torch.manual_seed(1)
     head = NextTokenHead(C, V, norm_class="LayerNorm" if config.startswith("pythia") else "RMSNorm").to("cuda").to(torch.bfloat16).eval()
@@ -82,19 +117,24 @@ def case(config, stack, alg, B, args):
     prompt = torch.randint(0, V, (B, T), generator=torch.Generator().manual_seed(2)).cuda()
     kw = dict(cos=cos, sin=sin, temperature=0.8, top_k=200)
     eager_states, states = make_states(config, alg, B, n_blocks), make_states(config, alg, B, n_blocks)
+    routed(True)
     decoder = GraphedDecoder(wte, stack, head, states, max_len=total, **kw)
 
-    def eager(n):
+    def eager(n, on=False):
+        routed(on)
         for s in eager_states:
             s.reset()
         return generate(wte, stack, head, eager_states, prompt, n, sampler=Sampler(7), **kw)
 
     def graphed(n):
+        routed(True)
         for s in states:
             s.reset()
         return decoder.generate(prompt, n, Sampler(7))
 
     arms = {"eager": eager, "graphed": graphed}
+    if moes:
+        arms["eager routed"] = lambda n: eager(n, True)
     if args.top_p is not None:
         p_states = make_states(config, alg, B, n_blocks)
         p_decoder = GraphedDecoder(wte, stack, head, p_states, max_len=total, top_p=args.top_p, **kw)
@@ -108,6 +148,8 @@ def case(config, stack, alg, B, args):
     first = {k: fn(total) for k, fn in arms.items()}                      # warm-up of every shape; the capture
     if not torch.equal(first["eager"], first["graphed"]):
         raise SystemExit(f"{config} {alg} B={B}: the graphed tokens differ from the eager loop's")
+    if moes and not torch.equal(first["eager"], first["eager routed"]):
+        raise SystemExit(f"{config} {alg} B={B}: the eager tokens with device_routed on differ from those with it off")
     if args.top_p is not None:
         for s in eager_states:
             s.reset()
@@ -131,6 +173,9 @@ def case(config, stack, alg, B, args):
     if args.top_p is not None:
         with_p = statistics.median(per_token["graphed top_p"]) / statistics.median(per_token["graphed"])
         line += f" {fmt(per_token['graphed top_p'])} | {with_p:.3f}x |"
+    if moes:
+        off_on = statistics.median(per_token["eager"]) / statistics.median(per_token["eager routed"])
+        line += f" {fmt(per_token['eager routed'])} | {off_on:.2f}x |"
     return line
 
 
@@ -141,6 +186,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cases", default="tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m")
     ap.add_argument("--llama-blocks", type=int, default=32)
+    ap.add_argument("--mixtral-blocks", type=int, default=4)
+    ap.add_argument("--algs", default="fastmax,linearmax")
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--top-p", type=float, default=None, help="also time the graphed loop with this top_p behind the top-k")
     ap.add_argument("--out", default=None, help="also write the table to this file")
@@ -149,12 +196,17 @@ def main():
         raise SystemExit("bench_generate.py needs an MI355X")
     if args.new < 2:
         raise SystemExit("--new should be at least 2: the first token is not a decode step")
-    n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6}
+    if args.top_p is not None and MIXTRAL in args.cases.split(","):
+        raise SystemExit("--top-p and the Mixtral case are timed in separate runs: each adds its own arm and columns")
+    n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6, MIXTRAL: args.mixtral_blocks}
     lines = [f"{args.new} tokens after a {args.prompt}-token prompt, bf16, NF4 base; {args.reps} rounds, the arms alternating.\n",
              HEADER if args.top_p is None else TOP_P_HEADER]
     print("\n".join(lines), flush=True)
     for config in args.cases.split(","):
-        for alg in ("fastmax", "linearmax"):
+        if config == MIXTRAL:
+            lines += ["", MOE_HEADER]
+            print("\n".join(lines[-2:]), flush=True)
+        for alg in args.algs.split(","):
             stack = make_stack(config, n_blocks[config], alg)
             for B in (int(b) for b in args.batches.split(",")):
                 lines.append(case(config, stack, alg, B, args))

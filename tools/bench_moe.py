@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Time the mixture-of-experts MLP (fastmax_experiments_amd/moe.py) from the router to the combine on an MI355X, routing kernels
-on against off (``fused_neighbours``), on the same commit in the same process.
+on against off (``fused_neighbours``), and at decode sizes the device-routed expert kernels (``device_routed``) beside both, on
+the same commit in the same process.
 
     python tools/bench_moe.py [--iters 10] [--reps 3] [--n-embd 4096 --intermediate 14336 --experts 8 --per-token 2]
 
 The default is the Mixtral-8x7B width in bf16 with the experts' linears in NF4.  Sizes: 4096 tokens forward + backward (the gate
-is the trainable part: the NF4 experts are frozen), and 1 and 8 tokens forward (decode).  Per size and arm the table gives
+is the trainable part: the NF4 experts are frozen), and 1, 8 and 16 tokens forward (decode), where the arm "device" is
+``device_routed = True``: gate, route, experts_up, experts_down, combine.  Per size and arm the table gives
   * device kernels per call, counted by torch.profiler over ONE call in a pass of its own (never inside a timed window);
   * host reads per call: ``moe._read_offsets`` calls on the fused route, ``torch.where`` calls on the tensor-op route;
   * ms per call: device events around `--iters` calls after a warm-up at the same size, the two arms alternating `--reps` times;
     median (lowest .. highest).
-The experts' matrix products run in both arms and take most of the time at 4096 tokens; no time here is a pass criterion."""
+The experts' matrix products run in every arm and take most of the time at 4096 tokens; no time here is a pass criterion.
+A second table times experts_up + experts_down ALONE on the routing of the same rows and sets the NF4 code and scale bytes of
+the experts that have rows (each read once by the pair) against that time."""
 import argparse
 import os
 import statistics
@@ -95,9 +99,14 @@ def main():
     moe = build(args.n_embd, args.intermediate, args.experts, args.per_token)
     print(f"LLaMAMoE n_embd {args.n_embd}, intermediate {args.intermediate}, {args.experts} experts, {args.per_token} per token, "
           "bf16, experts NF4\n")
-    print("| tokens | pass | arm | device kernels | host reads | ms per call, median (lowest .. highest) | off / on |\n|---|---|---|---|---|---|---|",
+    print("| tokens | pass | arm | device kernels | host reads | ms per call, median (lowest .. highest) | off / arm |\n|---|---|---|---|---|---|---|",
           flush=True)
-    for tokens, train in ((4096, True), (8, False), (1, False)):
+
+    def select(arm):
+        moe.fused_neighbours = arm != "off"
+        moe.device_routed = arm == "device"
+
+    for tokens, train in ((4096, True), (16, False), (8, False), (1, False)):
         x = torch.randn(1, tokens, args.n_embd, device="cuda").to(torch.bfloat16)
         gy = torch.randn_like(x)
 
@@ -110,19 +119,46 @@ def main():
                 with torch.no_grad():
                     moe(x)
 
-        ms, kernels, reads = {True: [], False: []}, {}, {}
-        for on in (True, False):
-            moe.fused_neighbours = on
-            reads[on] = count_reads(call)
-            kernels[on] = "not counted" if args.no_kernel_count else count_kernels(call)
+        arms = ("on", "off") if train else ("on", "off", "device")
+        ms, kernels, reads = {a: [] for a in arms}, {}, {}
+        for arm in arms:
+            select(arm)
+            reads[arm] = count_reads(call)
+            kernels[arm] = "not counted" if args.no_kernel_count else count_kernels(call)
         for _ in range(args.reps):
-            for on in (True, False):
-                moe.fused_neighbours = on
-                ms[on].append(timed(call, args.iters))
-        ratio = statistics.median(ms[False]) / statistics.median(ms[True])
-        for on in (True, False):
-            print(f"| {tokens} | {'forward + backward' if train else 'forward'} | {'on' if on else 'off'} | {kernels[on]} | {reads[on]} | "
-                  f"{fmt(ms[on])} | {f'{ratio:.2f}x' if on else ''} |", flush=True)
+            for arm in arms:
+                select(arm)
+                ms[arm].append(timed(call, args.iters))
+        select("on")
+        for arm in arms:
+            ratio = statistics.median(ms["off"]) / statistics.median(ms[arm])
+            print(f"| {tokens} | {'forward + backward' if train else 'forward'} | {arm} | {kernels[arm]} | {reads[arm]} | "
+                  f"{fmt(ms[arm])} | {'' if arm == 'off' else f'{ratio:.2f}x'} |", flush=True)
+    expert_kernels(moe, args)
+
+
+def expert_kernels(moe, args):
+    """experts_up + experts_down alone, on the routing of random rows: time, and the active experts' NF4 bytes over it"""
+    from fastmax_experiments_amd import moe as moe_mod
+    C, I, k = args.n_embd, args.intermediate, args.per_token
+    per_expert = 3 * (C * I // 2 + C * I // 64 * 4)                    # codes and float32 block scales of fc_1, fc_2, proj
+    table = moe.expert_table()
+    print("\n| tokens | experts with rows | NF4 code + scale bytes read | experts_up + experts_down, ms: median (lowest .. highest) | "
+          "GB/s |\n|---|---|---|---|---|", flush=True)
+    for tokens in (16, 8, 1):
+        x = torch.randn(tokens, C, device="cuda").to(torch.bfloat16)
+        with torch.no_grad():
+            _, _, _, offsets, row_of, _ = moe_mod.route(moe.gate(x), k)
+        bounds = offsets.tolist()
+        active = sum(1 for a, b in zip(bounds, bounds[1:]) if b > a)
+
+        def pair():
+            moe_mod.experts_down(moe_mod.experts_up(x, table, offsets, row_of, k, I), table, offsets, k, C)
+
+        ms = [timed(pair, args.iters) for _ in range(args.reps)]
+        nbytes = active * per_expert
+        print(f"| {tokens} | {active} of {args.experts} | {nbytes / 1e6:.1f} MB | {fmt(ms)} | {nbytes / statistics.median(ms) / 1e6:.0f} |",
+              flush=True)
 
 
 if __name__ == "__main__":
