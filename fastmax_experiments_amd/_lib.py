@@ -2,7 +2,8 @@
 header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
 NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, top-p sampling's
 (NUCLEUS_HEADER) the table NUCLEUS_ABI, the mixture-of-experts MLP's (MOE_HEADER) the table MOE_ABI and its decode-size expert
-kernels' (MOE_DECODE_HEADER) the table MOE_DECODE_ABI, set on the same handle.
+kernels' (MOE_DECODE_HEADER) the table MOE_DECODE_ABI and the biased / NF4 next-token head's (HEAD_HEADER) the table HEAD_ABI, set on
+the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -201,6 +202,14 @@ MOE_DECODE_ABI = {
     "fastmax_hip_moe_experts_up": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_moe_experts_down": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
 }
+# the biased / NF4-quantised next-token head's side header (the last-row logits with an lm_head bias, and on packed NF4 codes):
+# same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_nf4_head_cpu.py checks each row
+# against the prototype.
+HEAD_HEADER = "fastmax_hip_head.h"
+HEAD_ABI = {
+    "fastmax_hip_last_logits_bias": (ci, [vp, i64, vp, i64, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_last_logits_nf4": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -214,7 +223,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI, MOE_DECODE_ABI):
+    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI, MOE_DECODE_ABI, HEAD_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

@@ -8,7 +8,9 @@ token.  Here (csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, boun
                    logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device.
                    ``top_p`` adds the nucleus filter behind the top-k, inside the same kernel (include/fastmax_hip_nucleus.h,
                    ``_lib.NUCLEUS_ABI``): the shortest prefix of the kept entries, largest first, whose softmax mass reaches top_p
-    NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler
+    NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler.  ``lm_head_bias=True``
+                   and ``quantize_base()`` (``lm_head`` as NF4 codes) go through csrc/next_token_nf4.hip (include/fastmax_hip_head.h,
+                   ``_lib.HEAD_ABI``): the last-row logits with a bias, and straight from the codes
     generate       prompt -> tokens through decoder blocks (``Block`` or ``NeoXBlock``) on their decode state caches
     DecodeCursor, GraphedDecoder   the same loop as ONE graph replay per token: position, draw number and output column live in a
                    device record (csrc/decode_cursor.hip, include/fastmax_hip_cursor.h, ``_lib.CURSOR_ABI``) that the step's first
@@ -17,12 +19,15 @@ What differs from the reference: logits are float32 by default (``dtype=`` gives
 sampler's own seeded one instead of torch's generator, so a (seed, draw) pair reproduces a token on any batch.  There is no CPU
 path through the kernels; ``NextTokenHead.fused = False`` selects the tensor-op restatement for A/B runs.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
 from .block import BlockStack, RMSNorm, rms_norm_forward
+from .lora import NF4Linear, Params4bit, scales_cached, scales_of
 from .neox_block import LayerNorm, NeoXStack, layer_norm_forward
 
 _MASK64 = (1 << 64) - 1
@@ -43,24 +48,85 @@ def _unit_rows(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(1) == 1 and t.stride(0) >= 0 else t.contiguous()
 
 
-def last_logits(x: torch.Tensor, weight: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+def _head_scales(base: NF4Linear):
+    """``scales_of(base)``; building it copies nothing to the device but, for double-quantised scales, reads one scalar back, so
+    it has to exist before a stream starts capturing"""
+    if not scales_cached(base) and base.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("last_logits: the NF4 head's block scales have not been handed to the library yet, which cannot happen "
+                           "while a stream is capturing (a double-quantised offset is read back from the device); score once "
+                           "eagerly before the recording")
+    return scales_of(base)
+
+
+def _nf4_base(weight):
+    """the NF4Linear behind ``weight``: itself, or a holder kept on a bare ``Params4bit`` so that its scales are built once"""
+    if isinstance(weight, NF4Linear):
+        return weight
+    if isinstance(weight, Params4bit) and weight.quant_state is not None:
+        base = weight.__dict__.get("_head_base")
+        if base is None:
+            base = weight.__dict__["_head_base"] = _BareNF4(weight)
+        return base
+    return None
+
+
+class _BareNF4:
+    """what ``scales_of`` reads of an NF4Linear, around a ``Params4bit`` alone (held weakly: the holder lives on the parameter)"""
+
+    def __init__(self, weight):
+        self._weight = weakref.ref(weight)
+
+    @property
+    def weight(self):
+        return self._weight()
+
+
+def last_logits(x: torch.Tensor, weight, dtype=torch.float32, bias=None, rows=None) -> torch.Tensor:
     """x (B, C) with unit stride along C and any row stride (a last-position view), weight (V, C) -> logits (B, V) in ``dtype``
-    (float32 or the inputs' dtype), accumulated in float32.  A row's logits do not depend on the batch it is computed in."""
-    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or 0 in x.shape or 0 in weight.shape:
-        raise ValueError(f"last_logits: x should be (B, C) and weight (V, C), got {tuple(x.shape)} and {tuple(weight.shape)}")
-    if x.dtype != weight.dtype or x.dtype not in ops._DT:
-        raise TypeError(f"last_logits: x and weight should share float32, bfloat16 or float16, got {x.dtype} and {weight.dtype}")
+    (float32 or the inputs' dtype), accumulated in float32.  A row's logits do not depend on the batch it is computed in.
+    ``weight``: a tensor of x's dtype, or an ``NF4Linear`` (or its ``Params4bit`` with a quant state) over C inputs with
+    C % 64 == 0: the logits of its dequantised weight ``weight.dequantize(x.dtype)``, straight from the codes.  ``bias`` (>= V
+    elements of x's dtype) is added in float32 before the logits are rounded.  ``rows``: score the first ``rows`` rows of the
+    weight only (``vocab_size`` of a padded vocabulary)."""
+    base = _nf4_base(weight)
+    shape = tuple(weight.shape) if base is None else tuple(base.weight.quant_state[1])
+    if x.dim() != 2 or len(shape) != 2 or x.shape[1] != shape[1] or 0 in x.shape or 0 in shape:
+        raise ValueError(f"last_logits: x should be (B, C) and weight (V, C), got {tuple(x.shape)} and {shape}")
+    V = shape[0] if rows is None else int(rows)
+    if not 1 <= V <= shape[0]:
+        raise ValueError(f"last_logits: rows should lie in 1 .. {shape[0]}, got {rows}")
+    if x.dtype not in ops._DT or (base is None and x.dtype != weight.dtype):
+        raise TypeError(f"last_logits: x and weight should share float32, bfloat16 or float16, got {x.dtype} and "
+                        f"{'NF4 codes' if base is not None else weight.dtype}")
     if dtype not in (torch.float32, x.dtype):
         raise TypeError(f"last_logits: dtype should be float32 or {x.dtype}, got {dtype}")
+    if bias is not None and (bias.dim() != 1 or bias.shape[0] < V or bias.dtype != x.dtype or bias.device != x.device):
+        raise ValueError(f"last_logits: bias should hold {V} elements of {x.dtype} on x's device, got {tuple(bias.shape)} {bias.dtype}")
+    if base is not None and shape[1] % 64:
+        raise ValueError(f"last_logits: an NF4 weight needs C % 64 == 0 (a 64-weight block inside one row), got C = {shape[1]}")
     _need_device(x, "last_logits")
     x2 = _unit_rows(x)
-    w = weight if weight.stride(1) == 1 and weight.stride(0) >= weight.shape[1] else weight.contiguous()
     B, C = x2.shape
-    V = w.shape[0]
     out = torch.empty((B, V), dtype=dtype, device=x.device)
-    ops._call("fastmax_hip_last_logits", x.device,
-              (x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), B, V, C, ops._DT[x.dtype],
-               ops._DT[dtype]))
+    bs = None if bias is None else bias.contiguous()
+    if base is not None:
+        codes = base.weight.data
+        if codes.device != x.device:
+            raise ValueError(f"last_logits: x is on {x.device}, the NF4 codes on {codes.device}")
+        ops._call("fastmax_hip_last_logits_nf4", x.device,
+                  (x2.data_ptr(), x2.stride(0), codes.data_ptr(), _head_scales(base).ref, ops._ptr(bs), out.data_ptr(), out.stride(0),
+                   B, V, C, ops._DT[x.dtype], ops._DT[dtype]))
+        return out
+    weight = weight[:V]
+    w = weight if weight.stride(1) == 1 and weight.stride(0) >= weight.shape[1] else weight.contiguous()
+    if bs is None:
+        ops._call("fastmax_hip_last_logits", x.device,
+                  (x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0), B, V, C, ops._DT[x.dtype],
+                   ops._DT[dtype]))
+    else:
+        ops._call("fastmax_hip_last_logits_bias", x.device,
+                  (x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), bs.data_ptr(), out.data_ptr(), out.stride(0), B, V, C,
+                   ops._DT[x.dtype], ops._DT[dtype]))
     return out
 
 
@@ -159,10 +225,12 @@ def _sample_tensor_ops(logits: torch.Tensor, temperature: float, top_k, top_p=No
 class NextTokenHead(nn.Module):
     """``ln_f`` + ``lm_head`` (the reference's names, so its state-dict keys load) + the sampler.  ``vocab_size`` rows of the
     ``padded_vocab_size`` rows of the weight are scored; the default is all of them, which is what the reference samples over.
-    ``norm_class``: "RMSNorm", or "LayerNorm" (the pythia models; state-dict keys ``ln_f.weight`` and ``ln_f.bias``)."""
+    ``norm_class``: "RMSNorm", or "LayerNorm" (the pythia models; state-dict keys ``ln_f.weight`` and ``ln_f.bias``).
+    ``lm_head_bias``: the reference's ``config.lm_head_bias`` (the Phi models; state-dict key ``lm_head.bias``).
+    ``quantize_base()`` stores ``lm_head`` as NF4 codes, as the reference's quantised runs do with every linear of the model."""
 
     def __init__(self, n_embd: int, padded_vocab_size: int, vocab_size: int = None, norm_eps: float = 1e-5,
-                 add_unit_offset: bool = False, norm_class: str = "RMSNorm") -> None:
+                 add_unit_offset: bool = False, norm_class: str = "RMSNorm", lm_head_bias: bool = False) -> None:
         super().__init__()
         vocab_size = padded_vocab_size if vocab_size is None else vocab_size
         if not 1 <= vocab_size <= padded_vocab_size:
@@ -173,23 +241,56 @@ class NextTokenHead(nn.Module):
             raise ValueError("add_unit_offset belongs to RMSNorm")
         self.ln_f = (LayerNorm(n_embd, eps=norm_eps) if norm_class == "LayerNorm"
                      else RMSNorm(n_embd, eps=norm_eps, add_unit_offset=add_unit_offset))
-        self.lm_head = nn.Linear(n_embd, padded_vocab_size, bias=False)
+        self.lm_head = nn.Linear(n_embd, padded_vocab_size, bias=bool(lm_head_bias))
         self.vocab_size = vocab_size
         self.fused = True                     # False: the tensor-op restatement (whole (B, T, V) head, topk + softmax + multinomial)
+
+    def quantize_base(self, double_quant: bool = False) -> "NextTokenHead":
+        """``lm_head`` becomes an ``NF4Linear`` of the same weight (block 64; ``double_quant``: 8-bit block scales), the bias
+        stays; the state-dict keys are ``NF4Linear``'s.  Called again, nothing happens; the other scale form is refused."""
+        if isinstance(self.lm_head, NF4Linear):
+            if self.lm_head.double_quant != bool(double_quant):
+                raise ValueError(f"NextTokenHead.quantize_base: lm_head is already quantised with double_quant="
+                                 f"{self.lm_head.double_quant}")
+            return self
+        if self.lm_head.in_features % 64:
+            raise ValueError(f"NextTokenHead.quantize_base: n_embd should be a multiple of 64 (one NF4 block lies inside one row "
+                             f"of the weight), got {self.lm_head.in_features}")
+        self.lm_head = NF4Linear.from_linear(self.lm_head, double_quant=bool(double_quant))
+        return self
+
+    def _bias(self, dtype):
+        """lm_head's bias in ``dtype`` (an NF4Linear keeps it in float32), or None; the cast is kept until the bias changes"""
+        b = self.lm_head.bias
+        if b is None or b.dtype == dtype:
+            return None if b is None else b.detach()
+        key = (b.data_ptr(), b._version, dtype, b.device)
+        hit = self.__dict__.get("_bias_cast")
+        if hit is None or hit[0] != key:
+            if b.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("NextTokenHead: the bias has not been cast to the activations' dtype yet, and a copy made while "
+                                   "a stream is capturing would belong to that graph; score once eagerly before the recording")
+            hit = self.__dict__["_bias_cast"] = (key, b.detach().to(dtype))
+        return hit[1]
 
     def logits(self, x: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
         """x (B, T, C) or (B, C) -> the logits (B, vocab_size) of the last position"""
         if x.dim() not in (2, 3):
             raise ValueError(f"NextTokenHead: x should be (B, T, C) or (B, C), got {tuple(x.shape)}")
+        nf4 = isinstance(self.lm_head, NF4Linear)
         if not self.fused:
             n = self.ln_f._eager(x)
-            y = self.lm_head(n)
+            y = F.linear(n, self.lm_head.dequantize(n.dtype), self._bias(n.dtype)) if nf4 else self.lm_head(n)
             return (y[:, -1] if x.dim() == 3 else y)[:, :self.vocab_size].to(dtype)
         last = x[:, -1] if x.dim() == 3 else x
         if isinstance(self.ln_f, LayerNorm):
             _, n, _, _, _ = layer_norm_forward(last, self.ln_f.weight.detach(), self.ln_f.bias.detach(), self.ln_f.eps)
         else:
             _, n, _ = rms_norm_forward(last, None, self.ln_f.weight.detach(), self.ln_f.eps, self.ln_f.add_unit_offset)
+        if nf4:
+            return last_logits(n, self.lm_head, dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
+        if self.lm_head.bias is not None:
+            return last_logits(n, self.lm_head.weight.detach(), dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
         return last_logits(n, self.lm_head.weight.detach()[:self.vocab_size], dtype)
 
     def forward(self, x: torch.Tensor, sampler: Sampler, temperature: float = 1.0, top_k=None, top_p=None) -> torch.Tensor:

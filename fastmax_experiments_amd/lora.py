@@ -136,14 +136,23 @@ class NF4Scales:
         return self.tensors[0].device
 
 
+def _scales_key(qs):
+    return (qs[0].data_ptr(), None if qs[4] is None else (qs[4][1][0].data_ptr(), qs[4][1][1].data_ptr()))
+
+
+def scales_cached(base) -> bool:
+    """whether ``scales_of(base)`` is a lookup (True) or would rebuild the struct, which a recording stream cannot do"""
+    hit = base.__dict__.get("_scales_cache")
+    return hit is not None and hit[0] == _scales_key(base.weight.quant_state)
+
+
 def scales_of(base) -> "NF4Scales":
     """the NF4Scales of an NF4Linear, rebuilt only when its quant_state tensors changed (a double-quantised state holds its
     offset as a device scalar: reading it costs a host synchronisation, which must not happen once per forward call)"""
-    qs = base.weight.quant_state
-    key = (qs[0].data_ptr(), None if qs[4] is None else (qs[4][1][0].data_ptr(), qs[4][1][1].data_ptr()))
+    key = _scales_key(base.weight.quant_state)
     hit = base.__dict__.get("_scales_cache")
     if hit is None or hit[0] != key:
-        hit = (key, NF4Scales(qs))
+        hit = (key, NF4Scales(base.weight.quant_state))
         base.__dict__["_scales_cache"] = hit
     return hit[1]
 

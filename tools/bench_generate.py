@@ -4,6 +4,7 @@
     python tools/bench_generate.py [--prompt 128] [--new 128] [--reps 5] [--cases tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m]
                                    [--llama-blocks 32] [--top-p 0.9] [--out profiles/r15_graphed_generate.md]
     python tools/bench_generate.py --cases Mixtral-8x7B-v0.1 [--mixtral-blocks 4] [--algs fastmax]
+    python tools/bench_generate.py --nf4-head nf4 --cases tiny-llama-1.1b,Llama-2-7b-hf [--algs fastmax]
 
 Shapes: tiny-llama-1.1b (22 blocks) and Llama-2-7b-hf (--llama-blocks of its 32) as BlockStack, pythia-70m as a 6-block NeoXStack;
 bf16, NF4 base, LoRA on q and v; batch 1 and 8; both decode state caches.  The blocks of a stack are copies of one randomly
@@ -18,7 +19,11 @@ median and its spread (lowest .. highest).  The graph is recorded, and both arms
 arms draw under the same seed and the tool stops if their tokens differ.  No time here is a pass criterion.
 
 `--top-p P` adds a third arm, the graphed loop with nucleus sampling behind the top-k (a second GraphedDecoder and its own states),
-timed in the same rounds; its tokens are checked against the eager loop's under the same top_p once, before the rounds."""
+timed in the same rounds; its tokens are checked against the eager loop's under the same top_p once, before the rounds.
+
+`--nf4-head nf4|nf4-dq` adds two arms, the eager and the graphed loop under a copy of the head after ``quantize_base()`` (with
+their own states and GraphedDecoder), timed in the same rounds as the dense head's two.  The quantised head scores other weights,
+so its tokens are checked against each other (graphed against eager), not against the dense head's."""
 import argparse
 import copy
 import os
@@ -36,6 +41,11 @@ HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (
           "whole call, eager | graphed |\n|---|---|---|---|---|---|---|---|---|")
 TOP_P_HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
                 "whole call, eager | graphed | graphed with top_p, per token | with / without top_p |\n|---|---|---|---|---|---|---|---|---|---|---|")
+
+
+NF4_HEAD_HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
+                   "whole call, eager | graphed | eager, NF4 head, per token | graphed, NF4 head | dense / NF4 head, eager | graphed |\n"
+                   "|---|---|---|---|---|---|---|---|---|---|---|---|---|")
 
 
 MOE_HEADER = ("| config | blocks | decode cache | batch | eager (device_routed off), per token: median (lowest .. highest) | graphed | "
@@ -145,7 +155,25 @@ def case(config, stack, alg, B, args):
             return p_decoder.generate(prompt, n, Sampler(7))
 
         arms["graphed top_p"] = graphed_top_p
+    if args.nf4_head is not None:
+        q_head = copy.deepcopy(head).quantize_base(double_quant=args.nf4_head == "nf4-dq")
+        q_eager_states, q_states = make_states(config, alg, B, n_blocks), make_states(config, alg, B, n_blocks)
+        q_decoder = GraphedDecoder(wte, stack, q_head, q_states, max_len=total, **kw)
+
+        def eager_nf4_head(n):
+            for s in q_eager_states:
+                s.reset()
+            return generate(wte, stack, q_head, q_eager_states, prompt, n, sampler=Sampler(7), **kw)
+
+        def graphed_nf4_head(n):
+            for s in q_states:
+                s.reset()
+            return q_decoder.generate(prompt, n, Sampler(7))
+
+        arms["eager nf4 head"], arms["graphed nf4 head"] = eager_nf4_head, graphed_nf4_head
     first = {k: fn(total) for k, fn in arms.items()}                      # warm-up of every shape; the capture
+    if args.nf4_head is not None and not torch.equal(first["eager nf4 head"], first["graphed nf4 head"]):
+        raise SystemExit(f"{config} {alg} B={B}: under the NF4 head the graphed tokens differ from the eager loop's")
     if not torch.equal(first["eager"], first["graphed"]):
         raise SystemExit(f"{config} {alg} B={B}: the graphed tokens differ from the eager loop's")
     if moes and not torch.equal(first["eager"], first["eager routed"]):
@@ -173,6 +201,10 @@ def case(config, stack, alg, B, args):
     if args.top_p is not None:
         with_p = statistics.median(per_token["graphed top_p"]) / statistics.median(per_token["graphed"])
         line += f" {fmt(per_token['graphed top_p'])} | {with_p:.3f}x |"
+    if args.nf4_head is not None:
+        line += (f" {fmt(per_token['eager nf4 head'])} | {fmt(per_token['graphed nf4 head'])} | "
+                 f"{statistics.median(per_token['eager']) / statistics.median(per_token['eager nf4 head']):.3f}x | "
+                 f"{statistics.median(per_token['graphed']) / statistics.median(per_token['graphed nf4 head']):.3f}x |")
     if moes:
         off_on = statistics.median(per_token["eager"]) / statistics.median(per_token["eager routed"])
         line += f" {fmt(per_token['eager routed'])} | {off_on:.2f}x |"
@@ -190,17 +222,21 @@ def main():
     ap.add_argument("--algs", default="fastmax,linearmax")
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--top-p", type=float, default=None, help="also time the graphed loop with this top_p behind the top-k")
+    ap.add_argument("--nf4-head", choices=("nf4", "nf4-dq"), default=None,
+                    help="also time both loops under the head after quantize_base() (nf4-dq: double-quantised scales)")
     ap.add_argument("--out", default=None, help="also write the table to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_generate.py needs an MI355X")
+    if args.nf4_head is not None and (args.top_p is not None or MIXTRAL in args.cases.split(",")):
+        raise SystemExit("--nf4-head, --top-p and the Mixtral case are timed in separate runs: each adds its own arms and columns")
     if args.new < 2:
         raise SystemExit("--new should be at least 2: the first token is not a decode step")
     if args.top_p is not None and MIXTRAL in args.cases.split(","):
         raise SystemExit("--top-p and the Mixtral case are timed in separate runs: each adds its own arm and columns")
     n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6, MIXTRAL: args.mixtral_blocks}
     lines = [f"{args.new} tokens after a {args.prompt}-token prompt, bf16, NF4 base; {args.reps} rounds, the arms alternating.\n",
-             HEADER if args.top_p is None else TOP_P_HEADER]
+             NF4_HEAD_HEADER if args.nf4_head is not None else HEADER if args.top_p is None else TOP_P_HEADER]
     print("\n".join(lines), flush=True)
     for config in args.cases.split(","):
         if config == MIXTRAL:

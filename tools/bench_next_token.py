@@ -2,6 +2,7 @@
 """Time the next-token head on an MI355X: norm + last-row logits + sample in HIP beside the tensor-op route.
 
     python tools/bench_next_token.py [--iters 50] [--rounds 5] [--tables head,sampler] [--top-p 0.9] [--out profiles/r12_next_token.md]
+    python tools/bench_next_token.py --tables quantised [--out FILE]
 
 Sizes (n_embd, vocab): TinyLlama (2048, 32000), Llama-2-7B (4096, 32000), pythia-14m (128, 50304), each at B = 1 and 8, bf16,
 top_k 200, temperature 0.8, on the hidden state of ONE new token, (B, 1, C).
@@ -15,7 +16,16 @@ peak.  Times are device events around `--iters` calls after a warm-up; no time h
 The sampler table (top-p): the sampler alone on float32 logits (B, V) drawn once (normal, standard deviation 3), V = 32000 and
 50304, B = 1 and 8, top_k None and 200, temperature 0.8.  Four arms alternate round by round: the top-k-only sampler kernel, the
 same kernel with the nucleus filter (`--top-p`), and the tensor-op restatement (`_sample_tensor_ops`: topk + scatter_ + softmax
-[+ sort + cumsum] + multinomial) without and with top-p."""
+[+ sort + cumsum] + multinomial) without and with top-p.
+
+The quantised table (`--tables quantised`): ``head.logits`` (the norm kernel and the last-row logits, two launches, float32 logits)
+per call on the head shapes of pythia-70m (50304 x 512), tiny-llama-1.1b (32000 x 2048) and Llama-2-7b-hf (32000 x 4096), B = 1 and
+8, bf16, with the head dense, ``quantize_base()`` (NF4, fp32 block scales) and ``quantize_base(double_quant=True)``.  The three arms
+alternate round by round, each over copies of its head that together exceed 512 MiB.  Two times per arm: the eager call (device
+events around `--iters` calls; at these sizes the host's two launches can be the longer part), and the same `--iters` calls
+recorded once in a graph and replayed, which leaves the device's time.  Bytes per second are the weight stream's alone over the
+replayed call's time: 2 V C for the dense head, codes + scales for the quantised ones (V C / 2 + 4 V C / 64, or
+V C / 2 + V C / 64 + 4 ceil(V C / 64 / 256) + 1024 double-quantised)."""
 import argparse
 import os
 import statistics
@@ -41,6 +51,33 @@ def timed(fn, iters):
     t1.record()
     torch.cuda.synchronize()
     return t0.elapsed_time(t1) * 1e3 / iters          # microseconds
+
+
+def recorded(fn, iters):
+    """`iters` calls of fn recorded in one graph on a side stream (after an eager warm-up there) -> what one replay takes, per call"""
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for i in range(iters):
+            fn(i)
+    stream.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        for i in range(iters):
+            fn(i)
+    torch.cuda.current_stream().wait_stream(stream)
+
+    def replay():
+        graph.replay()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(4):
+            graph.replay()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) * 1e3 / (4 * iters)          # microseconds
+    return replay
 
 
 def case(config, B, args):
@@ -87,6 +124,70 @@ def case(config, B, args):
     return lines
 
 
+QUANTISED_SIZES = {"pythia-70m": (512, 50304), "tiny-llama-1.1b": (2048, 32000), "Llama-2-7b-hf": (4096, 32000)}
+
+
+def head_bytes(arm, C, V):
+    """the bytes of lm_head one call streams"""
+    blocks = V * C // 64
+    return {"dense": 2 * V * C, "nf4": V * C // 2 + 4 * blocks, "nf4-dq": V * C // 2 + blocks + 4 * -(-blocks // 256) + 1024}[arm]
+
+
+def quantised_case(config, B, args):
+    import copy
+    from fastmax_experiments_amd.generate import NextTokenHead
+    C, V = QUANTISED_SIZES[config]
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    norm = "LayerNorm" if config.startswith("pythia") else "RMSNorm"
+    dense = NextTokenHead(C, V, norm_class=norm).to(dev, torch.bfloat16).eval()
+    x = torch.randn(B, 1, C, device=dev).to(torch.bfloat16)
+    heads, nbytes = {}, {}
+    for arm, dq in (("dense", None), ("nf4", False), ("nf4-dq", True)):
+        first = copy.deepcopy(dense) if dq is None else copy.deepcopy(dense).quantize_base(dq)
+        nbytes[arm] = head_bytes(arm, C, V)
+        copies = min(64, (512 << 20) // nbytes[arm] + 2)
+        heads[arm] = [first] + [copy.deepcopy(first) for _ in range(copies - 1)]
+    with torch.no_grad():
+        ref = heads["nf4"][0].logits(x)
+        for arm in ("nf4", "nf4-dq"):                 # every copy scores once eagerly (its scales struct), and they agree
+            for h in heads[arm]:
+                got = h.logits(x)
+                if arm == "nf4" and not torch.equal(got, ref):
+                    raise SystemExit(f"{config} B={B}: two copies of the NF4 head give different logits")
+
+    def route(arm):
+        hs = heads[arm]
+
+        def fn(i):
+            with torch.no_grad():
+                hs[i % len(hs)].logits(x)
+        return fn
+
+    replays = {arm: recorded(route(arm), args.iters) for arm in heads}
+    times, device = {arm: [] for arm in heads}, {arm: [] for arm in heads}
+    for _ in range(args.rounds):
+        for arm in heads:
+            times[arm].append(timed(route(arm), args.iters))
+        for arm in heads:
+            device[arm].append(replays[arm]())
+    med = {k: statistics.median(v) for k, v in times.items()}
+    played = {k: statistics.median(v) for k, v in device.items()}
+    cells = []
+    for arm in heads:
+        tbs = nbytes[arm] / (played[arm] * 1e-6) / 1e12
+        cells.append(f"{med[arm]:.1f} ({min(times[arm]):.1f} .. {max(times[arm]):.1f}) | "
+                     f"{played[arm]:.1f} ({min(device[arm]):.1f} .. {max(device[arm]):.1f}) | {nbytes[arm] / 1e6:.1f} | {tbs:.2f}")
+    del heads, replays
+    torch.cuda.empty_cache()
+    return (f"| {config} | {V} x {C} | {B} | " + " | ".join(cells) +
+            f" | {played['dense'] / played['nf4']:.2f}x | {played['dense'] / played['nf4-dq']:.2f}x |")
+
+
+QUANTISED_HEADER = """| config | V x C | B | dense: eager µs / call (rounds) | replayed µs / call (rounds) | MB | TB/s | NF4: eager | replayed | MB | TB/s | NF4-dq: eager | replayed | MB | TB/s | replayed, dense / NF4 | dense / NF4-dq |
+|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"""
+
+
 def sampler_case(V, B, top_k, args):
     from fastmax_experiments_amd.generate import Sampler, _sample_tensor_ops
     logits = (torch.randn(B, V, generator=torch.Generator().manual_seed(V + B)) * 3).cuda()
@@ -120,7 +221,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--tables", default="head,sampler", help="which tables to measure: head, sampler or both")
+    ap.add_argument("--tables", default="head,sampler", help="which tables to measure: head, sampler, quantised")
     ap.add_argument("--top-p", type=float, default=0.9, help="the sampler table's top_p")
     ap.add_argument("--out", default=None, help="also write the tables to this file")
     args = ap.parse_args()
@@ -144,6 +245,15 @@ def main():
                     print(rows[-1], flush=True)
         tables.append(f"the sampler alone, float32 logits, temperature {TEMPERATURE}, top_p {args.top_p}, {args.iters} calls per round, "
                       f"{args.rounds} rounds, the four arms alternating, median (min .. max)\n\n" + "\n".join([SAMPLER_HEADER] + rows))
+    if "quantised" in args.tables.split(","):
+        rows = []
+        for config in QUANTISED_SIZES:
+            for B in (1, 8):
+                rows.append(quantised_case(config, B, args))
+                print(rows[-1], flush=True)
+        tables.append(f"head.logits (norm + last-row logits), bf16 in, float32 logits, {args.iters} calls per round, {args.rounds} rounds, "
+                      "the three arms alternating, median (min .. max); MB and TB/s: the weight stream alone over the replayed call's time\n\n" +
+                      "\n".join([QUANTISED_HEADER] + rows))
     print("\n\n".join(tables))
     if args.out:
         with open(args.out, "w") as f:
