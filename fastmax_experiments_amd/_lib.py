@@ -1,9 +1,4 @@
-"""ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI; the optimizer's side
-header (OPTIM_HEADER) has the table OPTIM_ABI, the next-token head's (NEXT_TOKEN_HEADER) the table NEXT_TOKEN_ABI, the
-NeoX block's (NEOX_HEADER) the table NEOX_ABI, the decode cursor's (CURSOR_HEADER) the table CURSOR_ABI, top-p sampling's
-(NUCLEUS_HEADER) the table NUCLEUS_ABI, the mixture-of-experts MLP's (MOE_HEADER) the table MOE_ABI and its decode-size expert
-kernels' (MOE_DECODE_HEADER) the table MOE_DECODE_ABI and the biased / NF4 next-token head's (HEAD_HEADER) the table HEAD_ABI, set on
-the same handle.
+"""ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI, set on one handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -46,8 +41,16 @@ QKV = [vp, i64p, vp, i64p, vp, i64p]          # q, q_strides, k, k_strides, v, v
 BWD = [pp] + QKV + [vp, vp, vp, i64p]         # ..., o, g, grad_o, go_strides
 NF4 = [vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]
 ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act (include/fastmax_hip_block.h)
-# the public headers under include/: one library, one FASTMAX_ABI_VERSION
-HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
+# the public headers under include/: one library, one FASTMAX_ABI_VERSION.  A new header goes at the end, with its rows at the
+# end of ABI.
+HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h", "fastmax_hip_optim.h",
+           "fastmax_hip_next_token.h", "fastmax_hip_neox.h", "fastmax_hip_cursor.h", "fastmax_hip_nucleus.h", "fastmax_hip_moe.h",
+           "fastmax_hip_moe_decode.h", "fastmax_hip_head.h")
+NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
+CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
+NUCLEUS_MAX_V = 1 << 22                         # the largest V the fixed-point mass of top-p sampling admits
+MOE_MAX_EXPERTS, MOE_MAX_PER_TOKEN = 64, 8      # FASTMAX_MOE_MAX_EXPERTS, FASTMAX_MOE_MAX_PER_TOKEN
+MOE_DECODE_MAX_ROWS = 16                        # FASTMAX_MOE_DECODE_MAX_ROWS
 # every function the HEADERS declare, in their order and in each header's own order: name -> (restype, argtypes).
 # tests/test_binding_cpu.py checks each row against the prototype.
 ABI = {
@@ -124,32 +127,18 @@ ABI = {
     "fastmax_hip_rmsnorm_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, ci, ci, ci, ci, ci, vp, sz, vp]),
     "fastmax_hip_gated_act_forward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_gated_act_backward": (ci, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
-}
-SYMBOLS = list(ABI)
-# the optimizer's side header: same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
-# tests/test_flat_adamw_cpu.py checks each row against the prototype.
-OPTIM_HEADER = "fastmax_hip_optim.h"
-OPTIM_ABI = {
+    # fastmax_hip_optim.h: the fused AdamW over the flat gradient bucket
     "fastmax_hip_adamw_workspace": (sz, [i64]),
     "fastmax_hip_adamw_chunk": (ci, []),
     "fastmax_hip_adamw_norm": (ci, [vp, ci, i64, cf, vp, sz, vp]),
     "fastmax_hip_adamw_update": (ci, [vp, ci, i64, vp, vp, vp, i64, vp, i64, vp, i64, cf, vp, cf, cf, cf, cf, cf, cf, cf, cf,
                                       ci, ci, ci, vp, sz, vp]),
-}
-# the next-token head's side header (last-row logits, exact top-k, seeded sampling): same library, same FASTMAX_ABI_VERSION
-# (additions only), a table of its own.  tests/test_next_token_cpu.py checks each row against the prototype.
-NEXT_TOKEN_HEADER = "fastmax_hip_next_token.h"
-NEXT_TOKEN_ABI = {
+    # fastmax_hip_next_token.h: last-row logits, exact top-k, seeded sampling
     "fastmax_hip_last_logits": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_sample": (ci, [vp, i64, vp, ci, ci, ci, cf, i64, i64, vp]),
     "fastmax_hip_topk_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, vp]),
-}
-# the NeoX (pythia) block's side header (the LayerNorm pair with the three-way residual add, the ungated GELU, their backward
-# passes): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_neox_cpu.py checks each row
-# against the prototype.
-NEOX_HEADER = "fastmax_hip_neox.h"
-NEOX_ACT_GELU = 0                               # enum fastmax_neox_act
-NEOX_ABI = {
+    # fastmax_hip_neox.h: the NeoX (pythia) block's LayerNorm pair with the three-way residual add, the ungated GELU, their
+    # backward passes
     "fastmax_hip_layernorm_forward": (ci, [vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, ci, ci, cf,
                                            ci, ci, vp]),
     "fastmax_hip_layernorm_backward_workspace": (sz, [ci, ci, ci, ci, ci]),
@@ -157,33 +146,16 @@ NEOX_ABI = {
                                             ci, vp, sz, vp]),
     "fastmax_hip_act_forward": (ci, [vp, i64, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_act_backward": (ci, [vp, i64, vp, i64, vp, i64, ci, ci, ci, ci, vp]),
-}
-# the decode cursor's side header (position, draw number and output column of a generation loop in device memory: the feed at the
-# start of a step, the sampler at its end): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
-# tests/test_cursor_cpu.py checks each row against the prototype.
-CURSOR_HEADER = "fastmax_hip_cursor.h"
-CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
-CURSOR_ABI = {
+    # fastmax_hip_cursor.h: position, draw number and output column of a generation loop in device memory (the feed at the
+    # start of a step, the sampler at its end)
     "fastmax_hip_cursor_bytes": (sz, []),
     "fastmax_hip_cursor_feed": (ci, [vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, vp, vp, i64, i64, vp, vp, ci, ci, vp]),
     "fastmax_hip_sample_cursor": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, vp]),
-}
-# top-p (nucleus) sampling's side header (the filter behind the top-k in the sampler of the next-token head and of the decode
-# cursor, and the mask that exposes its kept set): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
-# tests/test_nucleus_cpu.py checks each row against the prototype.
-NUCLEUS_HEADER = "fastmax_hip_nucleus.h"
-NUCLEUS_MAX_V = 1 << 22                         # the largest V the fixed-point mass admits
-NUCLEUS_ABI = {
+    # fastmax_hip_nucleus.h: the top-p filter behind the top-k in both samplers, and the mask that exposes its kept set
     "fastmax_hip_sample_nucleus": (ci, [vp, i64, vp, ci, ci, ci, cf, cf, i64, i64, vp]),
     "fastmax_hip_nucleus_mask": (ci, [vp, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
     "fastmax_hip_sample_cursor_nucleus": (ci, [vp, i64, vp, vp, vp, i64, i64, vp, i64, ci, ci, ci, cf, cf, vp]),
-}
-# the mixture-of-experts MLP's side header (top-k routing with the stable dispatch, gather, combine and their backward passes):
-# same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_moe_cpu.py checks each row against
-# the prototype.
-MOE_HEADER = "fastmax_hip_moe.h"
-MOE_MAX_EXPERTS, MOE_MAX_PER_TOKEN = 64, 8      # FASTMAX_MOE_MAX_EXPERTS, FASTMAX_MOE_MAX_PER_TOKEN
-MOE_ABI = {
+    # fastmax_hip_moe.h: top-k routing with the stable dispatch, gather, combine and their backward passes
     "fastmax_hip_moe_route_workspace": (sz, [ci, ci]),
     "fastmax_hip_moe_route": (ci, [vp, i64, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
     "fastmax_hip_moe_gather": (ci, [vp, i64, vp, vp, i64, ci, ci, ci, ci, vp]),
@@ -191,25 +163,16 @@ MOE_ABI = {
     "fastmax_hip_moe_combine_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, ci, ci, ci, ci, vp]),
     "fastmax_hip_moe_gather_backward": (ci, [vp, i64, vp, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_moe_route_backward": (ci, [vp, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
-}
-# the decode-size expert kernels' side header (the experts' gated MLPs at M <= 16 tokens on the route kernel's device-side row
-# counts, their NF4 operands from a device table): same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.
-# tests/test_moe_decode_cpu.py checks each row against the prototype.
-MOE_DECODE_HEADER = "fastmax_hip_moe_decode.h"
-MOE_DECODE_MAX_ROWS = 16                        # FASTMAX_MOE_DECODE_MAX_ROWS
-MOE_DECODE_ABI = {
+    # fastmax_hip_moe_decode.h: the experts' gated MLPs at M <= 16 tokens on the route kernel's device-side row counts, their
+    # NF4 operands from a device table
     "fastmax_hip_moe_expert_entry_bytes": (sz, []),
     "fastmax_hip_moe_experts_up": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_moe_experts_down": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, ci, ci, vp]),
-}
-# the biased / NF4-quantised next-token head's side header (the last-row logits with an lm_head bias, and on packed NF4 codes):
-# same library, same FASTMAX_ABI_VERSION (additions only), a table of its own.  tests/test_nf4_head_cpu.py checks each row
-# against the prototype.
-HEAD_HEADER = "fastmax_hip_head.h"
-HEAD_ABI = {
+    # fastmax_hip_head.h: the last-row logits with an lm_head bias, and on packed NF4 codes
     "fastmax_hip_last_logits_bias": (ci, [vp, i64, vp, i64, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_last_logits_nf4": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
 }
+SYMBOLS = list(ABI)
 
 _lib = None
 
@@ -223,12 +186,11 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, OPTIM_ABI, NEXT_TOKEN_ABI, NEOX_ABI, CURSOR_ABI, NUCLEUS_ABI, MOE_ABI, MOE_DECODE_ABI, HEAD_ABI):
-        for name, (restype, argtypes) in table.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"libfastmax_hip.so does not export {name}")
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
+    for name, (restype, argtypes) in ABI.items():
+        if not hasattr(L, name):
+            raise RuntimeError(f"libfastmax_hip.so does not export {name}")
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.fastmax_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libfastmax_hip.so ABI version mismatch")
     _lib = L

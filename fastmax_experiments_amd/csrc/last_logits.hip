@@ -1,14 +1,19 @@
-// The last-row lm-head on a weight that next_token.hip's kernel does not take (include/fastmax_hip_head.h): a dense weight with
-// a bias, and a weight stored as NF4 codes (the codebook and the block scales of nf4_gemv.h), with or without a bias.
+// The lm-head over the last position only: the three logits entry points.  fastmax_hip_last_logits
+// (include/fastmax_hip_next_token.h) takes a dense weight; include/fastmax_hip_head.h adds a dense weight with a bias
+// (fastmax_hip_last_logits_bias: the first is this one with no bias) and a weight stored as NF4 codes (the codebook and the
+// block scales of nf4_gemv.h), with or without a bias.
 //
-//   head_logits_kernel   last_logits_kernel's (next_token.hip) plan, with the rows of W behind a policy: 256 threads = 4 waves, a
-//                        wave owns ROWS = 4 rows of W and up to G rows of x (G = 1, 2, 4, 8).  A row is cut into pieces of E
-//                        weights; lane l takes pieces l, l + 64, ...: ROWS pieces of W and G pieces of x feed ROWS x G x E fused
-//                        multiply-adds.  Every (b, v) sum has ONE accumulator per lane, filled in index order from +0, one xor
-//                        butterfly over the lanes, then one float32 add of the bias: the bits depend on C, the dtype and the
-//                        policy only, not on G, the batch, ldx or the load route of x.
-//       DenseRows        E = 16 bytes of W, as floats: that kernel's pieces, order and (without a bias) bits.  next_token.hip keeps
-//                        its own kernel so that its code object stays what it was.
+//   head_logits_kernel   one plan, with the rows of W behind a policy: 256 threads = 4 waves, a wave owns ROWS = 4 rows of W and
+//                        up to G rows of x (G = 1, 2, 4, 8: the pass's row count rounded up, the surplus rows re-read the last
+//                        one and are not stored).  A row is cut into pieces of E weights; lane l takes pieces l, l + 64, ...: ROWS
+//                        pieces of W and G pieces of x (L1 / L2) feed ROWS x G x E fused multiply-adds, W straight to registers
+//                        (it is streamed once, no LDS round trip).  Every (b, v) sum has ONE accumulator per lane, filled in
+//                        index order from +0, one xor butterfly over the lanes, then (with a bias) one float32 add of the bias:
+//                        the bits depend on C, the dtype and the policy only, not on G, the batch, ldx or the load route of x.
+//                        The output type and the presence of a bias are template parameters: without a bias the epilogue is
+//                        a butterfly and a store.
+//       DenseRows        E = 16 bytes of W, as floats, or on the element route the first n elements of a possibly short piece.
+//                        tests/golden/last_logits_*.npz pin its bits.
 //       Nf4Rows          float32 and float16.  E = 8: one 32-bit word of codes, high nibble first, each looked up in the LDS copy of
 //                        the codebook, times the scale of the piece's 64-block (a piece never straddles one: C % 64 == 0), rounded
 //                        to T -- the weight nf4_dequantize returns -- and widened back to float.  x is never rounded: it is
@@ -19,6 +24,7 @@
 #include "nf4_gemv.h"
 #include "row_kernels.h"
 #include "../../include/fastmax_hip_head.h"
+#include "../../include/fastmax_hip_next_token.h"
 
 namespace fastmax {
 namespace head {
@@ -26,7 +32,7 @@ namespace head {
 constexpr int ROWS = 4;             // rows of W per wave
 constexpr int WAVES = 4;            // waves per workgroup
 constexpr int GROUP = 8;            // rows of x per pass over W
-constexpr int MAX_C = 1 << 30;      // DenseRows: fastmax_hip_last_logits' limit
+constexpr int MAX_C = 1 << 30;      // DenseRows: piece indices stay in int
 
 // E elements of a row as floats: 16-byte loads, or the first n elements one by one (the rest are zeros)
 template <typename T, int E, bool VEC>
@@ -81,9 +87,9 @@ template <typename T> struct Nf4Rows {
     }
 };
 
-template <typename T, int G, bool VEC, typename W>
+template <typename T, typename O, bool BIAS, int G, bool VEC, typename W>
 __global__ __launch_bounds__(256) void head_logits_kernel(const T* __restrict__ x, int64_t ldx, const W w, const T* __restrict__ bias,
-                                                          void* __restrict__ out, int out_f32, int64_t ldo, int nb, int V, int C) {
+                                                          O* __restrict__ out, int64_t ldo, int nb, int V, int C) {
     constexpr int E = W::E;
     __shared__ float lut[16];
     if constexpr (W::LUT) {
@@ -133,10 +139,8 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const T* __restrict__ 
         for (int g = 0; g < G; ++g) {
             float s = wave_sum(acc[r][g]);
             if (lane == 0 && v0 + r < V && g < nb) {
-                if (bias) s += to_float(bias[v0 + r]);
-                const int64_t at = (int64_t)g * ldo + v0 + r;
-                if (out_f32) reinterpret_cast<float*>(out)[at] = s;
-                else reinterpret_cast<T*>(out)[at] = from_float<T>(s);
+                if constexpr (BIAS) s += to_float(bias[v0 + r]);
+                out[(int64_t)g * ldo + v0 + r] = from_float<O>(s);
             }
         }
 }
@@ -241,32 +245,45 @@ __global__ __launch_bounds__(256) void head_logits_bf16_kernel(const __bf16* __r
     }
 }
 
-template <typename T, int G, typename W>
-static void launch_route(bool vec, dim3 grid, hipStream_t st, const T* x, int64_t ldx, const W& w, const T* bias, void* out, int out_f32,
-                         int64_t ldo, int nb, int V, int C) {
-    if (vec) hipLaunchKernelGGL((head_logits_kernel<T, G, true, W>), grid, dim3(256), 0, st, x, ldx, w, bias, out, out_f32, ldo, nb, V, C);
-    else hipLaunchKernelGGL((head_logits_kernel<T, G, false, W>), grid, dim3(256), 0, st, x, ldx, w, bias, out, out_f32, ldo, nb, V, C);
+template <typename T, typename O, bool BIAS, int G, typename W>
+static void launch_route(bool vec, dim3 grid, hipStream_t st, const T* x, int64_t ldx, const W& w, const T* bias, O* out, int64_t ldo,
+                         int nb, int V, int C) {
+    if (vec) hipLaunchKernelGGL((head_logits_kernel<T, O, BIAS, G, true, W>), grid, dim3(256), 0, st, x, ldx, w, bias, out, ldo, nb, V, C);
+    else hipLaunchKernelGGL((head_logits_kernel<T, O, BIAS, G, false, W>), grid, dim3(256), 0, st, x, ldx, w, bias, out, ldo, nb, V, C);
 }
 
-// `vec`: x (and the rows of a dense W) move as 16-byte loads
+template <typename T, typename O, bool BIAS, typename W>
+static int launch_passes(const T* x, int64_t ldx, const W& w, bool vec, const T* bias, O* out, int64_t ldo, int B, int V, int C,
+                         hipStream_t st) {
+    const int per_block = WAVES * ROWS;
+    const dim3 grid((unsigned)(((int64_t)V + per_block - 1) / per_block));
+    for (int b0 = 0; b0 < B; b0 += GROUP) {
+        const int nb = B - b0 < GROUP ? B - b0 : GROUP;
+        const T* xb = x + (int64_t)b0 * ldx;
+        O* ob = out + (int64_t)b0 * ldo;
+        if (nb == 1) launch_route<T, O, BIAS, 1, W>(vec, grid, st, xb, ldx, w, bias, ob, ldo, nb, V, C);
+        else if (nb == 2) launch_route<T, O, BIAS, 2, W>(vec, grid, st, xb, ldx, w, bias, ob, ldo, nb, V, C);
+        else if (nb <= 4) launch_route<T, O, BIAS, 4, W>(vec, grid, st, xb, ldx, w, bias, ob, ldo, nb, V, C);
+        else launch_route<T, O, BIAS, 8, W>(vec, grid, st, xb, ldx, w, bias, ob, ldo, nb, V, C);
+    }
+    return (int)hipGetLastError();
+}
+
+// `vec`: x (and the rows of a dense W) move as 16-byte loads.  The output type and the presence of a bias choose the instantiation:
+// as run-time arguments they cost the dense kernel 4 to 10 % at 8 rows of x (profiles/r20_one_logits_kernel.md).
 template <typename T, typename W>
 static int launch_head(const void* xv, int64_t ldx, const W& w, bool vec, const void* bias, void* out, int out_f32, int64_t ldo, int B,
                        int V, int C, hipStream_t st) {
     const T* x = reinterpret_cast<const T*>(xv);
     const T* bs = reinterpret_cast<const T*>(bias);
-    const int per_block = WAVES * ROWS;
-    const dim3 grid((unsigned)(((int64_t)V + per_block - 1) / per_block));
-    const size_t out_es = out_f32 ? 4 : sizeof(T);
-    for (int b0 = 0; b0 < B; b0 += GROUP) {
-        const int nb = B - b0 < GROUP ? B - b0 : GROUP;
-        const T* xb = x + (int64_t)b0 * ldx;
-        void* ob = reinterpret_cast<char*>(out) + (int64_t)b0 * ldo * out_es;
-        if (nb == 1) launch_route<T, 1, W>(vec, grid, st, xb, ldx, w, bs, ob, out_f32, ldo, nb, V, C);
-        else if (nb == 2) launch_route<T, 2, W>(vec, grid, st, xb, ldx, w, bs, ob, out_f32, ldo, nb, V, C);
-        else if (nb <= 4) launch_route<T, 4, W>(vec, grid, st, xb, ldx, w, bs, ob, out_f32, ldo, nb, V, C);
-        else launch_route<T, 8, W>(vec, grid, st, xb, ldx, w, bs, ob, out_f32, ldo, nb, V, C);
+    if (out_f32) {
+        float* o = reinterpret_cast<float*>(out);
+        return bs ? launch_passes<T, float, true>(x, ldx, w, vec, bs, o, ldo, B, V, C, st)
+                  : launch_passes<T, float, false>(x, ldx, w, vec, bs, o, ldo, B, V, C, st);
     }
-    return (int)hipGetLastError();
+    T* o = reinterpret_cast<T*>(out);
+    return bs ? launch_passes<T, T, true>(x, ldx, w, vec, bs, o, ldo, B, V, C, st)
+              : launch_passes<T, T, false>(x, ldx, w, vec, bs, o, ldo, B, V, C, st);
 }
 
 template <typename T>
@@ -301,7 +318,7 @@ static int nf4_head_bf16(const void* x, int64_t ldx, const uint8_t* codes, const
     return (int)hipGetLastError();
 }
 
-// what the two entry points check alike
+// what the dense and the NF4 entry points check alike
 static int check_common(const void* x, int64_t ldx, const void* bias, const void* logits, int64_t ldo, int B, int V, int C, int dtype,
                         int out_dtype, bool shape_ok) {
     if (dtype < 0 || dtype > FASTMAX_F16 || (out_dtype != FASTMAX_F32 && out_dtype != dtype)) return FASTMAX_E_BAD_DTYPE;
@@ -318,6 +335,11 @@ using namespace fastmax;
 using namespace fastmax::head;
 
 extern "C" {
+
+int fastmax_hip_last_logits(const void* x, int64_t ldx, const void* w, int64_t ldw, void* logits, int64_t ldo, int B, int V, int C,
+                            int dtype, int out_dtype, void* stream) {
+    return fastmax_hip_last_logits_bias(x, ldx, w, ldw, nullptr, logits, ldo, B, V, C, dtype, out_dtype, stream);
+}
 
 int fastmax_hip_last_logits_bias(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* logits, int64_t ldo,
                                  int B, int V, int C, int dtype, int out_dtype, void* stream) {

@@ -2,18 +2,18 @@
 
 The last stretch of the reference's loop (generate/base.py:30-47 after lit_gpt/model.py's ``ln_f`` + ``lm_head``) computes a
 (B, T, V) head GEMM of which one row is used, then ``topk``, ``scatter_``, ``softmax`` and ``multinomial`` with a host read per
-token.  Here (csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, bound by ``_lib.NEXT_TOKEN_ABI``):
+token.  Here (csrc/last_logits.hip and csrc/next_token.hip, C ABI: include/fastmax_hip_next_token.h, bound by ``_lib.ABI``):
     last_logits    the head over the LAST position only; the weight is read once for up to 8 rows
     Sampler        exact top-k (ties: the lowest indices are kept) and a draw from softmax(logits / temperature) as the argmax of
                    logit / temperature - log(-log u), u from Philox-4x32-10 under (seed, draw number): the token stays on the device.
-                   ``top_p`` adds the nucleus filter behind the top-k, inside the same kernel (include/fastmax_hip_nucleus.h,
-                   ``_lib.NUCLEUS_ABI``): the shortest prefix of the kept entries, largest first, whose softmax mass reaches top_p
+                   ``top_p`` adds the nucleus filter behind the top-k, inside the same kernel (include/fastmax_hip_nucleus.h):
+                   the shortest prefix of the kept entries, largest first, whose softmax mass reaches top_p
     NextTokenHead  ``ln_f`` (the RMSNorm or LayerNorm kernel on the B last rows) + ``lm_head`` + the sampler.  ``lm_head_bias=True``
-                   and ``quantize_base()`` (``lm_head`` as NF4 codes) go through csrc/next_token_nf4.hip (include/fastmax_hip_head.h,
-                   ``_lib.HEAD_ABI``): the last-row logits with a bias, and straight from the codes
+                   and ``quantize_base()`` (``lm_head`` as NF4 codes) go through the other two entry points of
+                   csrc/last_logits.hip (include/fastmax_hip_head.h): the same kernel with a bias, and straight from the codes
     generate       prompt -> tokens through decoder blocks (``Block`` or ``NeoXBlock``) on their decode state caches
     DecodeCursor, GraphedDecoder   the same loop as ONE graph replay per token: position, draw number and output column live in a
-                   device record (csrc/decode_cursor.hip, include/fastmax_hip_cursor.h, ``_lib.CURSOR_ABI``) that the step's first
+                   device record (csrc/decode_cursor.hip, include/fastmax_hip_cursor.h) that the step's first
                    and last kernel read and advance, so every replay takes the same arguments
 What differs from the reference: logits are float32 by default (``dtype=`` gives the reference's), and the random stream is the
 sampler's own seeded one instead of torch's generator, so a (seed, draw) pair reproduces a token on any batch.  There is no CPU

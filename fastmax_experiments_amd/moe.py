@@ -3,7 +3,7 @@ and combine in HIP around the expert MLPs.
 
 The reference routes with a ``topk``, a softmax and an (E, M, k) boolean mask, then per expert a ``torch.where`` (one host
 synchronisation each), two fancy-index gathers and an indexed read-modify-write of ``y``.  Here csrc/moe.hip (C ABI:
-include/fastmax_hip_moe.h, bound by ``_lib.MOE_ABI``) does the routing and a stable counting sort of the (token, expert) pairs in
+include/fastmax_hip_moe.h, bound by ``_lib.ABI``) does the routing and a stable counting sort of the (token, expert) pairs in
 one to three launches, gathers the tokens into per-expert runs of rows, and combines the experts' outputs with the reference's
 rounding points.  The experts are ``block.LLaMAMLP`` (three ``LoRALinear``, NF4 after ``quantize_base``, the gated activation
 kernel), each run on its slice of the gathered rows.
@@ -17,7 +17,7 @@ reference's loop restated in tensor ops (A/B runs, parity tests, CPU).
 
 At decode size (M <= 16 tokens, NF4 experts, no gradient) ``LLaMAMoE.device_routed = True`` replaces gather, the per-expert
 calls and the ``cat`` by two launches that take their runs from ``offsets`` / ``row_of`` ON THE DEVICE (csrc/moe_decode.hip, C ABI
-include/fastmax_hip_moe_decode.h, bound by ``_lib.MOE_DECODE_ABI``), with the same bits:
+include/fastmax_hip_moe_decode.h, bound by ``_lib.ABI``), with the same bits:
     experts_up             h[s] = round(silu(fc_1_e(x[row_of[s]]))) * fc_2_e(x[row_of[s]])   for s in expert e's run
     experts_down           ys[s] = proj_e(h[s])
 The experts' NF4 operands reach the kernels through a device table (``expert_table``).  Nothing is read back, so the layer can

@@ -7,7 +7,7 @@ The reference's ``Block.forward`` (lit_gpt/model.py:340-361), parallel-residual 
     x = mlp(n_2) + h + x
 with ``torch.nn.LayerNorm`` and ``GptNeoxMLP`` (model.py:608-619: proj(gelu(fc(x)))).  ``CausalSelfAttention`` is
 attention_block.py's; ``fc`` and ``proj`` are ``LoRALinear`` (NF4 base after ``quantize_base``).
-What this file adds runs in csrc/neox_block.hip (C ABI: include/fastmax_hip_neox.h, bound by ``_lib.NEOX_ABI``):
+What this file adds runs in csrc/neox_block.hip (C ABI: include/fastmax_hip_neox.h, bound by ``_lib.ABI``):
     layer_norm_pair    norm_1 and norm_2 of one block normalise the SAME row with the same eps: one pass computes mean and
                        rstd once and writes both outputs, optionally with the hand-over  s = mlp + h + x  of the block before
                        in front of it (3 row reads and 3 row writes where tensor ops take 6 and 4)

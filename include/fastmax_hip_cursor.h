@@ -2,7 +2,7 @@
  * one generated token to the next -- the position fed, the draw number, the column that receives the token -- kept in device
  * memory, so that a whole decode step (feed -> blocks -> head -> sample) takes the same arguments every token and one recorded
  * graph generates a token per replay.  The dtype and error enums are those of fastmax_hip.h; the entry points belong to the same
- * library and FASTMAX_ABI_VERSION and are bound by the table CURSOR_ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
+ * library and FASTMAX_ABI_VERSION and are bound by the table ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
  * `stream`; nothing is allocated, nothing is read back, there are no atomics.
  *
  *   the cursor    fastmax_hip_cursor_bytes() bytes of device memory (a multiple of 8, 8-byte aligned), read as int64 words:

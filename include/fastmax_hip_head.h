@@ -1,6 +1,6 @@
 /* fastmax_hip_head.h -- the next-token head on a biased or NF4-quantised lm_head in libfastmax_hip.so (MI355X / gfx950 only;
- * csrc/next_token_nf4.hip).  The dtype and error enums and `fastmax_nf4_scales` are those of fastmax_hip.h; the entry points
- * belong to the same library and FASTMAX_ABI_VERSION and are bound by the table HEAD_ABI in fastmax_experiments_amd/_lib.py.
+ * csrc/last_logits.hip).  The dtype and error enums and `fastmax_nf4_scales` are those of fastmax_hip.h; the entry points
+ * belong to the same library and FASTMAX_ABI_VERSION and are bound by the table ABI in fastmax_experiments_amd/_lib.py.
  * Everything runs on `stream`; nothing is allocated, nothing is read back, there are no atomics, and a dot product is never
  * split over workgroups.
  *
@@ -8,7 +8,8 @@
  *                     S is the float32 sum that entry point produces, bit for bit -- the same 16-byte pieces, lane l taking
  *                     pieces l, l + 64, ..., one fused multiply-add per product in index order from +0, the same xor
  *                     butterfly over the 64 lanes.  Then ONE float32 add of the bias, then the store's rounding to out_dtype.
- *                     bias: V elements of `dtype`, or NULL: the bits of fastmax_hip_last_logits.
+ *                     bias: V elements of `dtype`, or NULL: fastmax_hip_last_logits itself, which is this entry point with no
+ *                     bias (one kernel, csrc/last_logits.hip).
  *
  *   last_logits_nf4   logits[b, v] = sum_c x[b, c] w^[v, c] (+ (float)bias[v]),  w^[v, c] = round_to_dtype(code * scale):
  *                     `codes` holds V C / 2 bytes (or more: further rows are not read), row-major with no row padding, two

@@ -2,7 +2,7 @@
  * only; csrc/moe.hip): what lit_gpt/model.py:644-674 (LLaMAMoE) does around its expert MLPs with a topk, a softmax, a boolean
  * mask and, per expert, a torch.where, two gathers and an indexed read-modify-write.  The dtype and error enums are those of
  * fastmax_hip.h; the entry points belong to the same library and FASTMAX_ABI_VERSION (additions only) and are bound by the
- * table MOE_ABI in fastmax_experiments_amd/_lib.py.
+ * table ABI in fastmax_experiments_amd/_lib.py.
  *
  * Notation: M tokens (rows), E experts, k experts per token, S = M k slots, C = n_embd; `dtype` (FASTMAX_F32 / BF16 / F16) is
  * the activation dtype dt.  Limits: 1 <= k <= 8, k <= E <= 64, S < 2^31, M >= 1, C >= 1.

@@ -3,7 +3,7 @@
  * (E + 1) and `row_of` (S) on the device; here a workgroup takes its expert's run of rows from those and its expert's NF4 weights
  * from a device table, so that nothing is read back and which weights a workgroup reads is decided by the data, not by the
  * launch: the whole layer can be recorded in a graph.  The dtype and error enums are those of fastmax_hip.h; the entry points
- * belong to the same library and FASTMAX_ABI_VERSION (additions only) and are bound by the table MOE_DECODE_ABI in
+ * belong to the same library and FASTMAX_ABI_VERSION (additions only) and are bound by the table ABI in
  * fastmax_experiments_amd/_lib.py.
  *
  * Notation: M tokens, 1 <= M <= 16; E experts; k experts per token; S = M k slots; C = n_embd, I = intermediate_size, both

@@ -3,7 +3,7 @@
  * block normalise the same row with the same eps, so they share mean and rstd) with the three-way residual add in front, its
  * backward pass, and the ungated exact-GELU activation of GptNeoxMLP with its backward pass.  The dtype and error enums are
  * those of fastmax_hip.h; the entry points belong to the same library and FASTMAX_ABI_VERSION (additions only) and are bound by
- * the table NEOX_ABI in fastmax_experiments_amd/_lib.py.
+ * the table ABI in fastmax_experiments_amd/_lib.py.
  *
  * Conventions (those of fastmax_hip_block.h): every matrix operand is (M rows, C or I columns) with a row stride in ELEMENTS
  * and unit stride along the row; `dtype` (FASTMAX_F32 / BF16 / F16) is the activation dtype; arithmetic is float32; every kernel

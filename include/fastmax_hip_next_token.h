@@ -1,7 +1,7 @@
 /* fastmax_hip_next_token.h -- from a hidden state to the next token in libfastmax_hip.so (MI355X / gfx950 only;
- * csrc/next_token.hip): the lm-head over the LAST position only, an exact top-k filter and a seeded sampler that leaves its
+ * csrc/last_logits.hip for the logits, csrc/next_token.hip for the rest): the lm-head over the LAST position only, an exact top-k filter and a seeded sampler that leaves its
  * token in device memory.  The dtype and error enums are those of fastmax_hip.h; the entry points belong to the same library
- * and FASTMAX_ABI_VERSION and are bound by the table NEXT_TOKEN_ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
+ * and FASTMAX_ABI_VERSION and are bound by the table ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
  * `stream`; nothing is allocated, nothing is read back, there are no float atomics.
  *
  *   last_logits   logits[b, v] = sum_c x[b, c] W[v, c], accumulated in float32.

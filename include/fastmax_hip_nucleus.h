@@ -1,7 +1,7 @@
 /* fastmax_hip_nucleus.h -- top-p (nucleus) sampling in libfastmax_hip.so (MI355X / gfx950 only; csrc/next_token_sample.h,
  * csrc/next_token.hip, csrc/decode_cursor.hip): the filter behind the exact top-k of fastmax_hip_next_token.h, inside the same
  * sampler kernel.  The dtype and error enums are those of fastmax_hip.h; the entry points belong to the same library and
- * FASTMAX_ABI_VERSION and are bound by the table NUCLEUS_ABI in fastmax_experiments_amd/_lib.py.  Everything runs on `stream`;
+ * FASTMAX_ABI_VERSION and are bound by the table ABI in fastmax_experiments_amd/_lib.py.  Everything runs on `stream`;
  * nothing is allocated, nothing is read back, there are no float atomics.
  *
  * Terms, for one row of float32 logits:

@@ -2,7 +2,7 @@
  * csrc/flat_adamw.hip): the whole accumulation boundary of a fine-tune step -- division by the world size, global-norm clip,
  * decoupled weight decay, both moments, bias correction, the update, the parameter written in its own dtype, the gradient zeroed
  * -- in at most two launches.  The dtype and error enums are those of fastmax_hip.h; the entry points belong to the same library
- * and FASTMAX_ABI_VERSION and are bound by the table OPTIM_ABI in fastmax_experiments_amd/_lib.py.
+ * and FASTMAX_ABI_VERSION and are bound by the table ABI in fastmax_experiments_amd/_lib.py.
  *
  * Buffers: `g` is the flat gradient, n elements of `g_dtype` (FASTMAX_F32 / BF16 / F16).  m, v are flat float32 moments (n each).
  * `master` is a flat float32 copy (n) used ONLY at the flat positions of 16-bit parameters: a float32 parameter is updated in

@@ -1,13 +1,17 @@
 """The ctypes table in fastmax_experiments_amd/_lib.py against the prototypes in the public headers under include/
 (_lib.HEADERS): same functions in the same order, and for each one the same number of parameters and the same kind of every
 parameter and of the return type.  A wrong entry would hand a kernel garbage without any error, so this is checked from the
-headers' text (no library needed).  This is the only place that parses the headers."""
+headers' text; per header, also that the library exports every name and that the bound types are the table's, and that the build
+watches the header.  This is the only place that parses the headers and the only one that checks the table against them: a new
+header needs a name in _lib.HEADERS, rows at the end of _lib.ABI and a new checksum below, and no test of its own for this."""
 import ctypes
 import os
 import re
 import zlib
 
-from fastmax_experiments_amd import _lib
+import pytest
+
+from fastmax_experiments_amd import _lib, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -58,7 +62,9 @@ def test_parser_reads_the_header():
 
 
 def test_each_header_declares_its_own_entry_points():
-    assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
+    assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h",
+                            "fastmax_hip_optim.h", "fastmax_hip_next_token.h", "fastmax_hip_neox.h", "fastmax_hip_cursor.h",
+                            "fastmax_hip_nucleus.h", "fastmax_hip_moe.h", "fastmax_hip_moe_decode.h", "fastmax_hip_head.h")
     names = {h: [n for n, _, _ in header_prototypes(h)] for h in _lib.HEADERS}
     assert len(names["fastmax_hip.h"]) == 59
     assert names["fastmax_hip_generate.h"] == ["fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"]
@@ -69,8 +75,28 @@ def test_each_header_declares_its_own_entry_points():
     assert [len(_lib.ABI[n][1]) for n in names["fastmax_hip_linearmax_decode.h"]] == [4, 15]
     # q, q_strides, k, k_strides, v, v_strides: the strides are bound as int64 pointers, not as untyped ones
     assert [t is _lib.i64p for t in _lib.ABI["fastmax_hip_linearmax_decode_advance"][1][:6]] == [False, True] * 3
-    for side in _lib.HEADERS[1:]:
-        assert '#include "fastmax_hip.h"' in header_text(side), side
+    every = [n for h in _lib.HEADERS for n in names[h]]
+    assert len(every) == len(set(every)), "a name is declared in two headers"
+
+
+@pytest.mark.parametrize("header", _lib.HEADERS)
+def test_table_rows_match_the_header_and_the_library(header):
+    """the header's prototypes against their slice of the table, the library's exports and the types bound on the handle"""
+    protos = header_prototypes(header)
+    start = sum(len(header_prototypes(h)) for h in _lib.HEADERS[:_lib.HEADERS.index(header)])
+    rows = list(_lib.ABI.items())[start:start + len(protos)]
+    assert protos and [n for n, _, _ in protos] == [n for n, _ in rows], "names in the header's order"
+    raw, bound = ctypes.CDLL(_lib.LIB_PATH), _lib.lib()
+    for (name, ret, kinds), (_, (restype, argtypes)) in zip(protos, rows):
+        assert ctypes_kind(restype) == ret, name
+        assert [ctypes_kind(t) for t in argtypes] == kinds, name
+        assert hasattr(raw, name), f"{name} is not exported"
+        fn = getattr(bound, name)
+        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
+    if header != _lib.HEADERS[0]:
+        assert '#include "fastmax_hip.h"' in header_text(header)
+    assert os.path.join("..", "..", "include", header) in build.HEADERS, "the build does not watch the header"
+    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
 
 
 def test_binding_table_matches_every_prototype():
@@ -84,20 +110,39 @@ def test_binding_table_matches_every_prototype():
             assert ctypes_kind(t) == kind, f"{name}: parameter {i} is bound as {ctypes_kind(t)}, the header says {kind}"
 
 
-# crc32 of the (name, return kind, parameter kinds) rows, taken on the commit before the four tables became one: its tables
-# concatenated in HEADERS order (68 rows), and its ABI alone (the 59 rows of fastmax_hip.h)
-PINNED_ABI_CRC, PINNED_FIRST_HEADER_CRC = 1240384090, 329697078
+# crc32 of the (name, return kind, parameter kinds) rows.  The first two were taken on the commit before the four tables became
+# one: its ABI alone (the 59 rows of fastmax_hip.h) and its tables concatenated in HEADERS order (68 rows).  The third on the commit
+# before the eight side headers' tables joined them: its nine tables concatenated in HEADERS order (98 rows).
+PINNED_FIRST_HEADER_CRC, PINNED_FOUR_HEADERS_CRC, PINNED_ABI_CRC = 329697078, 1240384090, 3488605058
 
 
 def test_pinned_table_and_abi_version_are_unchanged():
-    """names in order and their signatures, as a checksum taken from the parent commit: no signature moved in the merge"""
-    def digest(table):
-        rows = [(n, ctypes_kind(r), [ctypes_kind(a) for a in args]) for n, (r, args) in table.items()]
-        return zlib.crc32(repr(rows).encode())
+    """names in order and their signatures, as checksums taken from the parent commits: no signature moved in the merges"""
+    def digest(rows):
+        return zlib.crc32(repr([(n, ctypes_kind(r), [ctypes_kind(a) for a in args]) for n, (r, args) in rows]).encode())
+    rows = list(_lib.ABI.items())
     assert _lib.ABI_VERSION == 9
-    assert len(_lib.ABI) == 68 and _lib.SYMBOLS == list(_lib.ABI)
-    assert digest(_lib.ABI) == PINNED_ABI_CRC
-    assert digest(dict(list(_lib.ABI.items())[:59])) == PINNED_FIRST_HEADER_CRC
+    assert len(rows) == 98 and _lib.SYMBOLS == list(_lib.ABI)
+    assert digest(rows[:59]) == PINNED_FIRST_HEADER_CRC
+    assert digest(rows[:68]) == PINNED_FOUR_HEADERS_CRC
+    assert digest(rows) == PINNED_ABI_CRC
+
+
+def test_rows_that_their_headers_define_by_another_row():
+    kinds = {n: [ctypes_kind(t) for t in args] for n, (_, args) in _lib.ABI.items()}
+    # the dense entry point with a bias is fastmax_hip_last_logits with one more pointer, behind w and its stride
+    plain = _lib.ABI["fastmax_hip_last_logits"][1]
+    assert _lib.ABI["fastmax_hip_last_logits_bias"][1] == plain[:4] + [_lib.vp] + plain[4:]
+    # sample_cursor_nucleus: sample_cursor's arguments plus top_p ahead of the stream; sample_nucleus: sample's plus top_p;
+    # nucleus_mask: topk_mask's plus top_p and the temperature
+    assert kinds["fastmax_hip_sample_cursor_nucleus"] == kinds["fastmax_hip_sample_cursor"][:-1] + ["float", "pointer"]
+    assert len(kinds["fastmax_hip_sample_nucleus"]) == len(kinds["fastmax_hip_sample"]) + 1
+    assert len(kinds["fastmax_hip_nucleus_mask"]) == len(kinds["fastmax_hip_topk_mask"]) + 2
+    # from fastmax_hip_optim.h on, whatever returns an error code takes the stream last
+    for header in _lib.HEADERS[4:]:
+        for name, ret, params in header_prototypes(header):
+            if ret == "int" and params:
+                assert params[-1] == "pointer", f"{name}: the stream comes last"
 
 
 def test_error_codes_and_abi_version_match_the_header():

@@ -1,53 +1,23 @@
 """The decode cursor (include/fastmax_hip_cursor.h, csrc/decode_cursor.hip, generate.DecodeCursor / GraphedDecoder), everything that
 needs no device:
 
-1. the table _lib.CURSOR_ABI against the prototypes of _lib.CURSOR_HEADER (the parser of test_binding_cpu), the library's exports,
-   the earlier tables and the ABI version left as they were, the source and the headers in the build's lists;
+1. the record's size and word numbers against the header, the source and the shared sampler header in the build's lists (the
+   binding table against this header: test_binding_cpu);
 2. every rejection the header lists, returned before any launch;
 3. the host contract: what GraphedDecoder refuses, before it touches a device, and ``generate(graphed=...)``."""
-import ctypes
 
 import pytest
 import torch
 
 from fastmax_experiments_amd import _lib, build, generate
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
+from test_binding_cpu import header_text
 
 
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_cursor_table_matches_every_prototype():
-    protos = header_prototypes(_lib.CURSOR_HEADER)
-    assert _lib.CURSOR_HEADER == "fastmax_hip_cursor.h"
-    assert [n for n, _, _ in protos] == list(_lib.CURSOR_ABI)
-    assert [n for n, _, _ in protos] == ["fastmax_hip_cursor_bytes", "fastmax_hip_cursor_feed", "fastmax_hip_sample_cursor"]
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.CURSOR_ABI[name]
-        assert ctypes_kind(restype) == ret, name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        if kinds:
-            assert ret == "int" and kinds[-1] == "pointer", f"{name}: an error code, and the stream comes last"
-    assert '#include "fastmax_hip.h"' in header_text(_lib.CURSOR_HEADER)
-
-
-def test_library_exports_the_cursor_and_the_earlier_tables_are_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.CURSOR_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds every table or raises
-    for name, (restype, argtypes) in _lib.CURSOR_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
-    assert len(_lib.ABI) == 68 and len(_lib.OPTIM_ABI) == 4 and len(_lib.NEXT_TOKEN_ABI) == 3 and len(_lib.NEOX_ABI) == 5
-    earlier = set(_lib.ABI) | set(_lib.OPTIM_ABI) | set(_lib.NEXT_TOKEN_ABI) | set(_lib.NEOX_ABI)
-    assert not set(_lib.CURSOR_ABI) & earlier
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
-
-
+# ---- 1. the record ------------------------------------------------------------------------------------------------------------
 def test_the_record_is_whole_int64_words_and_the_word_numbers_are_the_headers():
     nbytes = _lib.lib().fastmax_hip_cursor_bytes()
     assert nbytes % 8 == 0 and nbytes // 8 > _lib.CURSOR_OVERFLOW
-    text = header_text(_lib.CURSOR_HEADER)
+    text = header_text("fastmax_hip_cursor.h")
     for word, number in (("POS", _lib.CURSOR_POS), ("NEXT", _lib.CURSOR_NEXT), ("DRAW_BASE", _lib.CURSOR_DRAW_BASE),
                          ("SEED", _lib.CURSOR_SEED), ("OVERFLOW", _lib.CURSOR_OVERFLOW), ("WORDS", nbytes // 8)):
         assert f"FASTMAX_CURSOR_{word} = {number}" in text, word
@@ -56,7 +26,6 @@ def test_the_record_is_whole_int64_words_and_the_word_numbers_are_the_headers():
 def test_the_build_compiles_the_source_and_watches_the_headers():
     assert "decode_cursor.hip" in build.SOURCES and "next_token.hip" in build.SOURCES
     assert "next_token_sample.h" in build.HEADERS
-    assert any(h.endswith(_lib.CURSOR_HEADER) for h in build.HEADERS)
 
 
 # ---- 2. rejections -----------------------------------------------------------------------------------------------------------

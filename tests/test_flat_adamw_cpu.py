@@ -1,12 +1,10 @@
 """optim.FlatAdamW (include/fastmax_hip_optim.h, csrc/flat_adamw.hip), everything that needs no device:
 
-1. the table _lib.OPTIM_ABI against the prototypes of _lib.OPTIM_HEADER (the parser of test_binding_cpu), the library's exports,
-   and the first table left as it was;
+1. the size queries, which need no device (the binding table against this header: test_binding_cpu);
 2. every rejection the header lists, returned before any launch;
 3. the chunk table: every flat index exactly once, no chunk across a segment boundary;
 4. the host contract of FlatAdamW: ValueErrors, a state_dict round trip that continues bit for bit;
 5. the CPU rehearsal path against the float64 restatement (flat_adamw_ref.py)."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -14,36 +12,11 @@ import torch
 
 from flat_adamw_ref import PARITY_TOL, AdamWRef
 from fastmax_experiments_amd import _lib, dp, optim
-from test_binding_cpu import ctypes_kind, header_prototypes
 
 SIZES = [1, 7, 64, 1023, 1025, 4099]
 
 
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_optim_table_matches_every_prototype():
-    protos = header_prototypes(_lib.OPTIM_HEADER)
-    assert _lib.OPTIM_HEADER == "fastmax_hip_optim.h"
-    assert [n for n, _, _ in protos] == list(_lib.OPTIM_ABI)
-    assert len(protos) == 4 and all(n.startswith("fastmax_hip_adamw_") for n, _, _ in protos)
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.OPTIM_ABI[name]
-        assert ctypes_kind(restype) == ret, name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-
-
-def test_library_exports_the_optimizer_and_the_first_table_is_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.OPTIM_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds both tables or raises
-    for name, (restype, argtypes) in _lib.OPTIM_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
-    assert len(_lib.ABI) == 68 and not set(_lib.ABI) & set(_lib.OPTIM_ABI)
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
-
-
+# ---- 1. size queries (the binding itself: test_binding_cpu) -------------------------------------------------------------------
 def test_size_queries_need_no_device():
     L = _lib.lib()
     chunk = L.fastmax_hip_adamw_chunk()

@@ -1,15 +1,14 @@
 """The mixture-of-experts MLP (include/fastmax_hip_moe.h, csrc/moe.hip, fastmax_experiments_amd/moe.py), everything that needs
 no device:
 
-1. the table _lib.MOE_ABI against the prototypes of _lib.MOE_HEADER (the parser of test_binding_cpu), the library's exports, the
-   six earlier tables left as they were, header and source in the build's lists;
+1. the size limits against the header, the source in the build's list (the binding table against this header:
+   test_binding_cpu);
 2. every rejection of the C ABI, returned before any launch (null streams, made-up addresses);
 3. the restatement moe_ref.py on every fixture of tests/golden/make_golden_moe.py: float32 to 1e-6 of the tensor's scale, 16-bit to
    one unit in the last place;
 4. ``LLaMAMoE(fused_neighbours=False)`` on CPU, loaded from a fixture's parameters: y, dx and every parameter gradient to the same
    bounds, the experts without tokens with zero gradients;
 5. the host contract: state-dict keys, ``Block(mlp_class="LLaMAMoE")``, the size limits, the fused route's CPU-tensor error."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,48 +18,21 @@ import moe_ref
 from block_ref import ulp_err
 from conftest import golden_names, load_golden, rel_err
 from fastmax_experiments_amd import _lib, build
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
+from test_binding_cpu import header_text
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 FIXTURES = golden_names("moe_")
-NAMES = ["fastmax_hip_moe_route_workspace", "fastmax_hip_moe_route", "fastmax_hip_moe_gather", "fastmax_hip_moe_combine",
-         "fastmax_hip_moe_combine_backward", "fastmax_hip_moe_gather_backward", "fastmax_hip_moe_route_backward"]
 
 
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_moe_table_matches_every_prototype():
-    protos = header_prototypes(_lib.MOE_HEADER)
-    assert _lib.MOE_HEADER == "fastmax_hip_moe.h"
-    assert [n for n, _, _ in protos] == list(_lib.MOE_ABI) == NAMES
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.MOE_ABI[name]
-        assert ctypes_kind(restype) == ret == ("size_t" if name.endswith("_workspace") else "int"), name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        if not name.endswith("_workspace"):
-            assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-    text = header_text(_lib.MOE_HEADER)
-    assert '#include "fastmax_hip.h"' in text
+# ---- 1. limits, build ------------------------------------------------------------------------------------------------------------
+def test_the_limits_are_the_headers():
+    text = header_text("fastmax_hip_moe.h")
     assert f"#define FASTMAX_MOE_MAX_EXPERTS {_lib.MOE_MAX_EXPERTS}" in text
     assert f"#define FASTMAX_MOE_MAX_PER_TOKEN {_lib.MOE_MAX_PER_TOKEN}" in text
 
 
-def test_library_exports_the_moe_and_the_earlier_tables_are_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.MOE_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds every table or raises
-    for name, (restype, argtypes) in _lib.MOE_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    earlier = (_lib.ABI, _lib.OPTIM_ABI, _lib.NEXT_TOKEN_ABI, _lib.NEOX_ABI, _lib.CURSOR_ABI, _lib.NUCLEUS_ABI)
-    assert [len(t) for t in earlier] == [68, 4, 3, 5, 3, 3]
-    assert not set(_lib.MOE_ABI) & set().union(*earlier)
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
-
-
 def test_the_build_lists_the_source_and_the_header():
     assert "moe.hip" in build.SOURCES and "row_kernels.h" in build.HEADERS
-    assert any(h.endswith(_lib.MOE_HEADER) for h in build.HEADERS)
 
 
 # ---- 2. rejections -----------------------------------------------------------------------------------------------------------

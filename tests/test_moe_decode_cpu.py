@@ -1,8 +1,8 @@
 """The decode-size expert kernels on device-side row counts (include/fastmax_hip_moe_decode.h, csrc/moe_decode.hip,
 fastmax_experiments_amd/moe.py ``device_routed``), everything that needs no device:
 
-1. the table _lib.MOE_DECODE_ABI against the prototypes of _lib.MOE_DECODE_HEADER (the parser of test_binding_cpu), the library's
-   exports, the seven earlier tables left as they were, source and headers in the build's lists;
+1. the row limit against the header, source and shared headers in the build's lists (the binding table against this header:
+   test_binding_cpu);
 2. the packer's entry size against the library's ``sizeof``;
 3. every rejection of the C ABI, returned before any launch (null streams, made-up addresses);
 4. what the ``device_routed`` setter refuses, each with its own message, and what ``GraphedDecoder`` refuses before it touches a
@@ -13,56 +13,20 @@ import pytest
 import torch
 
 from fastmax_experiments_amd import _lib, build
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
-
-NAMES = ["fastmax_hip_moe_expert_entry_bytes", "fastmax_hip_moe_experts_up", "fastmax_hip_moe_experts_down"]
+from test_binding_cpu import header_text
 
 
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_moe_decode_table_matches_every_prototype():
-    protos = header_prototypes(_lib.MOE_DECODE_HEADER)
-    assert _lib.MOE_DECODE_HEADER == "fastmax_hip_moe_decode.h"
-    assert [n for n, _, _ in protos] == list(_lib.MOE_DECODE_ABI) == NAMES
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.MOE_DECODE_ABI[name]
-        assert ctypes_kind(restype) == ret == ("size_t" if name.endswith("_bytes") else "int"), name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        if not name.endswith("_bytes"):
-            assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-    text = header_text(_lib.MOE_DECODE_HEADER)
-    assert '#include "fastmax_hip.h"' in text and '#include "fastmax_hip_moe.h"' in text
+
+# ---- 1. limit, build ------------------------------------------------------------------------------------------------------------
+def test_the_limit_is_the_headers_and_it_builds_on_the_moe_header():
+    text = header_text("fastmax_hip_moe_decode.h")
+    assert '#include "fastmax_hip_moe.h"' in text
     assert f"#define FASTMAX_MOE_DECODE_MAX_ROWS {_lib.MOE_DECODE_MAX_ROWS}" in text
-
-
-def test_library_exports_the_table_and_the_earlier_tables_are_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.MOE_DECODE_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds every table or raises
-    for name, (restype, argtypes) in _lib.MOE_DECODE_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    earlier = (_lib.ABI, _lib.OPTIM_ABI, _lib.NEXT_TOKEN_ABI, _lib.NEOX_ABI, _lib.CURSOR_ABI, _lib.NUCLEUS_ABI, _lib.MOE_ABI)
-    assert [len(t) for t in earlier] == [68, 4, 3, 5, 3, 3, 7]
-    assert list(_lib.MOE_ABI) == ["fastmax_hip_moe_route_workspace", "fastmax_hip_moe_route", "fastmax_hip_moe_gather",
-                                  "fastmax_hip_moe_combine", "fastmax_hip_moe_combine_backward", "fastmax_hip_moe_gather_backward",
-                                  "fastmax_hip_moe_route_backward"]
-    assert list(_lib.NUCLEUS_ABI) == ["fastmax_hip_sample_nucleus", "fastmax_hip_nucleus_mask", "fastmax_hip_sample_cursor_nucleus"]
-    assert list(_lib.CURSOR_ABI) == ["fastmax_hip_cursor_bytes", "fastmax_hip_cursor_feed", "fastmax_hip_sample_cursor"]
-    assert list(_lib.NEXT_TOKEN_ABI) == ["fastmax_hip_last_logits", "fastmax_hip_sample", "fastmax_hip_topk_mask"]
-    assert list(_lib.OPTIM_ABI) == ["fastmax_hip_adamw_workspace", "fastmax_hip_adamw_chunk", "fastmax_hip_adamw_norm",
-                                    "fastmax_hip_adamw_update"]
-    assert list(_lib.NEOX_ABI) == ["fastmax_hip_layernorm_forward", "fastmax_hip_layernorm_backward_workspace",
-                                   "fastmax_hip_layernorm_backward", "fastmax_hip_act_forward", "fastmax_hip_act_backward"]
-    assert list(_lib.ABI) == [n for h in _lib.HEADERS for n, _, _ in header_prototypes(h)]
-    assert not set(_lib.MOE_DECODE_ABI) & set().union(*earlier)
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
 
 
 def test_the_build_lists_the_source_and_the_headers():
     assert "moe_decode.hip" in build.SOURCES and "nf4_lora.hip" in build.SOURCES
     assert "nf4_gemv.h" in build.HEADERS and "row_kernels.h" in build.HEADERS
-    assert any(h.endswith(_lib.MOE_DECODE_HEADER) for h in build.HEADERS)
 
 
 # ---- 2. the table's entry ---------------------------------------------------------------------------------------------------

@@ -1,13 +1,11 @@
-"""The next-token head (include/fastmax_hip_next_token.h, csrc/next_token.hip, fastmax_experiments_amd/generate.py), everything
+"""The next-token head (include/fastmax_hip_next_token.h, csrc/last_logits.hip, csrc/next_token.hip, fastmax_experiments_amd/generate.py), everything
 that needs no device:
 
-1. the table _lib.NEXT_TOKEN_ABI against the prototypes of _lib.NEXT_TOKEN_HEADER (the parser of test_binding_cpu), the
-   library's exports, and the earlier tables left as they were;
+1. (the binding table against this header: test_binding_cpu);
 2. every rejection the header lists, returned before any launch;
 3. the restatement (next_token_ref.py): Philox-4x32-10 against its known-answer vectors, the keep mask on designed ties, and the
    distribution of the restated draws against softmax(logits / temperature);
 4. the host contract of Sampler, NextTokenHead and generate: ValueErrors before any call, the seed taken from torch's generator."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -15,34 +13,6 @@ import torch
 
 import next_token_ref as ref
 from fastmax_experiments_amd import _lib, generate
-from test_binding_cpu import ctypes_kind, header_prototypes
-
-
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_next_token_table_matches_every_prototype():
-    protos = header_prototypes(_lib.NEXT_TOKEN_HEADER)
-    assert _lib.NEXT_TOKEN_HEADER == "fastmax_hip_next_token.h"
-    assert [n for n, _, _ in protos] == list(_lib.NEXT_TOKEN_ABI)
-    assert [n for n, _, _ in protos] == ["fastmax_hip_last_logits", "fastmax_hip_sample", "fastmax_hip_topk_mask"]
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.NEXT_TOKEN_ABI[name]
-        assert ctypes_kind(restype) == ret == "int", name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-
-
-def test_library_exports_the_head_and_the_earlier_tables_are_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.NEXT_TOKEN_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds all three tables or raises
-    for name, (restype, argtypes) in _lib.NEXT_TOKEN_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h")
-    assert len(_lib.ABI) == 68 and len(_lib.OPTIM_ABI) == 4 and _lib.OPTIM_HEADER == "fastmax_hip_optim.h"
-    assert not set(_lib.NEXT_TOKEN_ABI) & (set(_lib.ABI) | set(_lib.OPTIM_ABI))
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
 
 
 # ---- 2. rejections -----------------------------------------------------------------------------------------------------------

@@ -1,10 +1,10 @@
-"""The next-token head on an MI355X (csrc/next_token.hip, fastmax_experiments_amd/generate.py) against float64 and the numpy
-restatement (next_token_ref.py).
+"""The next-token head on an MI355X (csrc/last_logits.hip, csrc/next_token.hip, fastmax_experiments_amd/generate.py) against
+float64 and the numpy restatement (next_token_ref.py).
 
 1. last_logits against float64, per logit |err| <= (C + 3) 2^-24 sum_c |x_c w_c|: one rounding per product and per add at
    unit roundoff 2^-24 (the fused multiply-adds round less often).  A 16-bit output adds its own rounding, relative 2^-8 (bf16)
    or 2^-11 (fp16) of the float32 value.  Rows of a batch against the same rows alone, two calls, and the 16-byte route
-   against the element route: equal bits.
+   against the element route: equal bits.  The bits themselves against tests/golden/last_logits_*.npz.
 2. the keep mask element for element against the restatement: designed ties and random rows.
 3. temperature 0 against argmax.
 4. sampled tokens against the restatement wherever the float64 gap between the two best scores is >= 1e-3: scores stay below
@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import next_token_ref as ref
+from conftest import load_golden
 from test_next_token_cpu import tie_cases
 
 pytestmark = pytest.mark.gpu
@@ -83,6 +84,32 @@ def test_sixteen_byte_route_and_element_route_give_equal_bits(B, C, V, dtname):
     w_off.copy_(w)
     assert w.data_ptr() % 16 == 0 and w_off.data_ptr() % 16 != 0 and torch.equal(w, w_off)
     assert torch.equal(last_logits(x, w), last_logits(x, w_off))
+
+
+@pytest.mark.parametrize("dtname", list(DTYPES))
+def test_last_logits_keep_the_recorded_bits(dtname):
+    """tests/golden/make_golden_last_logits.py: both load routes, G = 1, 2, 4 and 8 + 1, both output types, with and without a
+    bias, against the bits a build before the plain and the biased entry point shared a kernel produced"""
+    from fastmax_experiments_amd.generate import last_logits
+    dt = DTYPES[dtname]
+    d, m = load_golden(f"last_logits_{dtname}")
+
+    def tensor(a, dtype):
+        t = torch.from_numpy(a)
+        return (t.view(dtype) if t.dtype == torch.int16 else t).cuda()
+    V, C = m["V"], m["C_elem"]
+    bias = tensor(d["bias"], dt)
+    cases = {"vec": (tensor(d["vec_x"], dt), tensor(d["vec_w"], dt)),
+             "elem": (tensor(d["elem_hidden"], dt)[:, -1], tensor(d["elem_wide"], dt)[1:V + 1, 1:1 + C])}
+    assert cases["vec"][1].shape == (V, m["C_vec"]) and cases["elem"][1].stride() == (120, 1) and cases["elem"][0].stride() == (5 * C, 1)
+    assert bias.shape == (V + 5,) and m["batches"] == [1, 2, 3, 9]
+    for case, (x, w) in cases.items():
+        for B in m["batches"]:
+            for out_name, out_dt in (("f32", torch.float32), ("same", dt)):
+                for bias_name, b in (("bias", bias), ("nobias", None)):
+                    want = tensor(d[f"{case}_B{B}_{out_name}_{bias_name}"], out_dt)
+                    got = last_logits(x[:B], w, out_dt, bias=b)
+                    assert got.dtype == want.dtype and torch.equal(got, want), (case, B, out_name, bias_name)
 
 
 # ---- 2. the keep mask ------------------------------------------------------------------------------------------------------------

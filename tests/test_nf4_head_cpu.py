@@ -1,7 +1,7 @@
-"""The next-token head on a biased or NF4-quantised lm_head (include/fastmax_hip_head.h, csrc/next_token_nf4.hip,
+"""The next-token head on a biased or NF4-quantised lm_head (include/fastmax_hip_head.h, csrc/last_logits.hip,
 fastmax_experiments_amd/generate.py), everything that needs no device:
 
-1. the table _lib.HEAD_ABI against the prototypes of _lib.HEAD_HEADER (the parser of test_binding_cpu) and the library's exports;
+1. (the binding table against this header, and the bias entry point's row against the plain one's: test_binding_cpu);
 2. every rejection the header lists, returned before any launch;
 3. NextTokenHead.quantize_base on host tensors: sizes, state-dict keys, a round trip, the refusals; the default head unchanged."""
 import ctypes
@@ -12,36 +12,6 @@ import torch
 from fastmax_experiments_amd import _lib
 from fastmax_experiments_amd.generate import NextTokenHead, last_logits
 from fastmax_experiments_amd.lora import NF4Linear, NF4Scales
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
-
-
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_head_table_matches_every_prototype():
-    protos = header_prototypes(_lib.HEAD_HEADER)
-    assert _lib.HEAD_HEADER == "fastmax_hip_head.h" and '#include "fastmax_hip.h"' in header_text(_lib.HEAD_HEADER)
-    assert [n for n, _, _ in protos] == list(_lib.HEAD_ABI) == ["fastmax_hip_last_logits_bias", "fastmax_hip_last_logits_nf4"]
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.HEAD_ABI[name]
-        assert ctypes_kind(restype) == ret == "int", name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-    # the dense entry point is fastmax_hip_last_logits with one more pointer, behind w and its stride
-    plain = _lib.NEXT_TOKEN_ABI["fastmax_hip_last_logits"][1]
-    assert _lib.HEAD_ABI["fastmax_hip_last_logits_bias"][1] == plain[:4] + [_lib.vp] + plain[4:]
-
-
-def test_library_exports_the_head_entry_points_under_the_same_abi_version():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.HEAD_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()
-    for name, (restype, argtypes) in _lib.HEAD_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    every = [_lib.ABI, _lib.OPTIM_ABI, _lib.NEXT_TOKEN_ABI, _lib.NEOX_ABI, _lib.CURSOR_ABI, _lib.NUCLEUS_ABI, _lib.MOE_ABI,
-             _lib.MOE_DECODE_ABI]
-    assert not any(set(_lib.HEAD_ABI) & set(t) for t in every)
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
 
 
 # ---- 2. rejections -----------------------------------------------------------------------------------------------------------

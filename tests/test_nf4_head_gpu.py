@@ -1,4 +1,4 @@
-"""The next-token head on a biased or NF4-quantised lm_head on an MI355X (csrc/next_token_nf4.hip, include/fastmax_hip_head.h,
+"""The next-token head on a biased or NF4-quantised lm_head on an MI355X (csrc/last_logits.hip, include/fastmax_hip_head.h,
 fastmax_experiments_amd/generate.py).
 
 1. last_logits on NF4 codes against float64.  The weight the reference multiplies is the HOST path of nf4_dequantize on the

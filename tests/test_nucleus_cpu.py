@@ -1,15 +1,14 @@
 """Top-p (nucleus) sampling (include/fastmax_hip_nucleus.h, csrc/next_token_sample.h, fastmax_experiments_amd/generate.py),
 everything that needs no device:
 
-1. the table _lib.NUCLEUS_ABI against the prototypes of _lib.NUCLEUS_HEADER (the parser of test_binding_cpu), the library's
-   exports, the five earlier tables left as they were, the header in the build's list;
+1. the sources and the shared sampler header in the build's lists (the binding table against this header, and its rows against
+   the samplers' without top_p: test_binding_cpu);
 2. every rejection the header adds, returned before any launch;
 3. the host contract: a top_p outside (0, 1] raises ValueError everywhere before any device work, CPU tensors raise the existing
    RuntimeError, ``serves`` tells two top_p apart;
 4. the restatement (nucleus_ref.py): designed rows, the tensor-op route's keep rule (torch sort + cumsum in float64), the
    library's fixed-point evaluation restated in numpy inside the band of nucleus_ref.epsilon, how sharp that band is, and the
    distribution of the restated draw inside a nucleus."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -18,47 +17,13 @@ import torch
 import next_token_ref as ref
 import nucleus_ref as nuc
 from fastmax_experiments_amd import _lib, build, generate
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
 from test_next_token_cpu import CHI2_999_DF7, LOGITS8, SEEDS, _chi2
 
 BAD_TOP_P = [0, -0.1, 1.5, float("nan")]
 
 
-# ---- 1. binding ------------------------------------------------------------------------------------------------------------
-def test_nucleus_table_matches_every_prototype():
-    protos = header_prototypes(_lib.NUCLEUS_HEADER)
-    assert _lib.NUCLEUS_HEADER == "fastmax_hip_nucleus.h"
-    assert [n for n, _, _ in protos] == list(_lib.NUCLEUS_ABI)
-    assert [n for n, _, _ in protos] == ["fastmax_hip_sample_nucleus", "fastmax_hip_nucleus_mask", "fastmax_hip_sample_cursor_nucleus"]
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.NUCLEUS_ABI[name]
-        assert ctypes_kind(restype) == ret == "int", name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-    assert '#include "fastmax_hip.h"' in header_text(_lib.NUCLEUS_HEADER)
-    # sample_cursor_nucleus: sample_cursor's arguments plus top_p; sample_nucleus: sample's plus top_p
-    cursor = [ctypes_kind(t) for t in _lib.CURSOR_ABI["fastmax_hip_sample_cursor"][1]]
-    assert [ctypes_kind(t) for t in _lib.NUCLEUS_ABI["fastmax_hip_sample_cursor_nucleus"][1]] == cursor[:-1] + ["float", "pointer"]
-    assert len(_lib.NUCLEUS_ABI["fastmax_hip_sample_nucleus"][1]) == len(_lib.NEXT_TOKEN_ABI["fastmax_hip_sample"][1]) + 1
-    assert len(_lib.NUCLEUS_ABI["fastmax_hip_nucleus_mask"][1]) == len(_lib.NEXT_TOKEN_ABI["fastmax_hip_topk_mask"][1]) + 2
-
-
-def test_library_exports_the_nucleus_and_the_earlier_tables_are_unchanged():
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in _lib.NUCLEUS_ABI:
-        assert hasattr(raw, name), name
-    bound = _lib.lib()                       # binds every table or raises
-    for name, (restype, argtypes) in _lib.NUCLEUS_ABI.items():
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-    earlier = (_lib.ABI, _lib.OPTIM_ABI, _lib.NEXT_TOKEN_ABI, _lib.NEOX_ABI, _lib.CURSOR_ABI)
-    assert [len(t) for t in earlier] == [68, 4, 3, 5, 3]
-    assert not set(_lib.NUCLEUS_ABI) & set().union(*earlier)
-    assert bound.fastmax_hip_abi_version() == _lib.ABI_VERSION == 9
-
-
+# ---- 1. the build ------------------------------------------------------------------------------------------------------------
 def test_the_build_watches_the_header():
-    assert any(h.endswith(_lib.NUCLEUS_HEADER) for h in build.HEADERS)
     assert "next_token.hip" in build.SOURCES and "decode_cursor.hip" in build.SOURCES and "next_token_sample.h" in build.HEADERS
 
 
