@@ -1,10 +1,15 @@
 // Loss path of the fine-tune step: row-wise cross entropy over the vocabulary, the op behind the
 // reference's chunked_cross_entropy (lit_gpt/utils.py:228-272, torch.nn.functional.cross_entropy with reduction="none" and
 // ignore_index).  One workgroup per row, one pass over the logits each way:
-//   forward : lse_i = log sum_v exp(z_iv),  loss_i = lse_i - z_i,t_i   (0 where t_i == ignore_index)
+//   forward : lse_i = m_i + log s_i (m the row max, s = sum_v exp(z_iv - m_i)),  loss_i = log s_i + (m_i - z_i,t_i)
+//             (0 where t_i == ignore_index or outside [0, V))
 //   backward: dz_iv = (exp(z_iv - lse_i) - [v == t_i]) * gscale_i      (0 rows where ignored), written in place or to dz
 // Logits are float32 / bf16 / fp16, read with 16-byte loads; the running (max, sum) pair is combined across the lanes
 // and waves of the block.  HBM-bound: one read (forward), one read + one write (backward) of the (M, V) logits.
+// Error model: the row loss is summed from terms of its own size, so it is accurate to about (|loss| + K) 2^-22 whatever
+// the logits' offset.  One float per row (lse) is kept for the backward pass, so lse and with it the probabilities carry a
+// relative error of about |lse| 2^-24.  tests/ce_ref.py states these allowances (K = 16) and tests/test_loss_rows_gpu.py
+// pins exactly that, per row and per entry.
 #include "fastmax_common.h"
 
 namespace fastmax {
@@ -62,10 +67,11 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* logits, int64_t ld
     if (tid == 0) {
         float mm = sm[0], st = ss[0];
         for (int w = 1; w < 4; ++w) ms_combine(mm, st, sm[w], ss[w]);
-        const float l = mm + __logf(st);
+        const float ls = __logf(st);
         const int64_t t = targets[i];
-        lse[i] = l;
-        loss[i] = (t == ignore_index || t < 0 || t >= V) ? 0.f : l - to_float(row[t]);
+        lse[i] = mm + ls;
+        // log s + (m - z_t), not (m + log s) - z_t: both terms are of the loss's own size, whatever the logits' offset
+        loss[i] = (t == ignore_index || t < 0 || t >= V) ? 0.f : ls + (mm - to_float(row[t]));
     }
 }
 
