@@ -8,7 +8,7 @@
 // (products with 1.0 are exact, accumulation is fp32), so staging is a plain 16-byte copy global -> LDS, no per-chunk
 // partial-sum arrays exist and the workgroup needs 45 KB of LDS at D <= 64: three workgroups per CU.
 // NORM fuses the linearmax prologue (fastmax_hack.py:38-43) into staging as in the generic kernel.
-#include "fastmax_mfma_common.h"
+#include "fastmax_scan128.h"
 
 namespace fastmax {
 
@@ -444,15 +444,7 @@ template <bool NORM>
 static int launch_bf16_d128(const Bf16Params& prm, int nb, hipStream_t stream) {
     constexpr int DP = 128;
     constexpr int lds = 3 * 64 * DP * 2 + (DP + 16) * DP * 2 + DP * 4 + 8 * 2048;
-    auto kern = fwd_p1_mfma_bf16_d128_kernel<NORM>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, stream, prm);
-    return (int)hipGetLastError();
+    return scan128::launch512<fwd_p1_mfma_bf16_d128_kernel<NORM>, lds>(prm, nb, stream);
 }
 
 template <int DP, bool NORM>

@@ -7,7 +7,7 @@
 // ahead, raw, split in registers), and the result tile is stored from the accumulators (16-byte pieces per lane) instead
 // of through a staging area.  LDS: K, V images 64 KB + state images 72 KB + S1.
 // NORM fuses the linearmax prologue (fastmax_hack.py:38-43): K rows in staging, Q rows in registers.
-#include "fastmax_mfma_common.h"
+#include "fastmax_scan128.h"
 
 namespace fastmax {
 
@@ -27,15 +27,17 @@ template <typename TIN, bool NORM, bool BUF>
 __global__ __launch_bounds__(512, 1) void fwd_p1_mfma_d128_2p_kernel(D128Params prm) {
     constexpr int NP = 2, EPL = InTraits<TIN>::EPL;
     static_assert(InTraits<TIN>::NP == 2, "two-part operands");
-    constexpr int DP = 128, C = 64, IMG = C * DP * 2, SIMG = (DP + 16) * DP * 2;
+    using namespace scan128;
+    constexpr int SIMG = (DP + 16) * DP * 2;
     constexpr int KI = 0, VI = NP * IMG, S2I = 2 * NP * IMG, S1V = S2I + 2 * SIMG;
     constexpr int COLS = DP / EPL, RPP = 512 / COLS, NPASS = C / RPP;
-    constexpr int KS = DP / 32, MT = DP / 16, QL = 8 / EPL;                  // QL 16-byte loads per 8-element Q fragment piece
+    constexpr int QL = 8 / EPL;                                              // QL 16-byte loads per 8-element Q fragment piece
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qt = w & 3, dh = w >> 2;
     const int r = lane & 15, q4 = lane >> 4;
+    const WaveLane wl{w, r, q4};
     const int bh = blockIdx.x / prm.nseg, seg = blockIdx.x - bh * prm.nseg;
     const int b = bh / prm.H, h = bh % prm.H;
     const int N = prm.N, D = prm.D;
@@ -55,13 +57,7 @@ __global__ __launch_bounds__(512, 1) void fwd_p1_mfma_d128_2p_kernel(D128Params 
     auto issue = [&](int c) {
         kload.load(c, rk);
         vload.load(c, rv);
-        const int row = c * C + 16 * qt + r;                       // this wave's query row on this lane
-        int q4o = q4;                                              // opaque: the eight piece offsets are re-formed per chunk, not hoisted and spilled
-        asm volatile("" : "+v"(q4o));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int u = 0; u < QL; ++u) rq[ks][u] = qrows.load(row, (32 * ks + 8 * q4o) / EPL + u);
+        load_row_pieces(qrows, c * C + 16 * qt + r, q4, rq);       // this wave's query row on this lane
     };
     bf16x8 ones;
 #pragma unroll
@@ -71,24 +67,7 @@ __global__ __launch_bounds__(512, 1) void fwd_p1_mfma_d128_2p_kernel(D128Params 
     const int c_begin = seg * prm.cps, c_end = min(nchunks, c_begin + prm.cps);
     f32x4 s2acc[MT];               // S2[16mt + 4q4 + reg][16w + r]
     f32x4 s1acc, ksacc;            // S1[16w + r] (row 0), ksum[16w + 4q4 + reg] (column 0)
-    auto publish = [&]() {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            bf16x4 hi, lo;
-            split4(s2acc[mt] * a, hi, lo);
-            const int off = img_off<DP>(16 * w + r, 2 * mt + (q4 >> 1)) + ((q4 & 1) << 3);
-            *reinterpret_cast<bf16x4*>(smem + S2I + off) = hi;
-            *reinterpret_cast<bf16x4*>(smem + S2I + SIMG + off) = lo;
-        }
-        if (r == 0) {
-            bf16x4 hi, lo;
-            split4(ksacc * a, hi, lo);
-            const int off = img_off<DP>(DP, 2 * w + (q4 >> 1)) + ((q4 & 1) << 3);
-            *reinterpret_cast<bf16x4*>(smem + S2I + off) = hi;
-            *reinterpret_cast<bf16x4*>(smem + S2I + SIMG + off) = lo;
-        }
-        if (q4 == 0) reinterpret_cast<float*>(smem + S1V)[16 * w + r] = s1acc[0];
-    };
+    auto publish = [&]() { scan128::publish<S2I, SIMG>(smem, wl, s2acc, s1acc, ksacc, a); };
     for (int i = tid; i < (2 * SIMG) / 16; i += 512) *reinterpret_cast<f32x4*>(smem + S2I + 16 * i) = f32x4{0, 0, 0, 0};
     if (tid < DP) reinterpret_cast<float*>(smem + S1V)[tid] = 0.f;
     s1acc = f32x4{0, 0, 0, 0};
@@ -279,28 +258,12 @@ __global__ __launch_bounds__(512, 1) void fwd_p1_mfma_d128_2p_kernel(D128Params 
     }
 }
 
-template <typename TIN, bool NORM, bool BUF>
-static int launch_d128_2p_b(const D128Params& prm, int nb, hipStream_t stream) {
-    constexpr int DP = 128;
-    constexpr int lds = 4 * 64 * DP * 2 + 2 * (DP + 16) * DP * 2 + DP * 4;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = fwd_p1_mfma_d128_2p_kernel<TIN, NORM, BUF>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, stream, prm);
-    return (int)hipGetLastError();
-}
-
 template <typename TIN, bool NORM>
 static int launch_d128_2p_t(const D128Params& prm, int nb, hipStream_t stream) {
-    // K / V tiles through buffer descriptors when a (b,h) slab fits their 31-bit offsets
-    const bool buf = quad32_span_ok(prm.ks.sn, prm.N, prm.D, (int)sizeof(TIN)) && quad32_span_ok(prm.vs.sn, prm.N, prm.D, (int)sizeof(TIN)) &&
-                     quad32_span_ok(prm.qs.sn, prm.N, prm.D, (int)sizeof(TIN));
-    return buf ? launch_d128_2p_b<TIN, NORM, true>(prm, nb, stream) : launch_d128_2p_b<TIN, NORM, false>(prm, nb, stream);
+    constexpr int lds = 4 * scan128::IMG + 2 * (scan128::DP + 16) * scan128::DP * 2 + scan128::DP * 4;
+    if (scan128::buf_route<TIN>(prm.qs, prm.ks, prm.vs, prm.N, prm.D))
+        return scan128::launch512<fwd_p1_mfma_d128_2p_kernel<TIN, NORM, true>, lds>(prm, nb, stream);
+    return scan128::launch512<fwd_p1_mfma_d128_2p_kernel<TIN, NORM, false>, lds>(prm, nb, stream);
 }
 
 bool mfma_d128_2p_supported(const fastmax_problem& p) {

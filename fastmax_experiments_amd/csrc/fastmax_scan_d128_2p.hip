@@ -12,7 +12,7 @@
 // 64 x 64 tile inside the chunk, x rows straight from global memory into B fragments, no (N,D,D) temporaries.  The fused
 // two-kernel form used at D <= 64 (fastmax_mfma_bwd_lin.hip) needs four hi/lo images + the state = more than 160 KB here.
 // Cost: 9 tensor reads + 3 writes instead of 5 + 3, against the O(N^2) tiles these shapes fell back to before.
-#include "fastmax_mfma_common.h"
+#include "fastmax_scan128.h"
 
 namespace fastmax {
 
@@ -66,15 +66,17 @@ __global__ __launch_bounds__(512, 1) void scan_d128_2p_kernel(ScanParams prm) {
     static_assert(InTraits<TIN>::NP == 2, "two-part operands");
     constexpr bool REV = MODE != SCAN_DQ;
     constexpr bool XSCALE = MODE == SCAN_DQ, YSCALE = MODE == SCAN_DK, ZSCALE = MODE == SCAN_DV;
-    constexpr int DP = 128, C = 64, IMG = C * DP * 2, SIMG = DP * DP * 2;
+    using namespace scan128;
+    constexpr int SIMG = DP * DP * 2;
     constexpr int YI = 0, ZI = NP * IMG, S2I = 2 * NP * IMG, S1V = S2I + 2 * SIMG, EV = S1V + DP * 4;    // EV: e of the chunk's 64 rows
     constexpr int COLS = DP / EPL, RPP = 512 / COLS, NPASS = C / RPP;
-    constexpr int KS = DP / 32, MT = DP / 16, QL = 8 / EPL;
+    constexpr int QL = 8 / EPL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qt = w & 3, dh = w >> 2;
     const int r = lane & 15, q4 = lane >> 4;
+    const WaveLane wl{w, r, q4};
     const int bh = blockIdx.x / prm.nseg, seg = blockIdx.x - bh * prm.nseg, b = bh / prm.H, h = bh % prm.H;
     const int N = prm.N, D = prm.D;
     if constexpr (STATE_ONLY) {
@@ -98,12 +100,7 @@ __global__ __launch_bounds__(512, 1) void scan_d128_2p_kernel(ScanParams prm) {
         zload.load(c, rz);
         const int row = c * C + 16 * qt + r;                       // this wave's output row on this lane
         if constexpr (!STATE_ONLY) {
-            int q4o = q4;                                          // opaque: piece offsets re-formed per chunk (see fastmax_mfma_d128_2p.hip)
-            asm volatile("" : "+v"(q4o));
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int u = 0; u < QL; ++u) rx[ks][u] = xrows.load(row, (32 * ks + 8 * q4o) / EPL + u);
+            load_row_pieces(xrows, row, q4, rx);
         }
         if constexpr (YSCALE || ZSCALE) {
 #pragma unroll
@@ -128,17 +125,7 @@ __global__ __launch_bounds__(512, 1) void scan_d128_2p_kernel(ScanParams prm) {
     f32x4 s2acc[MT];               // S2[y index 16mt + 4q4 + reg][z index 16w + r]
     f32x4 s1acc;                   // S1[16w + r] (row 0)
     const float beta = prm.beta;
-    auto publish = [&]() {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            bf16x4 hi, lo;
-            split4(s2acc[mt] * beta, hi, lo);
-            const int off = img_off<DP>(16 * w + r, 2 * mt + (q4 >> 1)) + ((q4 & 1) << 3);
-            *reinterpret_cast<bf16x4*>(smem + S2I + off) = hi;
-            *reinterpret_cast<bf16x4*>(smem + S2I + SIMG + off) = lo;
-        }
-        if (q4 == 0) reinterpret_cast<float*>(smem + S1V)[16 * w + r] = s1acc[0];
-    };
+    auto publish = [&]() { scan128::publish<S2I, SIMG>(smem, wl, s2acc, s1acc, /* no ksum row: not read */ s1acc, beta); };
     s1acc = f32x4{0, 0, 0, 0};
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) s2acc[mt] = f32x4{0, 0, 0, 0};
@@ -337,28 +324,12 @@ __global__ __launch_bounds__(512, 1) void scan_d128_2p_kernel(ScanParams prm) {
     }
 }
 
-template <typename TIN, int MODE, bool STATE_ONLY, bool BUF>
-static int launch_scan_kb(const ScanParams& prm, int nb, hipStream_t stream) {
-    constexpr int DP = 128;
-    constexpr int lds = 4 * 64 * DP * 2 + 2 * DP * DP * 2 + DP * 4 + 256;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = scan_d128_2p_kernel<TIN, MODE, STATE_ONLY, BUF>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, stream, prm);
-    return (int)hipGetLastError();
-}
-
 template <typename TIN, int MODE, bool STATE_ONLY>
 static int launch_scan_k(const ScanParams& prm, int nb, hipStream_t stream) {
-    // streamed y / z tiles through buffer descriptors when a (b,h) slab fits their 31-bit offsets
-    const bool buf = quad32_span_ok(prm.ys.sn, prm.N, prm.D, (int)sizeof(TIN)) && quad32_span_ok(prm.zs.sn, prm.N, prm.D, (int)sizeof(TIN)) &&
-                     quad32_span_ok(prm.xs.sn, prm.N, prm.D, (int)sizeof(TIN));
-    return buf ? launch_scan_kb<TIN, MODE, STATE_ONLY, true>(prm, nb, stream) : launch_scan_kb<TIN, MODE, STATE_ONLY, false>(prm, nb, stream);
+    constexpr int lds = 4 * scan128::IMG + 2 * scan128::DP * scan128::DP * 2 + scan128::DP * 4 + 256;
+    if (scan128::buf_route<TIN>(prm.xs, prm.ys, prm.zs, prm.N, prm.D))
+        return scan128::launch512<scan_d128_2p_kernel<TIN, MODE, STATE_ONLY, true>, lds>(prm, nb, stream);
+    return scan128::launch512<scan_d128_2p_kernel<TIN, MODE, STATE_ONLY, false>, lds>(prm, nb, stream);
 }
 
 // one scan: with a sequence split, the segments' own sums first
@@ -405,8 +376,6 @@ static int launch_scan_bwd_t(const BwdArgs& a) {
     scan_split_plan(p, nseg, cps);
     hipLaunchKernelGGL((scan_prep_kernel<TIN>), dim3((p.Nq + 3) / 4, BH), dim3(256), 0, a.stream, a.grad_o, a.gos, a.o, a.g, wbuf, ebuf,
                        p.H, p.Nq, p.D);
-    const Strides3 os{(int64_t)p.H * p.Nq * p.D, (int64_t)p.Nq * p.D, (int64_t)p.D};
-    (void)os;
     // dQ: x = grad_o (scaled by w), y = v, z = k
     ScanParams dq{a.grad_o, a.v, a.k, a.gos, a.vs, a.ks, a.dq, wbuf, ebuf, p.H, p.Nq, p.D, p.in_dtype, 1.0f, p.a, state, nseg, cps};
     int rc = launch_scan_t<TIN, SCAN_DQ>(dq, BH, a.stream);
