@@ -1,4 +1,5 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI, set on one handle.
+The adapter-v2 side header (ADAPTER_HEADER) has the table ADAPTER_ABI, set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -173,6 +174,16 @@ ABI = {
     "fastmax_hip_last_logits_nf4": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
 }
 SYMBOLS = list(ABI)
+# adapter-v2 fine-tuning's side header (the per-column scale and bias behind a linear, forward and backward): same library, same
+# FASTMAX_ABI_VERSION (additions only), a table of its own until it is folded into ABI.  tests/test_adapter_v2_cpu.py checks
+# each row against the prototype.
+ADAPTER_HEADER = "fastmax_hip_adapter.h"
+ADAPTER_ROWS_PER_BLOCK = 64                     # FASTMAX_ADAPTER_ROWS_PER_BLOCK
+ADAPTER_ABI = {
+    "fastmax_hip_adapter_forward": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
+    "fastmax_hip_adapter_backward_workspace": (sz, [ci, ci, ci, ci]),
+    "fastmax_hip_adapter_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -186,11 +197,12 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.items():
-        if not hasattr(L, name):
-            raise RuntimeError(f"libfastmax_hip.so does not export {name}")
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (ABI, ADAPTER_ABI):
+        for name, (restype, argtypes) in table.items():
+            if not hasattr(L, name):
+                raise RuntimeError(f"libfastmax_hip.so does not export {name}")
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     if L.fastmax_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libfastmax_hip.so ABI version mismatch")
     _lib = L

@@ -28,15 +28,21 @@ class AttentionStack(nn.Module):
     ``block="full"``: n_layer whole decoder blocks (block.py: RMSNorm, attention, RMSNorm, gated MLP at the config's
     intermediate_size, both residual adds) in place of the bare attention sub-layers.  ``block="neox"``: n_layer whole
     parallel-residual blocks (neox_block.py: the LayerNorm pair, attention, the GELU MLP, the three-way add), what the pythia
-    configs are."""
+    configs are.  ``method="adapter_v2"``: the same blocks without a LoRA branch, every linear an ``AdapterV2Linear`` and the
+    adapter parameters and the norms trainable (finetune/adapter_v2.py), in place of the default ``"lora"``."""
 
     def __init__(self, config: str, n_layer: int, attn_alg: str, vocab: int = 32000, r: int = 8, alpha: int = 16,
-                 lora_dropout: float = 0.05, block: str = "attention"):
+                 lora_dropout: float = 0.05, block: str = "attention", method: str = "lora"):
         """r, alpha, lora_dropout: the reference's fine-tune defaults (finetune/lora.py:40-42)"""
         super().__init__()
         from .attention_block import CONFIG_SHAPES, CausalSelfAttention
         if block not in ("attention", "full", "neox"):
             raise ValueError(f"block should be 'attention', 'full' or 'neox', got {block!r}")
+        if method not in ("lora", "adapter_v2"):
+            raise ValueError(f"method should be 'lora' or 'adapter_v2', got {method!r}")
+        self.method = method
+        if method == "adapter_v2":
+            r, lora_dropout = 0, 0.0
         shape = CONFIG_SHAPES[config]
         self.n_embd = shape["n_embd"]
         self.block = block
@@ -50,12 +56,32 @@ class AttentionStack(nn.Module):
                                         for _ in range(n_layer))
         else:
             self.blocks = nn.ModuleList(CausalSelfAttention(attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout, **shape) for _ in range(n_layer))
-        for b in self.blocks:
-            attn = b if block == "attention" else b.attn
-            nn.init.normal_(attn.attn.lora_B, std=0.02)           # a non-zero branch, so every LoRA gradient is exercised
+        if method == "adapter_v2":
+            self._adapt()
+        else:
+            for b in self.blocks:
+                attn = b if block == "attention" else b.attn
+                nn.init.normal_(attn.attn.lora_B, std=0.02)       # a non-zero branch, so every LoRA gradient is exercised
         g = torch.Generator().manual_seed(1234)
         self.lm_head = nn.Parameter(torch.randn(vocab, self.n_embd, generator=g) * 0.02, requires_grad=False)
         self.rope_n_elem = (self.blocks[0] if block == "attention" else self.blocks[0].attn).rope_n_elem
+
+    def _adapt(self):
+        """the adapter-v2 form of the blocks: every linear adapted, only adapter parameters and norms trainable, and a seeded
+        start away from scale 1 and bias 0, so every adapter gradient is exercised"""
+        from .adapter_v2 import AdapterV2Linear, adapt, mark_only_adapter_v2_as_trainable
+        adapt(self.blocks)
+        mark_only_adapter_v2_as_trainable(self.blocks)
+        g = torch.Generator().manual_seed(4321)
+        for m in self.blocks.modules():
+            if isinstance(m, AdapterV2Linear):
+                # float32 master parameters, as the LoRA matrices of the default method are: a step of 1e-4 on a scale near 1 is
+                # below half a bfloat16 unit and would be lost in a 16-bit parameter
+                m.cast_params = True
+                m.adapter_scale.data, m.adapter_bias.data = m.adapter_scale.data.float(), m.adapter_bias.data.float()
+                with torch.no_grad():
+                    m.adapter_scale.add_(torch.randn(m.adapter_scale.shape, generator=g) * 0.02)
+                    m.adapter_bias.add_(torch.randn(m.adapter_bias.shape, generator=g) * 0.02)
 
     def prepare(self, device, quantize: bool = True):
         if quantize:
@@ -100,10 +126,10 @@ class ToyLoRA(nn.Module):
 
 def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, accum: int, steps: int, warmup: int, device,
         rank: int = 0, world: int = 1, toy: bool = False, precondition_ms: float = 0.0, graph: bool = False,
-        lora_dropout: float = 0.05, block: str = "attention", optimizer: str = "torch") -> dict:
+        lora_dropout: float = 0.05, block: str = "attention", optimizer: str = "torch", method: str = "lora") -> dict:
     """`warmup` untimed + `steps` timed optimizer steps; -> timings (seconds / milliseconds, this rank).
     ``optimizer``: "torch" (torch.optim.AdamW after the bucket's all-reduce-mean) or "flat" (optim.FlatAdamW: the boundary as one
-    pass over the flat bucket)."""
+    pass over the flat bucket).  ``method``: "lora", or "adapter_v2" (``AttentionStack``)."""
     if optimizer not in ("torch", "flat"):
         raise ValueError(f"optimizer should be 'torch' or 'flat', got {optimizer!r}")
     on_gpu = device.type == "cuda"
@@ -116,12 +142,12 @@ def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, ac
         cos = sin = None
     else:
         from .attention_block import build_rope_cache
-        model = AttentionStack(config, n_layer, attn_alg, lora_dropout=lora_dropout, block=block).prepare(device)
+        model = AttentionStack(config, n_layer, attn_alg, lora_dropout=lora_dropout, block=block, method=method).prepare(device)
         model.train()
         x = torch.randn(accum, micro_batch, seq, model.n_embd, device=device, generator=gen).to(torch.bfloat16)
         tgt = torch.randint(0, model.lm_head.shape[0], (accum, micro_batch, seq), device=device, generator=gen)
         cos, sin = (t.to(torch.bfloat16) for t in build_rope_cache(seq, model.rope_n_elem, device=device))
-    params = dp.trainable_lora_parameters(model)
+    params = dp.trainable_lora_parameters(model) if method == "lora" else [p for p in model.parameters() if p.requires_grad]
     if optimizer == "flat":
         from .optim import FlatAdamW
         opt = FlatAdamW(dp.FlatGradBucket(params), lr=1e-4)

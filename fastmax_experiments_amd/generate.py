@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
+from .adapter_v2 import AdapterV2Linear, adapter_forward
 from .block import BlockStack, RMSNorm, rms_norm_forward
 from .lora import NF4Linear, Params4bit, scales_cached, scales_of
 from .neox_block import LayerNorm, NeoXStack, layer_norm_forward
@@ -227,7 +228,10 @@ class NextTokenHead(nn.Module):
     ``padded_vocab_size`` rows of the weight are scored; the default is all of them, which is what the reference samples over.
     ``norm_class``: "RMSNorm", or "LayerNorm" (the pythia models; state-dict keys ``ln_f.weight`` and ``ln_f.bias``).
     ``lm_head_bias``: the reference's ``config.lm_head_bias`` (the Phi models; state-dict key ``lm_head.bias``).
-    ``quantize_base()`` stores ``lm_head`` as NF4 codes, as the reference's quantised runs do with every linear of the model."""
+    ``quantize_base()`` stores ``lm_head`` as NF4 codes, as the reference's quantised runs do with every linear of the model.
+    After ``adapter_v2.adapt`` ``lm_head`` is an ``AdapterV2Linear`` (state-dict keys ``lm_head.linear.weight``,
+    ``lm_head.adapter_scale`` ...): the score comes from its ``linear`` as before, then one pass of csrc/adapter_v2.hip scales
+    and shifts the float32 logits."""
 
     def __init__(self, n_embd: int, padded_vocab_size: int, vocab_size: int = None, norm_eps: float = 1e-5,
                  add_unit_offset: bool = False, norm_class: str = "RMSNorm", lm_head_bias: bool = False) -> None:
@@ -248,20 +252,43 @@ class NextTokenHead(nn.Module):
     def quantize_base(self, double_quant: bool = False) -> "NextTokenHead":
         """``lm_head`` becomes an ``NF4Linear`` of the same weight (block 64; ``double_quant``: 8-bit block scales), the bias
         stays; the state-dict keys are ``NF4Linear``'s.  Called again, nothing happens; the other scale form is refused."""
-        if isinstance(self.lm_head, NF4Linear):
-            if self.lm_head.double_quant != bool(double_quant):
+        lin = self._linear()
+        if isinstance(lin, NF4Linear):
+            if lin.double_quant != bool(double_quant):
                 raise ValueError(f"NextTokenHead.quantize_base: lm_head is already quantised with double_quant="
-                                 f"{self.lm_head.double_quant}")
+                                 f"{lin.double_quant}")
             return self
-        if self.lm_head.in_features % 64:
+        if lin.in_features % 64:
             raise ValueError(f"NextTokenHead.quantize_base: n_embd should be a multiple of 64 (one NF4 block lies inside one row "
-                             f"of the weight), got {self.lm_head.in_features}")
-        self.lm_head = NF4Linear.from_linear(self.lm_head, double_quant=bool(double_quant))
+                             f"of the weight), got {lin.in_features}")
+        if isinstance(self.lm_head, AdapterV2Linear):
+            self.lm_head.linear = NF4Linear.from_linear(lin, double_quant=bool(double_quant))
+        else:
+            self.lm_head = NF4Linear.from_linear(lin, double_quant=bool(double_quant))
         return self
+
+    def _linear(self):
+        """the layer that scores: ``lm_head``, or the ``linear`` inside an adapted one"""
+        return self.lm_head.linear if isinstance(self.lm_head, AdapterV2Linear) else self.lm_head
+
+    def _adapter(self):
+        """the first ``vocab_size`` entries of an adapted lm_head's (scale, bias) in float32, the logits' dtype; a cast is
+        kept until a parameter changes, and refused while a stream is capturing, exactly as ``_bias`` is"""
+        ps = (self.lm_head.adapter_scale, self.lm_head.adapter_bias)
+        if all(p.dtype == torch.float32 for p in ps):
+            return tuple(p.detach()[:self.vocab_size] for p in ps)
+        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in ps) + (self.vocab_size,)
+        hit = self.__dict__.get("_adapter_cast")
+        if hit is None or hit[0] != key:
+            if ps[0].is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("NextTokenHead: the adapter's scale and bias have not been cast to float32 yet, and a copy made "
+                                   "while a stream is capturing would belong to that graph; score once eagerly before the recording")
+            hit = self.__dict__["_adapter_cast"] = (key, tuple(p.detach()[:self.vocab_size].float() for p in ps))
+        return hit[1]
 
     def _bias(self, dtype):
         """lm_head's bias in ``dtype`` (an NF4Linear keeps it in float32), or None; the cast is kept until the bias changes"""
-        b = self.lm_head.bias
+        b = self._linear().bias
         if b is None or b.dtype == dtype:
             return None if b is None else b.detach()
         key = (b.data_ptr(), b._version, dtype, b.device)
@@ -277,21 +304,32 @@ class NextTokenHead(nn.Module):
         """x (B, T, C) or (B, C) -> the logits (B, vocab_size) of the last position"""
         if x.dim() not in (2, 3):
             raise ValueError(f"NextTokenHead: x should be (B, T, C) or (B, C), got {tuple(x.shape)}")
-        nf4 = isinstance(self.lm_head, NF4Linear)
+        lin = self._linear()
+        nf4, adapted = isinstance(lin, NF4Linear), lin is not self.lm_head
         if not self.fused:
             n = self.ln_f._eager(x)
-            y = F.linear(n, self.lm_head.dequantize(n.dtype), self._bias(n.dtype)) if nf4 else self.lm_head(n)
+            y = F.linear(n, lin.dequantize(n.dtype), self._bias(n.dtype)) if nf4 else lin(n)
+            if adapted:
+                y = self.lm_head.adapter_scale * (y + self.lm_head.adapter_bias)
             return (y[:, -1] if x.dim() == 3 else y)[:, :self.vocab_size].to(dtype)
+        if adapted:
+            if dtype != torch.float32:
+                raise TypeError(f"NextTokenHead: an adapted lm_head gives float32 logits, got dtype={dtype}")
+            return adapter_forward(self._scores(x, lin, nf4, dtype), *self._adapter())
+        return self._scores(x, lin, nf4, dtype)
+
+    def _scores(self, x, lin, nf4, dtype):
+        """the last position's scores of ``lin`` through the last_logits entry points"""
         last = x[:, -1] if x.dim() == 3 else x
         if isinstance(self.ln_f, LayerNorm):
             _, n, _, _, _ = layer_norm_forward(last, self.ln_f.weight.detach(), self.ln_f.bias.detach(), self.ln_f.eps)
         else:
             _, n, _ = rms_norm_forward(last, None, self.ln_f.weight.detach(), self.ln_f.eps, self.ln_f.add_unit_offset)
         if nf4:
-            return last_logits(n, self.lm_head, dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
-        if self.lm_head.bias is not None:
-            return last_logits(n, self.lm_head.weight.detach(), dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
-        return last_logits(n, self.lm_head.weight.detach()[:self.vocab_size], dtype)
+            return last_logits(n, lin, dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
+        if lin.bias is not None:
+            return last_logits(n, lin.weight.detach(), dtype, bias=self._bias(n.dtype), rows=self.vocab_size)
+        return last_logits(n, lin.weight.detach()[:self.vocab_size], dtype)
 
     def forward(self, x: torch.Tensor, sampler: Sampler, temperature: float = 1.0, top_k=None, top_p=None) -> torch.Tensor:
         """-> (B,) int64 tokens"""
