@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI, set on one handle.
-The adapter-v2 side header (ADAPTER_HEADER) has the table ADAPTER_ABI, set on the same handle.
+The adapter-v2 side header (ADAPTER_HEADER) has the table ADAPTER_ABI, the KV-cache decode header (KV_DECODE_HEADER) the table
+KV_DECODE_ABI, both set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -184,6 +185,18 @@ ADAPTER_ABI = {
     "fastmax_hip_adapter_backward_workspace": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_adapter_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
 }
+# the KV-cache decode route's side header (csrc/fastmax_kv_decode.hip): same library, same FASTMAX_ABI_VERSION (additions only), a
+# table of its own.  tests/test_kv_decode_cpu.py checks each row against the prototype.
+KV_DECODE_HEADER = "fastmax_hip_kv_decode.h"
+KV_CHUNK, KV_SLICE, KV_MAX_D = 128, 8, 256      # FASTMAX_KV_CHUNK, FASTMAX_KV_SLICE, FASTMAX_KV_MAX_D
+KV_LEN, KV_OVERFLOW, KV_HEADER_WORDS = 0, 1, 16  # enum fastmax_kv_word
+KV_DECODE_ABI = {
+    "fastmax_hip_kv_decode_state_bytes": (sz, [ci, ci, ci, ci, ci]),
+    "fastmax_hip_kv_decode_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
+    "fastmax_hip_kv_decode_load": (ci, [vp, i64p, vp, i64p, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_kv_decode_append_attend": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+    "fastmax_hip_kv_decode_set_len": (ci, [vp, ci, ci, vp]),
+}
 
 _lib = None
 
@@ -197,7 +210,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, ADAPTER_ABI):
+    for table in (ABI, ADAPTER_ABI, KV_DECODE_ABI):
         for name, (restype, argtypes) in table.items():
             if not hasattr(L, name):
                 raise RuntimeError(f"libfastmax_hip.so does not export {name}")

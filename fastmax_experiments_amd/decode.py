@@ -32,6 +32,10 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
            S2 = sum_j kc_j v_j^T,  S1 = sum_j v_j,  ksum = sum_j kc_j     (sums over j <= i)
        so the two statistics leave the bilinear sums as one scalar: a state of unscaled centred sums never needs rescaling,
        only a moves as the two running maxima grow.  O(D^2) per token and about 70 KB per KV head at D = 128.
+
+  KV cache  `FastmaxKVDecodeState` (csrc/fastmax_kv_decode.hip): the K and V rows themselves, the length a device word, and masked
+       fastmax over the live prefix at every new position: O(N D) per token like the reference's cache, but the masked function,
+       grouped-query heads on one K/V read, and head sizes up to 256, where the carried states stop at 128.  Opt-in like the rest.
 """
 import ctypes
 
@@ -64,6 +68,15 @@ class _DecodeState:
         """Empty sequence again; the allocation is kept (a generation loop resets between prompts)."""
         self.state.zero_()
         self.count = 0
+
+    def _restore(self, state, count):
+        """back to a saved (``state.clone()``, ``count``) pair: what a graph recording does after its warm-up steps"""
+        self.state.copy_(state)
+        self.count = count
+
+    def _replayed(self, steps):
+        """``steps`` single-token steps ran from a recorded graph, which moves no host counter: the mirror follows"""
+        self.count += steps
 
     # qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): one HIP pass where the split kernel takes
     # the shape, else tensor slicing + apply_rope (model.py:397-425)
@@ -231,6 +244,129 @@ class FastmaxDecodeState(_DecodeState):
 
     def _prefill_qkv(self, q, k, v):
         return self.prefill(q, k, v, chunk=self.prefill_chunk)     # None: the one-shot masked forward + state capture
+
+
+class FastmaxKVDecodeState(_DecodeState):
+    """KV-cache decode for fastmax blocks (csrc/fastmax_kv_decode.hip, include/fastmax_hip_kv_decode.h): the K and V rows of up to
+    ``max_len`` tokens in ``dtype`` (the activations'), and at each new position masked polynomial attention
+    o = sum_j f(s_j) v_j / sum_j f(s_j) over the cached rows and the new ones, in float32.  Head sizes 1 .. 256: the two config
+    shapes with 256-wide heads (pythia-1b, Gemma-2b) generate on this class only.  Per token it reads the live prefix of the
+    cache, 4 D bytes per bf16 position, where the second-order state moves (D+1)(D+2)/2 (D+1) floats whatever the length; the
+    measured crossover lengths are in profiles/r23_kv_decode.md.  Opt-in: nothing selects it automatically.
+
+    q (B,H,T,D); k and v (B,n_query_groups,T,D) at their KV heads: one read of a K/V row serves the group's query heads.
+    ``state`` is ONE tensor: a 64-byte header (int32 words: the length, a sticky overflow flag) and both caches, so a
+    ``clone()`` / ``copy_()`` pair saves and restores everything.  The length the kernels use is the header's; ``count`` is the
+    host's mirror of it and nothing is ever read back.  A row's output bits depend on its q row and the cache prefix alone: not on
+    B, the batch row, T (a token fed alone or inside an ``extend``), ``max_len``, the inputs' strides or eager / replayed."""
+
+    _count = 0
+
+    def __init__(self, B, H, D, device, max_len, dtype, p=2, n_query_groups=None, normalize_term=8, tensors_normalized=False):
+        if p not in (1, 2):
+            raise ValueError(f"p should be 1 or 2, got p={p}")
+        Hkv = H if n_query_groups is None else n_query_groups
+        if Hkv <= 0 or H % Hkv != 0:
+            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+        if dtype not in ops._DT:
+            raise ValueError(f"the KV decode cache holds float32, bfloat16 or float16, got {dtype}")
+        if int(max_len) != max_len or max_len < 1 or max_len >= 2 ** 31:
+            raise ValueError(f"max_len should be a number of tokens in 1 .. 2^31 - 1, got {max_len}")
+        self.p, self.dtype, self.max_len = p, dtype, int(max_len)
+        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
+        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
+        nbytes = _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[dtype])
+        if nbytes and torch.device(device).type != "cuda":
+            raise RuntimeError("the KV decode cache lives on an MI355X (HIP device); there is no CPU path through the kernels")
+        super().__init__(B, H, Hkv, D, nbytes, device,
+                         f"KV decode cache: batch {B} x {Hkv} KV heads of size {D} not supported (head sizes 1 .. {_lib.KV_MAX_D}, "
+                         f"B * n_query_groups <= 65535)")
+        self.capacity = -(-self.max_len // _lib.KV_CHUNK) * _lib.KV_CHUNK       # positions allocated: max_len up to a whole chunk
+
+    @classmethod
+    def for_attention(cls, attn, B, max_len, device, dtype):
+        """the cache of a ``CausalSelfAttention`` (``attn_alg="fastmax"``: the block's p = 2 with its default scaling)"""
+        return cls(B, attn.n_head, attn.head_size, device, max_len, dtype, p=2, n_query_groups=attn.n_query_groups)
+
+    @property
+    def header(self):
+        """the header's int32 words, a view of ``state`` (reading them synchronises)"""
+        return self.state[:_lib.KV_HEADER_WORDS].view(torch.int32)
+
+    @property
+    def count(self):
+        return self._count
+
+    @count.setter
+    def count(self, n):
+        """a smaller value truncates the cache (one small device write; the rows stay and are overwritten); a larger one raises"""
+        n = int(n)
+        if n < 0 or n > self._count:
+            raise ValueError(f"count can only be lowered (a truncation): the cache holds {self._count} tokens, got {n}")
+        if n < self._count:
+            ops._call("fastmax_hip_kv_decode_set_len", self.state.device, (self.state.data_ptr(), n, self.max_len))
+        self._count = n
+
+    def reset(self):
+        """Empty sequence again: the header is cleared, the rows stay where they are."""
+        self.state[:_lib.KV_HEADER_WORDS].zero_()
+        self._count = 0
+
+    def _restore(self, state, count):
+        self.state.copy_(state)          # the header's length with it
+        self._count = count
+
+    def _replayed(self, steps):
+        self._count += steps
+
+    def _inputs(self, q, k, v, T):
+        self._check_shapes(q, k, v, T)
+        if not (q.dtype == k.dtype == v.dtype == self.dtype):
+            raise TypeError(f"the cache holds {self.dtype}, got q {q.dtype}, k {k.dtype}, v {v.dtype}")
+        if self._count + T > self.max_len:
+            raise ValueError(f"the cache holds {self._count} of at most {self.max_len} tokens, {T} more do not fit")
+        dev = self.state.device
+        # the kernels take any strides with unit stride in D (views of the split's output as they are)
+        return tuple(t if t.stride(3) == 1 else t.contiguous() for t in (x.to(dev) for x in (q, k, v)))
+
+    def prefill(self, q, k, v):
+        """Masked forward over the prompt (the tile kernels), o (B,H,T,D); the cache then holds the prompt's K and V rows."""
+        assert self._count == 0, "prefill starts a sequence"
+        T = q.shape[2] if q.dim() == 4 else 0
+        if T < 1:
+            raise ValueError(f"prefill takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        qd, kd, vd = self._inputs(q, k, v, T)
+        with torch.no_grad():
+            o = self._masked_forward(lambda *qkv: fastmax(*qkv, mask=True, p=self.p, **self._kw), qd, kd, vd)
+        ops._call("fastmax_hip_kv_decode_load", self.state.device,
+                  (*ops._qkv(kd, vd), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
+        self._count = T
+        return o
+
+    def step(self, q, k, v):
+        """q (B,H,1,D), k and v (B,n_query_groups,1,D) of the new token -> o (B,H,1,D): the rows join the cache, one pass over
+        its live prefix serves every query head of a group."""
+        return self._append_attend(q, k, v, 1)
+
+    def extend(self, q, k, v):
+        """T >= 1 new tokens after the ``count`` cached ones (any count, 0 included) -> o (B,H,T,D) = masked attention at the T
+        new positions; bit for bit what T single steps give."""
+        T = q.shape[2] if q.dim() == 4 else 0
+        if T < 1:
+            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        return self._append_attend(q, k, v, T)
+
+    def _append_attend(self, q, k, v, T):
+        qd, kd, vd = self._inputs(q, k, v, T)
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        dev = self.state.device
+        o = torch.empty((B, H, T, D), dtype=self.dtype, device=dev)
+        ops._call("fastmax_hip_kv_decode_append_attend", dev,
+                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), B, H, Hkv, T, D, self.max_len, ops._DT[self.dtype],
+                   self.p, 1.0 / self.nt),
+                  ws=_lib.lib().fastmax_hip_kv_decode_workspace(B, H, Hkv, T, D, self.max_len))
+        self._count += T
+        return o
 
 
 class LinearmaxDecodeState(_DecodeState):

@@ -363,6 +363,17 @@ def _layers_and_run(blocks, states):
     return layers, run
 
 
+def _check_kv_capacity(states, fed, what):
+    """a KV decode cache cannot hold more than its ``max_len`` tokens: refuse before anything runs"""
+    from .decode import FastmaxKVDecodeState
+    for s in states:
+        if isinstance(s, FastmaxKVDecodeState) and fed > s.max_len:
+            raise ValueError(f"{what}: {fed} tokens are fed, a FastmaxKVDecodeState of this call holds at most {s.max_len}")
+
+
+_RECORDING_STEPS = 3          # GraphedDecoder._capture: two eager steps, then the recorded one
+
+
 class DecodeCursor:
     """The device record of include/fastmax_hip_cursor.h (csrc/decode_cursor.hip): the position of the next token to feed, the
     sampler's seed and draw number and a sticky overflow flag, advanced by the kernels themselves.  ``feed`` starts a decode step
@@ -444,6 +455,8 @@ class GraphedDecoder:
     the host.  An ``LLaMAMoE`` is taken with ``device_routed`` set on every one of them (quantized experts) and a batch of at most
     16 in bfloat16 or float32: its decode step then runs on device-side row counts; the two eager warm-up steps before the
     recording build each layer's expert table, which cannot be built inside it.  The prompt (B T > 16 rows) runs on the eager route.
+    A ``FastmaxKVDecodeState`` keeps its length in its own header, which every step's kernels read and the last one advances; it
+    needs room for ``max_len - 1`` tokens.
 
     ``captures``: graphs recorded so far (1 after the first call); ``replays``: graph launches so far, one per generated token
     after each call's first; ``poll``: with ``eos_id``, ``done`` is read back every ``poll`` replays instead of every token."""
@@ -452,12 +465,16 @@ class GraphedDecoder:
 
     def __init__(self, wte: torch.Tensor, blocks, head: NextTokenHead, states, *, cos, sin, max_len: int, temperature: float = 1.0,
                  top_k=None, eos_id=None, top_p=None) -> None:
-        from .decode import FastmaxDecodeState
+        from .decode import FastmaxDecodeState, FastmaxKVDecodeState
         _check_sampling(temperature, top_k, top_p)
         self._layers, self._run = _layers_and_run(blocks, states)
         if not len(states):
             raise ValueError("GraphedDecoder: no blocks")
+        _check_kv_capacity(states, max_len - 1, "GraphedDecoder")
         for s in states:
+            if isinstance(s, FastmaxKVDecodeState) and s.max_len <= _RECORDING_STEPS:
+                raise ValueError(f"GraphedDecoder: the recording runs {_RECORDING_STEPS} steps on a non-empty cache; a "
+                                 f"FastmaxKVDecodeState needs max_len > {_RECORDING_STEPS}, got {s.max_len}")
             if isinstance(s, FastmaxDecodeState) and s.p != 2:
                 raise NotImplementedError("GraphedDecoder: a first-order FastmaxDecodeState passes its token count to the step kernel "
                                           "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
@@ -510,9 +527,14 @@ class GraphedDecoder:
         """Record ``_step`` on the states as they are (non-empty: the blocks pick the single-token route from ``count > 0``).
         Two eager steps on a side stream first, so that every lazy initialisation of the step's own shapes happens outside the
         recording; then the recording on that same stream, one straight chain.  The warm-up advances the states and the recording
-        the host's counts: both are put back."""
+        the host's counts: both are put back.  A KV cache with less room than the recording's steps is taken back by that many
+        tokens first; the graph does not depend on the length, which its kernels read from the cache's header."""
         dev = self.tok.device
         saved = [(s.state.clone(), s.count) for s in self.states]
+        for s in self.states:
+            room = getattr(s, "max_len", None)
+            if room is not None and s.count + _RECORDING_STEPS > room:
+                s.count = room - _RECORDING_STEPS
         self.tok.zero_()
         self.cursor.arm(0, 0, 0)
         self._stream = torch.cuda.Stream(device=dev)
@@ -526,8 +548,7 @@ class GraphedDecoder:
             self._step()
         torch.cuda.current_stream(dev).wait_stream(self._stream)
         for s, (state, count) in zip(self.states, saved):
-            s.state.copy_(state)
-            s.count = count
+            s._restore(state, count)
         self.captures += 1
 
     @torch.no_grad()
@@ -542,6 +563,7 @@ class GraphedDecoder:
         if not self.head.fused:
             raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator; the graphed route needs the HIP sampler")
         _need_device(prompt, "GraphedDecoder.generate")
+        _check_kv_capacity(self.states, max_returned_tokens - 1, "GraphedDecoder.generate")
         sampler = Sampler() if sampler is None else sampler
         eos = self.eos_id
         pos = torch.arange(T, device=prompt.device)
@@ -578,7 +600,8 @@ class GraphedDecoder:
             if at:
                 n = T + 1 + at[0]
         for s in self.states:
-            s.count = n - 1                                                # the tokens the eager loop has fed
+            s._replayed(ran)                                               # the mirror of what the replays fed ...
+            s.count = n - 1                                                # ... back to what the eager loop has fed (a KV cache is cut)
         sampler.draws = first_draw + n - T
         return self.out[:, :n].clone()
 
@@ -599,7 +622,8 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
 
     ``wte`` is the embedding weight, ``blocks`` a ``BlockStack`` or a sequence of ``Block`` (a ``NeoXStack`` or a sequence of
     ``NeoXBlock`` for the parallel-residual form; one kind per call), ``states`` one EMPTY decode state
-    cache per block (``FastmaxDecodeState(p=2)`` / ``LinearmaxDecodeState``), ``cos`` / ``sin`` the rope cache with a row for
+    cache per block (``FastmaxDecodeState(p=2)`` / ``LinearmaxDecodeState``, or a ``FastmaxKVDecodeState`` with room for
+    ``max_returned_tokens - 1`` tokens), ``cos`` / ``sin`` the rope cache with a row for
     every position fed.  The prompt goes through the blocks in one call, then one token per call with the rope rows of its
     position.  Nothing is read back per token unless ``eos_id`` is given; then the loop ends once every row has produced it.
     ``graphed``: a ``GraphedDecoder`` built from these same arguments runs the loop as one graph replay per token; the default is
@@ -611,6 +635,7 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     B, T = _check_prompt(prompt, max_returned_tokens, cos, sin)
     _check_sampling(temperature, top_k, top_p)
     layers, run = _layers_and_run(blocks, states)
+    _check_kv_capacity(states, max_returned_tokens - 1, "generate")
     sampler = Sampler() if sampler is None else sampler
     dev = prompt.device
     pos = torch.arange(max_returned_tokens, device=dev)

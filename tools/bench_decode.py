@@ -8,7 +8,11 @@ decode state caches (p=1 and p=2).  Markdown to stdout.  `--p2`: the second-orde
 step beside the two-launch route (split + step), eager and as a HIP graph replay (`--no-graph`: eager only).
 `--block-case NAME,B,FUSED` runs ONE arm eagerly for a kernel trace (NAME: a key of attention_block.CONFIG_SHAPES).
 `--linearmax`: per-token time of `LinearmaxDecodeState.step` after 512- and 16384-token prompts, beside the masked linearmax
-forward over the whole prefix (the only route without the cache) and the second-order cache's step."""
+forward over the whole prefix (the only route without the cache) and the second-order cache's step.
+`--kv`: one step of the KV-cache decode route (`FastmaxKVDecodeState`) against one p=2 state step, both replayed from a graph and
+alternating in one process, at TinyLlama, Llama-2-7b and Gemma-2b head shapes, bf16, B 1 and 8, lengths 512 .. 32768.
+`--kv-trace ORDER.json` runs the same cells eagerly under `rocprofv3 --kernel-trace --stats`; `--kv-trace-table DIR ORDER.json`
+turns that trace into per-kernel times and bytes/s on the live cache prefix."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -292,9 +296,158 @@ def bench_linearmax():
                 del states, q, k, v, qg, kg, vg
 
 
+# ---- the KV-cache decode route against the second-order state ---------------------------------------------------------------
+KV_SHAPES = (("TinyLlama", 32, 4, 64, 22), ("Llama-2-7b", 32, 32, 128, 32), ("Gemma-2b", 8, 1, 256, 18))     # name, H, Hkv, D, layers
+KV_LENGTHS = (512, 2048, 8192, 32768)
+KV_BUDGET = 40 << 30          # bytes of caches per cell: fewer states than layers where a layer's cache is gigabytes
+KV_TRACE_STEPS = 3            # steps per state in the kernel-trace run
+
+
+def _kv_cells():
+    for name, H, Hkv, D, layers in KV_SHAPES:
+        for B in (1, 8):
+            for n in KV_LENGTHS:
+                live = B * Hkv * (n + 1) * 2 * D * 2                       # bf16 bytes a step reads: the issue's byte count
+                yield name, H, Hkv, D, B, n, live, max(2, min(layers, KV_BUDGET // (B * Hkv * (n + 128) * 2 * D * 2)))
+
+
+def _kv_states(H, Hkv, D, B, n, count):
+    """`count` KV caches holding the same n random tokens (written by the load entry point: no kernel of the step runs)"""
+    from fastmax_experiments_amd.decode import FastmaxKVDecodeState
+    k, v = (torch.randn(B, Hkv, n, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+    states = []
+    for _ in range(count):
+        st = FastmaxKVDecodeState(B, H, D, "cuda", n + 1, torch.bfloat16, n_query_groups=Hkv)
+        ops._call("fastmax_hip_kv_decode_load", st.state.device,
+                  (*ops._qkv(k, v), st.state.data_ptr(), B, Hkv, n, D, st.max_len, _lib.BF16))
+        st._count = n
+        states.append(st)
+    return states
+
+
+def _graph_of(fn):
+    side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn(); fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g.replay
+
+
+def bench_kv(rounds=7):
+    """One KV step against one p=2 state step, per layer: a graph of one step on each of `states` independent caches (one per
+    layer of the model, fewer where the caches would pass KV_BUDGET), replayed; the two routes alternate inside each round.
+    The KV graph takes every cache back to its length after the step (one one-thread launch per cache), so that every replay
+    reads the same prefix: its time is inside the KV column.  Event times; kernel times and rates come from `--kv-trace`."""
+    print("| shape (H, Hkv, D) | B | length | states | live cache MB/step | KV step us: median (min, spread) | state MB/step | "
+          "p=2 state step us: median (min, spread) | KV / state |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name, H, Hkv, D, B, n, live, count in _kv_cells():
+        q1 = torch.randn(B, H, 1, D, device="cuda").to(torch.bfloat16)
+        k1, v1 = (torch.randn(B, Hkv, 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+        kv = _kv_states(H, Hkv, D, B, n, count)
+
+        def kv_steps():
+            for st in kv:
+                st.step(q1, k1, v1)
+                st.count = n
+
+        arms = {"kv": None}
+        with torch.no_grad():
+            arms["kv"] = _graph_of(kv_steps)
+            sb = 0
+            if D <= 128:
+                p2 = [FastmaxDecodeState(B, H, D, device="cuda", p=2, n_query_groups=Hkv) for _ in range(count)]
+                qs, ks, vs = (torch.randn(B, h, 64, D, device="cuda").to(torch.bfloat16) for h in (H, Hkv, Hkv))
+                for st in p2:
+                    st.prefill(qs, ks, vs)
+                arms["state"] = _graph_of(lambda: [st.step(q1, k1, v1) for st in p2])
+                sb = 2 * B * Hkv * (D + 1) * (D + 2) // 2 * ((D + 4) // 4 * 4) * 4          # read and rewritten (bench_p2's count)
+            iters = max(2, min(200, int(4e9 / (live * count))))
+            ts = _alternate(arms, rounds, iters)
+        cells = {}
+        for a, t in ts.items():
+            us = [x * 1e3 / count for x in t]
+            med = statistics.median(us)
+            cells[a] = (med, f"{med:.1f} ({min(us):.1f}, {(max(us) - min(us)) / med * 100:.0f}%)")
+        state = f"{sb / 1e6:.2f} | {cells['state'][1]} | {cells['kv'][0] / cells['state'][0]:.2f}" if "state" in cells else "- | no such route | -"
+        print(f"| {name} ({H}, {Hkv}, {D}) | {B} | {n} | {count} | {live / 1e6:.1f} | {cells['kv'][1]} | {state} |", flush=True)
+        del kv, arms
+        torch.cuda.empty_cache()
+
+
+def kv_trace(path):
+    """for a `rocprofv3 --kernel-trace --stats` run: every cell of `--kv` in turn, KV_TRACE_STEPS eager steps on each cache (the
+    length taken back after each), and the cells' order written to `path` for `--kv-trace-table`"""
+    import json
+    order = []
+    with torch.no_grad():
+        for name, H, Hkv, D, B, n, live, count in _kv_cells():
+            count = min(count, 4)
+            q1 = torch.randn(B, H, 1, D, device="cuda").to(torch.bfloat16)
+            k1, v1 = (torch.randn(B, Hkv, 1, D, device="cuda").to(torch.bfloat16) for _ in range(2))
+            kv = _kv_states(H, Hkv, D, B, n, count)
+            for _ in range(KV_TRACE_STEPS):
+                for st in kv:
+                    st.step(q1, k1, v1)
+                    st.count = n
+            torch.cuda.synchronize()
+            order.append(dict(name=name, H=H, Hkv=Hkv, D=D, B=B, length=n, live=live, steps=KV_TRACE_STEPS * count))
+            del kv
+            torch.cuda.empty_cache()
+    with open(path, "w") as f:
+        json.dump(order, f)
+    print(f"{len(order)} cells -> {path}")
+
+
+def kv_trace_table(trace_dir, path):
+    """the kernel trace of a `--kv-trace` run as one row per cell: microseconds per step of each kernel of the step (mean over the
+    cell's steps, the first step of each cell left out) and bytes/s of the live cache prefix over the attend kernel's time and
+    over the whole step's, beside the 6.3 TB/s copy rate of the chip"""
+    import csv, glob, json
+    order = json.load(open(path))
+    kinds = ("kv_append_kernel", "kv_attend_kernel", "kv_combine_kernel", "kv_commit_kernel")
+    rows = []
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            kind = next((k for k in kinds if k in r["Kernel_Name"]), None)
+            if kind:
+                rows.append((int(r["Start_Timestamp"]), kind, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    rows.sort()
+    per = {k: [d for _, kind, d in rows if kind == k] for k in kinds}
+    total = sum(c["steps"] for c in order)
+    for k in kinds:
+        if len(per[k]) != total:
+            raise SystemExit(f"{k}: {len(per[k])} dispatches in the trace, the run made {total} steps")
+    print("| shape (H, Hkv, D) | B | length | live cache MB | append us | attend us | combine us | commit us | attend TB/s | "
+          "whole step TB/s | of 6.3 TB/s (attend) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    at = 0
+    for c in order:
+        sl = slice(at + 1, at + c["steps"])
+        at += c["steps"]
+        us = {k: statistics.mean(per[k][sl]) for k in kinds}
+        rate, whole = c["live"] / us["kv_attend_kernel"] / 1e6, c["live"] / sum(us.values()) / 1e6
+        print(f"| {c['name']} ({c['H']}, {c['Hkv']}, {c['D']}) | {c['B']} | {c['length']} | {c['live'] / 1e6:.1f} | "
+              + " | ".join(f"{us[k]:.1f}" for k in kinds) + f" | {rate:.2f} | {whole:.2f} | {rate / 6.3 * 100:.0f}% |")
+
+
 def _case_arg(flag):
     return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
 
+
+if "--kv-trace-table" in sys.argv:
+    i = sys.argv.index("--kv-trace-table")
+    kv_trace_table(sys.argv[i + 1], sys.argv[i + 2])
+    sys.exit(0)
+if "--kv-trace" in sys.argv:
+    kv_trace(sys.argv[sys.argv.index("--kv-trace") + 1])
+    sys.exit(0)
+if "--kv" in sys.argv:
+    bench_kv()
+    sys.exit(0)
 
 if "--linearmax" in sys.argv:
     bench_linearmax()

@@ -5,6 +5,7 @@
                                    [--llama-blocks 32] [--top-p 0.9] [--out profiles/r15_graphed_generate.md]
     python tools/bench_generate.py --cases Mixtral-8x7B-v0.1 [--mixtral-blocks 4] [--algs fastmax]
     python tools/bench_generate.py --nf4-head nf4 --cases tiny-llama-1.1b,Llama-2-7b-hf [--algs fastmax]
+    python tools/bench_generate.py --cases tiny-llama-1.1b,Llama-2-7b-hf,Gemma-2b --algs fastmax,fastmax-kv --blocks 4
 
 Shapes: tiny-llama-1.1b (22 blocks) and Llama-2-7b-hf (--llama-blocks of its 32) as BlockStack, pythia-70m as a 6-block NeoXStack;
 bf16, NF4 base, LoRA on q and v; batch 1 and 8; both decode state caches.  The blocks of a stack are copies of one randomly
@@ -23,7 +24,10 @@ timed in the same rounds; its tokens are checked against the eager loop's under 
 
 `--nf4-head nf4|nf4-dq` adds two arms, the eager and the graphed loop under a copy of the head after ``quantize_base()`` (with
 their own states and GraphedDecoder), timed in the same rounds as the dense head's two.  The quantised head scores other weights,
-so its tokens are checked against each other (graphed against eager), not against the dense head's."""
+so its tokens are checked against each other (graphed against eager), not against the dense head's.
+
+`--algs fastmax-kv` runs the fastmax blocks on ``FastmaxKVDecodeState`` caches of prompt + new tokens (the decode cache column says
+so); Gemma-2b (8 query heads on 1 KV head of 256) has no other cache.  `--blocks N` cuts every stack to N blocks."""
 import argparse
 import copy
 import os
@@ -36,7 +40,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 MIXTRAL = "Mixtral-8x7B-v0.1"
-VOCAB = {"tiny-llama-1.1b": 32000, "Llama-2-7b-hf": 32000, "pythia-70m": 50304, MIXTRAL: 32000}
+VOCAB = {"tiny-llama-1.1b": 32000, "Llama-2-7b-hf": 32000, "pythia-70m": 50304, MIXTRAL: 32000, "Gemma-2b": 256000}
 HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
           "whole call, eager | graphed |\n|---|---|---|---|---|---|---|---|---|")
 TOP_P_HEADER = ("| config | blocks | decode cache | batch | eager, per token: median (lowest .. highest) | graphed | eager / graphed | "
@@ -72,6 +76,7 @@ def make_mixtral_stack(n, alg):
 
 
 def make_stack(config, n, alg):
+    alg = "fastmax" if alg == "fastmax-kv" else alg          # the same blocks; the cache differs
     if config == MIXTRAL:
         return make_mixtral_stack(n, alg)
     from fastmax_experiments_amd.block import Block, BlockStack
@@ -87,11 +92,13 @@ def make_stack(config, n, alg):
     return (NeoXStack if neox else BlockStack)(blocks)
 
 
-def make_states(config, alg, B, n):
+def make_states(config, alg, B, n, max_len=None):
     from fastmax_experiments_amd.attention_block import CONFIG_SHAPES
-    from fastmax_experiments_amd.decode import FastmaxDecodeState, LinearmaxDecodeState
+    from fastmax_experiments_amd.decode import FastmaxDecodeState, FastmaxKVDecodeState, LinearmaxDecodeState
     s = CONFIG_SHAPES[config]
     H, G, hs = s["n_head"], s["n_query_groups"], s["head_size"]
+    if alg == "fastmax-kv":
+        return [FastmaxKVDecodeState(B, H, hs, "cuda", max_len, torch.bfloat16, n_query_groups=G) for _ in range(n)]
     if alg == "fastmax":
         return [FastmaxDecodeState(B, H, hs, "cuda", p=2, n_query_groups=G) for _ in range(n)]
     return [LinearmaxDecodeState(B, H, hs, "cuda", n_query_groups=G) for _ in range(n)]
@@ -126,7 +133,7 @@ def case(config, stack, alg, B, args):
     cos, sin = (t.to(torch.bfloat16) for t in build_rope_cache(total, stack.blocks[0].attn.rope_n_elem, device="cuda"))
     prompt = torch.randint(0, V, (B, T), generator=torch.Generator().manual_seed(2)).cuda()
     kw = dict(cos=cos, sin=sin, temperature=0.8, top_k=200)
-    eager_states, states = make_states(config, alg, B, n_blocks), make_states(config, alg, B, n_blocks)
+    eager_states, states = make_states(config, alg, B, n_blocks, total), make_states(config, alg, B, n_blocks, total)
     routed(True)
     decoder = GraphedDecoder(wte, stack, head, states, max_len=total, **kw)
 
@@ -146,7 +153,7 @@ def case(config, stack, alg, B, args):
     if moes:
         arms["eager routed"] = lambda n: eager(n, True)
     if args.top_p is not None:
-        p_states = make_states(config, alg, B, n_blocks)
+        p_states = make_states(config, alg, B, n_blocks, total)
         p_decoder = GraphedDecoder(wte, stack, head, p_states, max_len=total, top_p=args.top_p, **kw)
 
         def graphed_top_p(n):
@@ -157,7 +164,7 @@ def case(config, stack, alg, B, args):
         arms["graphed top_p"] = graphed_top_p
     if args.nf4_head is not None:
         q_head = copy.deepcopy(head).quantize_base(double_quant=args.nf4_head == "nf4-dq")
-        q_eager_states, q_states = make_states(config, alg, B, n_blocks), make_states(config, alg, B, n_blocks)
+        q_eager_states, q_states = make_states(config, alg, B, n_blocks, total), make_states(config, alg, B, n_blocks, total)
         q_decoder = GraphedDecoder(wte, stack, q_head, q_states, max_len=total, **kw)
 
         def eager_nf4_head(n):
@@ -219,6 +226,7 @@ def main():
     ap.add_argument("--cases", default="tiny-llama-1.1b,Llama-2-7b-hf,pythia-70m")
     ap.add_argument("--llama-blocks", type=int, default=32)
     ap.add_argument("--mixtral-blocks", type=int, default=4)
+    ap.add_argument("--blocks", type=int, default=None, help="at most this many blocks in every stack")
     ap.add_argument("--algs", default="fastmax,linearmax")
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--top-p", type=float, default=None, help="also time the graphed loop with this top_p behind the top-k")
@@ -234,7 +242,9 @@ def main():
         raise SystemExit("--new should be at least 2: the first token is not a decode step")
     if args.top_p is not None and MIXTRAL in args.cases.split(","):
         raise SystemExit("--top-p and the Mixtral case are timed in separate runs: each adds its own arm and columns")
-    n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6, MIXTRAL: args.mixtral_blocks}
+    n_blocks = {"tiny-llama-1.1b": 22, "Llama-2-7b-hf": args.llama_blocks, "pythia-70m": 6, MIXTRAL: args.mixtral_blocks, "Gemma-2b": 18}
+    if args.blocks is not None:
+        n_blocks = {k: min(v, args.blocks) for k, v in n_blocks.items()}
     lines = [f"{args.new} tokens after a {args.prompt}-token prompt, bf16, NF4 base; {args.reps} rounds, the arms alternating.\n",
              NF4_HEAD_HEADER if args.nf4_head is not None else HEADER if args.top_p is None else TOP_P_HEADER]
     print("\n".join(lines), flush=True)
