@@ -1,6 +1,4 @@
 """ctypes binding of the C ABI declared in the public headers under include/ (HEADERS): one table, ABI, set on one handle.
-The adapter-v2 side header (ADAPTER_HEADER) has the table ADAPTER_ABI, the KV-cache decode header (KV_DECODE_HEADER) the table
-KV_DECODE_ABI, both set on the same handle.
 
 Fails loudly: if libfastmax_hip.so is absent or a symbol is missing, importing the operator
 raises -- there is no eager/PyTorch/CPU fallback for the hot path.
@@ -47,12 +45,15 @@ ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act (includ
 # end of ABI.
 HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h", "fastmax_hip_optim.h",
            "fastmax_hip_next_token.h", "fastmax_hip_neox.h", "fastmax_hip_cursor.h", "fastmax_hip_nucleus.h", "fastmax_hip_moe.h",
-           "fastmax_hip_moe_decode.h", "fastmax_hip_head.h")
+           "fastmax_hip_moe_decode.h", "fastmax_hip_head.h", "fastmax_hip_adapter.h", "fastmax_hip_kv_decode.h")
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
 CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
 NUCLEUS_MAX_V = 1 << 22                         # the largest V the fixed-point mass of top-p sampling admits
 MOE_MAX_EXPERTS, MOE_MAX_PER_TOKEN = 64, 8      # FASTMAX_MOE_MAX_EXPERTS, FASTMAX_MOE_MAX_PER_TOKEN
 MOE_DECODE_MAX_ROWS = 16                        # FASTMAX_MOE_DECODE_MAX_ROWS
+ADAPTER_ROWS_PER_BLOCK = 64                     # FASTMAX_ADAPTER_ROWS_PER_BLOCK
+KV_CHUNK, KV_SLICE, KV_MAX_D = 128, 8, 256      # FASTMAX_KV_CHUNK, FASTMAX_KV_SLICE, FASTMAX_KV_MAX_D
+KV_LEN, KV_OVERFLOW, KV_HEADER_WORDS = 0, 1, 16  # enum fastmax_kv_word
 # every function the HEADERS declare, in their order and in each header's own order: name -> (restype, argtypes).
 # tests/test_binding_cpu.py checks each row against the prototype.
 ABI = {
@@ -173,30 +174,18 @@ ABI = {
     # fastmax_hip_head.h: the last-row logits with an lm_head bias, and on packed NF4 codes
     "fastmax_hip_last_logits_bias": (ci, [vp, i64, vp, i64, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_last_logits_nf4": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, ci, vp]),
-}
-SYMBOLS = list(ABI)
-# adapter-v2 fine-tuning's side header (the per-column scale and bias behind a linear, forward and backward): same library, same
-# FASTMAX_ABI_VERSION (additions only), a table of its own until it is folded into ABI.  tests/test_adapter_v2_cpu.py checks
-# each row against the prototype.
-ADAPTER_HEADER = "fastmax_hip_adapter.h"
-ADAPTER_ROWS_PER_BLOCK = 64                     # FASTMAX_ADAPTER_ROWS_PER_BLOCK
-ADAPTER_ABI = {
+    # fastmax_hip_adapter.h: adapter-v2 fine-tuning's per-column scale and bias behind a linear, forward and backward
     "fastmax_hip_adapter_forward": (ci, [vp, i64, vp, vp, vp, i64, ci, ci, ci, ci, vp]),
     "fastmax_hip_adapter_backward_workspace": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_adapter_backward": (ci, [vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, ci, ci, ci, ci, vp, sz, vp]),
-}
-# the KV-cache decode route's side header (csrc/fastmax_kv_decode.hip): same library, same FASTMAX_ABI_VERSION (additions only), a
-# table of its own.  tests/test_kv_decode_cpu.py checks each row against the prototype.
-KV_DECODE_HEADER = "fastmax_hip_kv_decode.h"
-KV_CHUNK, KV_SLICE, KV_MAX_D = 128, 8, 256      # FASTMAX_KV_CHUNK, FASTMAX_KV_SLICE, FASTMAX_KV_MAX_D
-KV_LEN, KV_OVERFLOW, KV_HEADER_WORDS = 0, 1, 16  # enum fastmax_kv_word
-KV_DECODE_ABI = {
+    # fastmax_hip_kv_decode.h: the KV-cache decode route of fastmax blocks (csrc/fastmax_kv_decode.hip)
     "fastmax_hip_kv_decode_state_bytes": (sz, [ci, ci, ci, ci, ci]),
     "fastmax_hip_kv_decode_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
     "fastmax_hip_kv_decode_load": (ci, [vp, i64p, vp, i64p, vp, ci, ci, ci, ci, ci, ci, vp]),
     "fastmax_hip_kv_decode_append_attend": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
     "fastmax_hip_kv_decode_set_len": (ci, [vp, ci, ci, vp]),
 }
+SYMBOLS = list(ABI)
 
 _lib = None
 
@@ -210,12 +199,11 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for table in (ABI, ADAPTER_ABI, KV_DECODE_ABI):
-        for name, (restype, argtypes) in table.items():
-            if not hasattr(L, name):
-                raise RuntimeError(f"libfastmax_hip.so does not export {name}")
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
+    for name, (restype, argtypes) in ABI.items():
+        if not hasattr(L, name):
+            raise RuntimeError(f"libfastmax_hip.so does not export {name}")
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.fastmax_hip_abi_version() != ABI_VERSION:
         raise RuntimeError("libfastmax_hip.so ABI version mismatch")
     _lib = L

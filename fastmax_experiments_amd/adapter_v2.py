@@ -8,7 +8,7 @@ Adapter v2 does not depend on the attention operator, which is why it is the ada
 adapter v1 lives inside scaled_dot_product_attention, which a ``fastmax`` / ``linearmax`` block never calls.  The base
 ``linear`` may be dense or an ``NF4Linear`` (``finetune/adapter_v2.py --quantize bnb.nf4``).
 
-What runs in csrc/adapter_v2.hip (C ABI and rounding points: include/fastmax_hip_adapter.h, bound by ``_lib.ADAPTER_ABI``):
+What runs in csrc/adapter_v2.hip (C ABI and rounding points: include/fastmax_hip_adapter.h, bound by ``_lib.ABI``):
     adapter_forward     z -> y, one read and one write
     adapter_backward    (dy, z) -> dz and both parameter gradients in one pass, the sums in a fixed order
 There is no CPU path through the kernels; ``AdapterV2Linear.fused = False`` selects the reference's expression in tensor ops

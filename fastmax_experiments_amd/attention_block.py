@@ -30,7 +30,7 @@ import torch.nn as nn
 from . import ops
 from .attention_mechanisms.fastmax import MAX_HEADS_PER_LAUNCH, fastmax
 from .attention_mechanisms.fastmax_hack import LinearmaxPlan, fastmax_hack_grouped, linearmax, linearmax_plan
-from .decode import FastmaxDecodeState, FastmaxKVDecodeState, LinearmaxDecodeState
+from .decode import check_block_cache
 from .lora import LoRALinear, LoRAQKVLinear
 from .ops import apply_rope, build_rope_cache  # noqa: F401  (re-exported: the public RoPE formula lives beside its kernels)
 
@@ -149,16 +149,7 @@ class CausalSelfAttention(nn.Module):
         projection's output, anything else an ``extend`` (a prefill on an empty state).  A ``fastmax`` block also takes a
         ``FastmaxKVDecodeState`` (p=2; ``FastmaxKVDecodeState.for_attention``): the same function over a cache of K and V rows,
         for head sizes up to 256."""
-        if self.attn_alg == "linearmax":
-            if isinstance(state, FastmaxDecodeState):
-                raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
-                                          "statistics run over the whole sequence, which the fastmax state caches do not carry")
-            if not isinstance(state, LinearmaxDecodeState):
-                raise TypeError(f"a linearmax block generates on a LinearmaxDecodeState, got {type(state).__name__}")
-        elif isinstance(state, LinearmaxDecodeState):
-            raise TypeError("a fastmax block generates on a FastmaxDecodeState(p=2), not on a LinearmaxDecodeState")
-        elif isinstance(state, FastmaxKVDecodeState) and state.p != 2:
-            raise ValueError(f"a fastmax block computes p=2 fastmax; the FastmaxKVDecodeState was built with p={state.p}")
+        check_block_cache(self.attn_alg, state)
         B, T, _ = x.size()
         if cos.shape[0] != T or sin.shape[0] != T:
             raise ValueError(f"cos / sin should hold the rope rows of the {T} new positions, got {tuple(cos.shape)}, {tuple(sin.shape)}")

@@ -16,7 +16,7 @@ SOURCES = ["fastmax_api.hip", "fastmax_generic.hip", "fastmax_normalize.hip", "f
     "fastmax_quad32_mfma.hip", "fastmax_quad_mfma_bwd.hip", "fastmax_quad32_bwd.hip", "fastmax_mfma_bwd_lin.hip", "fastmax_decode.hip", "fastmax_decode_p2.hip", "fastmax_decode_qkv.hip", "linearmax_decode.hip", "fastmax_kv_decode.hip", "block_neighbours.hip", "neox_block.hip", "adapter_v2.hip", "flat_adamw.hip", "next_token.hip", "last_logits.hip", "decode_cursor.hip", "moe.hip", "moe_decode.hip", "nf4_lora.hip", "nf4_gemm.hip", "lora_thin.hip"]
 # csrc's own headers, then the public ones (relative to csrc, like the sources)
 HEADERS = (["fastmax_common.h", "fastmax_mfma_common.h", "fastmax_mfma32_common.h", "fastmax_decode_p2_step.h", "row_kernels.h", "fastmax_scan128.h", "next_token_sample.h", "nf4_gemv.h"] +
-           [os.path.join("..", "..", "include", h) for h in _lib.HEADERS + (_lib.ADAPTER_HEADER, _lib.KV_DECODE_HEADER)])
+           [os.path.join("..", "..", "include", h) for h in _lib.HEADERS])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fno-gpu-rdc"]
 # per-source flags.  The p=2 tile kernels interleave their per-score vector work with MFMAs: packed-f32 instructions
 # (v_pk_fma_f32 / v_pk_add_f32, which the SLP vectoriser forms from adjacent scalar operations) cost 3-4x their issue slot

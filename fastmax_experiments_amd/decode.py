@@ -52,31 +52,92 @@ from .attention_mechanisms.fastmax_hack import fastmax_hack
 FUSED_STEP_DEFAULT = False
 
 
+def _kv_heads(H, n_query_groups):
+    """the number of KV heads under ``n_query_groups`` (None: one per query head)"""
+    Hkv = H if n_query_groups is None else n_query_groups
+    if Hkv <= 0 or H % Hkv != 0:
+        raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+    return Hkv
+
+
 class _DecodeState:
     """What the state caches share: the record `state` (float32, zeroed) of `count` tokens for B sequences of H query heads on
     Hkv KV heads of size D, and the entry points that take the attention block's QKV projection output.  A subclass gives
-    `prefill`, `step` and `extend` on split, rotated q (B,H,T,D) and k, v (B,Hkv,T,D)."""
+    `prefill`, `step` and `extend` on split, rotated q (B,H,T,D) and k, v (B,Hkv,T,D).
+
+    What the attention block and the generation loop ask of a cache is answered here and nowhere else: `check_block_cache`
+    (below the classes) for which block generates on which cache, `max_len` and `check_capacity` for how many tokens it holds,
+    `check_recordable` for a loop recorded as a graph.  Those three read `max_len`, `p` and `B` of a cache only."""
+
+    max_len = None          # the most tokens the cache holds; None: a carried state, which never fills up
+    _count = 0
 
     def __init__(self, B, H, Hkv, D, nbytes, device, unsupported):
         if nbytes == 0:
             raise NotImplementedError(unsupported)
         self.B, self.H, self.Hkv, self.D = B, H, Hkv, D
         self.state = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-        self.count = 0
+
+    @property
+    def count(self):
+        """the tokens fed so far, on the host; where the kernels keep a count of their own this is its mirror, never read back"""
+        return self._count
+
+    @count.setter
+    def count(self, n):
+        self._count = n
 
     def reset(self):
         """Empty sequence again; the allocation is kept (a generation loop resets between prompts)."""
         self.state.zero_()
-        self.count = 0
+        self._count = 0
 
     def _restore(self, state, count):
         """back to a saved (``state.clone()``, ``count``) pair: what a graph recording does after its warm-up steps"""
         self.state.copy_(state)
-        self.count = count
+        self._count = count
 
     def _replayed(self, steps):
         """``steps`` single-token steps ran from a recorded graph, which moves no host counter: the mirror follows"""
-        self.count += steps
+        self._count += steps
+
+    def check_capacity(self, fed, what):
+        """refuse, before anything runs, a call of ``what`` that feeds more tokens than the cache holds"""
+        if self.max_len is not None and fed > self.max_len:
+            raise ValueError(f"{what}: {fed} tokens are fed, a {type(self).__name__} of this call holds at most {self.max_len}")
+
+    def check_recordable(self, steps):
+        """refuse a cache that a graph of one decode step cannot be recorded on; the recording itself runs ``steps`` single-token
+        steps on the non-empty cache"""
+        if self.max_len is not None and self.max_len <= steps:
+            raise ValueError(f"GraphedDecoder: the recording runs {steps} steps on a non-empty cache; a "
+                             f"{type(self).__name__} needs max_len > {steps}, got {self.max_len}")
+
+    def _fastmax_of(self, D, p, normalize_term, tensors_normalized):
+        """a fastmax cache's function: order ``p`` and the scaling, as `fastmax` takes them"""
+        if p not in (1, 2):
+            raise ValueError(f"p should be 1 or 2, got p={p}")
+        self.p = p
+        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
+        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
+
+    def _masked_fastmax(self, q, k, v):
+        """that function over a whole prompt, masked (the tile kernels) -> o (B,H,T,D)"""
+        return self._masked_forward(lambda *qkv: fastmax(*qkv, mask=True, p=self.p, **self._kw), q, k, v)
+
+    @staticmethod
+    def _tokens(q, what):
+        """T of q (B,H,T,D), one token at least"""
+        T = q.shape[2] if q.dim() == 4 else 0
+        if T < 1:
+            raise ValueError(f"{what} takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        return T
+
+    def _unit_rows(self, q, k, v):
+        """q, k, v on the state's device in q's dtype, as the kernels that take any strides with unit stride in D read them (views
+        of the split's output as they are)"""
+        dev = self.state.device
+        return tuple(t if t.stride(3) == 1 else t.contiguous() for t in (x.to(device=dev, dtype=q.dtype) for x in (q, k, v)))
 
     # qkv (B,T,G,q_per_kv+2,hs) -> rotated q (B,H,T,hs), rotated k and v (B,G,T,hs): one HIP pass where the split kernel takes
     # the shape, else tensor slicing + apply_rope (model.py:397-425)
@@ -136,16 +197,10 @@ class _DecodeState:
 
 class FastmaxDecodeState(_DecodeState):
     def __init__(self, B, H, D, device, normalize_term=8, tensors_normalized=False, p=1, n_query_groups=None):
-        if p not in (1, 2):
-            raise ValueError(f"p should be 1 or 2, got p={p}")
-        Hkv = H if n_query_groups is None else n_query_groups
-        if p == 1 and Hkv != H:
+        self._fastmax_of(D, p, normalize_term, tensors_normalized)
+        if p == 1 and n_query_groups not in (None, H):
             raise ValueError("the first-order decode state has one record per head: n_query_groups must be None or H")
-        if p == 2 and (Hkv <= 0 or H % Hkv != 0):
-            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
-        self.p = p
-        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
-        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
+        Hkv = _kv_heads(H, n_query_groups)
         L = _lib.lib()
         # the second-order state is kept per KV head
         nbytes = L.fastmax_hip_decode_state_bytes(B, H, D) if p == 1 else L.fastmax_hip_p2_decode_state_bytes(B, Hkv, D)
@@ -171,12 +226,12 @@ class FastmaxDecodeState(_DecodeState):
             for s in range(0, q.shape[2], chunk):
                 o[:, :, s:s + chunk] = self.extend(q[:, :, s:s + chunk], k[:, :, s:s + chunk], v[:, :, s:s + chunk])
             return o
-        o = self._masked_forward(lambda *qkv: fastmax(*qkv, mask=True, p=self.p, **self._kw), q, k, v)
+        o = self._masked_fastmax(q, k, v)
         # the state of the whole prompt from its prepared k, v
         kd, vd = ops._prep(k, k.device), ops._prep(v.to(k.dtype), k.device)
         prob = ops._problem(kd, kd, kd.dtype, kd.dtype, self.p, True, self.nt, 0.0)
         ops._call(f"fastmax_hip_p{self.p}_prefill_state", kd.device, (ctypes.byref(prob), *ops._qkv(kd, vd), self.state.data_ptr()))
-        self.count = kd.shape[2]
+        self._count = kd.shape[2]
         return o
 
     def step(self, q, k, v):
@@ -194,7 +249,7 @@ class FastmaxDecodeState(_DecodeState):
             ops._call("fastmax_hip_p2_decode_step", q.device, args + (B, H, Hkv, D, dt, dt, 1.0 / self.nt))
         else:
             ops._call("fastmax_hip_p1_decode_step", q.device, args + (B, H, D, dt, dt, 1.0 / self.nt, self.count + 1))
-        self.count += 1
+        self._count += 1
         return o
 
     def extend(self, q, k, v):
@@ -204,9 +259,7 @@ class FastmaxDecodeState(_DecodeState):
         if self.p != 2:
             raise NotImplementedError("extend needs the second-order state cache (p=2); for linearmax blocks, whose statistics "
                                       "run over the whole sequence, use LinearmaxDecodeState")
-        T = q.shape[2] if q.dim() == 4 else 0
-        if T < 1:
-            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        T = self._tokens(q, "extend")
         self._check_shapes(q, k, v, T)
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         qd, kd, vd = (ops._prep(t.to(q.dtype), q.device) for t in (q, k, v))
@@ -214,8 +267,15 @@ class FastmaxDecodeState(_DecodeState):
         prob = ops._problem(qd, kd, qd.dtype, qd.dtype, 2, True, self.nt, 0.0)
         ops._call("fastmax_hip_p2_extend", q.device, (ctypes.byref(prob), Hkv, *ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr()),
                   ws=_lib.lib().fastmax_hip_p2_extend_workspace(B, H, Hkv, T, D))
-        self.count += T
+        self._count += T
         return o
+
+    def check_recordable(self, steps):
+        if self.p != 2:
+            raise NotImplementedError("GraphedDecoder: a first-order FastmaxDecodeState passes its token count to the step kernel "
+                                      "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
+                                      "LinearmaxDecodeState")
+        super().check_recordable(steps)
 
     def _check_qkv(self, qkv, cos, sin, rope_n_elem, what):
         if self.p != 2:
@@ -239,7 +299,7 @@ class FastmaxDecodeState(_DecodeState):
         ops._call("fastmax_hip_p2_decode_step_qkv", qkv.device,
                   (qkv.data_ptr(), cos32.data_ptr(), sin32.data_ptr(), self.state.data_ptr(), o.data_ptr(), B, G, H // G, D, n,
                    tables16, dt, dt, 1.0 / self.nt))
-        self.count += 1
+        self._count += 1
         return o
 
     def _prefill_qkv(self, q, k, v):
@@ -260,21 +320,14 @@ class FastmaxKVDecodeState(_DecodeState):
     host's mirror of it and nothing is ever read back.  A row's output bits depend on its q row and the cache prefix alone: not on
     B, the batch row, T (a token fed alone or inside an ``extend``), ``max_len``, the inputs' strides or eager / replayed."""
 
-    _count = 0
-
     def __init__(self, B, H, D, device, max_len, dtype, p=2, n_query_groups=None, normalize_term=8, tensors_normalized=False):
-        if p not in (1, 2):
-            raise ValueError(f"p should be 1 or 2, got p={p}")
-        Hkv = H if n_query_groups is None else n_query_groups
-        if Hkv <= 0 or H % Hkv != 0:
-            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+        self._fastmax_of(D, p, normalize_term, tensors_normalized)
+        Hkv = _kv_heads(H, n_query_groups)
         if dtype not in ops._DT:
             raise ValueError(f"the KV decode cache holds float32, bfloat16 or float16, got {dtype}")
         if int(max_len) != max_len or max_len < 1 or max_len >= 2 ** 31:
             raise ValueError(f"max_len should be a number of tokens in 1 .. 2^31 - 1, got {max_len}")
-        self.p, self.dtype, self.max_len = p, dtype, int(max_len)
-        self.nt = ops.effective_normalize_term(D, normalize_term, tensors_normalized)
-        self._kw = dict(normalize_term=normalize_term, tensors_normalized=tensors_normalized)
+        self.dtype, self.max_len = dtype, int(max_len)
         nbytes = _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[dtype])
         if nbytes and torch.device(device).type != "cuda":
             raise RuntimeError("the KV decode cache lives on an MI355X (HIP device); there is no CPU path through the kernels")
@@ -293,11 +346,7 @@ class FastmaxKVDecodeState(_DecodeState):
         """the header's int32 words, a view of ``state`` (reading them synchronises)"""
         return self.state[:_lib.KV_HEADER_WORDS].view(torch.int32)
 
-    @property
-    def count(self):
-        return self._count
-
-    @count.setter
+    @_DecodeState.count.setter
     def count(self, n):
         """a smaller value truncates the cache (one small device write; the rows stay and are overwritten); a larger one raises"""
         n = int(n)
@@ -312,32 +361,21 @@ class FastmaxKVDecodeState(_DecodeState):
         self.state[:_lib.KV_HEADER_WORDS].zero_()
         self._count = 0
 
-    def _restore(self, state, count):
-        self.state.copy_(state)          # the header's length with it
-        self._count = count
-
-    def _replayed(self, steps):
-        self._count += steps
-
     def _inputs(self, q, k, v, T):
         self._check_shapes(q, k, v, T)
         if not (q.dtype == k.dtype == v.dtype == self.dtype):
             raise TypeError(f"the cache holds {self.dtype}, got q {q.dtype}, k {k.dtype}, v {v.dtype}")
         if self._count + T > self.max_len:
             raise ValueError(f"the cache holds {self._count} of at most {self.max_len} tokens, {T} more do not fit")
-        dev = self.state.device
-        # the kernels take any strides with unit stride in D (views of the split's output as they are)
-        return tuple(t if t.stride(3) == 1 else t.contiguous() for t in (x.to(dev) for x in (q, k, v)))
+        return self._unit_rows(q, k, v)
 
     def prefill(self, q, k, v):
         """Masked forward over the prompt (the tile kernels), o (B,H,T,D); the cache then holds the prompt's K and V rows."""
         assert self._count == 0, "prefill starts a sequence"
-        T = q.shape[2] if q.dim() == 4 else 0
-        if T < 1:
-            raise ValueError(f"prefill takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        T = self._tokens(q, "prefill")
         qd, kd, vd = self._inputs(q, k, v, T)
         with torch.no_grad():
-            o = self._masked_forward(lambda *qkv: fastmax(*qkv, mask=True, p=self.p, **self._kw), qd, kd, vd)
+            o = self._masked_fastmax(qd, kd, vd)
         ops._call("fastmax_hip_kv_decode_load", self.state.device,
                   (*ops._qkv(kd, vd), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
         self._count = T
@@ -351,10 +389,7 @@ class FastmaxKVDecodeState(_DecodeState):
     def extend(self, q, k, v):
         """T >= 1 new tokens after the ``count`` cached ones (any count, 0 included) -> o (B,H,T,D) = masked attention at the T
         new positions; bit for bit what T single steps give."""
-        T = q.shape[2] if q.dim() == 4 else 0
-        if T < 1:
-            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
-        return self._append_attend(q, k, v, T)
+        return self._append_attend(q, k, v, self._tokens(q, "extend"))
 
     def _append_attend(self, q, k, v, T):
         qd, kd, vd = self._inputs(q, k, v, T)
@@ -381,9 +416,7 @@ class LinearmaxDecodeState(_DecodeState):
     The token count the kernels use lives in the state itself; `count` is the host's copy and nothing is ever read back."""
 
     def __init__(self, B, H, D, device, n_query_groups=None):
-        Hkv = H if n_query_groups is None else n_query_groups
-        if Hkv <= 0 or H % Hkv != 0:
-            raise ValueError(f"n_query_groups={n_query_groups} does not divide the {H} query heads")
+        Hkv = _kv_heads(H, n_query_groups)
         nbytes = _lib.lib().fastmax_hip_linearmax_decode_state_bytes(B, H, Hkv, D)
         super().__init__(B, H, Hkv, D, nbytes, device,
                          f"linearmax decode state: head size {D} with {H // Hkv} query heads per KV head not supported")
@@ -391,7 +424,7 @@ class LinearmaxDecodeState(_DecodeState):
     def prefill(self, q, k, v):
         """L over the prompt (the matrix-core masked forward), o (B,H,N,D); the state then holds the prompt."""
         assert self.count == 0, "prefill starts a sequence"
-        T = q.shape[2] if q.dim() == 4 else 0
+        T = self._tokens(q, "prefill")
         self._check_shapes(q, k, v, T)
         with torch.no_grad():
             o = self._masked_forward(lambda *qkv: fastmax_hack(*qkv, p=1, mask=True), q, k, v)
@@ -407,9 +440,7 @@ class LinearmaxDecodeState(_DecodeState):
     def extend(self, q, k, v):
         """T >= 1 new tokens after the `count` cached ones (any count, 0 included) -> o (B,H,T,D) in q's dtype = rows
         count .. count+T-1 of L over all count + T tokens.  T = 1 is `step`, bit for bit."""
-        T = q.shape[2] if q.dim() == 4 else 0
-        if T < 1:
-            raise ValueError(f"extend takes q (B,H,T,D) with T >= 1, got {tuple(q.shape)}")
+        T = self._tokens(q, "extend")
         self._check_shapes(q, k, v, T)
         return self._advance(q, k, v, T)
 
@@ -423,10 +454,23 @@ class LinearmaxDecodeState(_DecodeState):
         dev = self.state.device
         if dev.type != "cuda":
             ops._device()          # raises: there is no CPU path
-        # the kernel takes any strides with unit stride in D (views of the split's output as they are)
-        qd, kd, vd = (t if t.stride(3) == 1 else t.contiguous() for t in (x.to(device=dev, dtype=q.dtype) for x in (q, k, v)))
+        qd, kd, vd = self._unit_rows(q, k, v)          # k and v are cast to q's dtype
         o = torch.empty((self.B, self.H, T, self.D), dtype=q.dtype, device=dev) if readout else None
         ops._call("fastmax_hip_linearmax_decode_advance", dev,
                   (*ops._qkv(qd, kd, vd), self.state.data_ptr(), ops._ptr(o), self.B, self.H, self.Hkv, T, self.D, ops._DT[q.dtype]))
-        self.count += T
+        self._count += T
         return o
+
+
+def check_block_cache(attn_alg, state):
+    """Which cache a ``CausalSelfAttention`` of ``attn_alg`` generates on: raises unless ``state`` is one."""
+    if attn_alg == "linearmax":
+        if isinstance(state, FastmaxDecodeState):
+            raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
+                                      "statistics run over the whole sequence, which the fastmax state caches do not carry")
+        if not isinstance(state, LinearmaxDecodeState):
+            raise TypeError(f"a linearmax block generates on a LinearmaxDecodeState, got {type(state).__name__}")
+    elif isinstance(state, LinearmaxDecodeState):
+        raise TypeError("a fastmax block generates on a FastmaxDecodeState(p=2), not on a LinearmaxDecodeState")
+    elif isinstance(state, FastmaxKVDecodeState) and state.p != 2:
+        raise ValueError(f"a fastmax block computes p=2 fastmax; the FastmaxKVDecodeState was built with p={state.p}")

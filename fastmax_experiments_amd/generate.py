@@ -363,14 +363,6 @@ def _layers_and_run(blocks, states):
     return layers, run
 
 
-def _check_kv_capacity(states, fed, what):
-    """a KV decode cache cannot hold more than its ``max_len`` tokens: refuse before anything runs"""
-    from .decode import FastmaxKVDecodeState
-    for s in states:
-        if isinstance(s, FastmaxKVDecodeState) and fed > s.max_len:
-            raise ValueError(f"{what}: {fed} tokens are fed, a FastmaxKVDecodeState of this call holds at most {s.max_len}")
-
-
 _RECORDING_STEPS = 3          # GraphedDecoder._capture: two eager steps, then the recorded one
 
 
@@ -465,20 +457,14 @@ class GraphedDecoder:
 
     def __init__(self, wte: torch.Tensor, blocks, head: NextTokenHead, states, *, cos, sin, max_len: int, temperature: float = 1.0,
                  top_k=None, eos_id=None, top_p=None) -> None:
-        from .decode import FastmaxDecodeState, FastmaxKVDecodeState
         _check_sampling(temperature, top_k, top_p)
         self._layers, self._run = _layers_and_run(blocks, states)
         if not len(states):
             raise ValueError("GraphedDecoder: no blocks")
-        _check_kv_capacity(states, max_len - 1, "GraphedDecoder")
         for s in states:
-            if isinstance(s, FastmaxKVDecodeState) and s.max_len <= _RECORDING_STEPS:
-                raise ValueError(f"GraphedDecoder: the recording runs {_RECORDING_STEPS} steps on a non-empty cache; a "
-                                 f"FastmaxKVDecodeState needs max_len > {_RECORDING_STEPS}, got {s.max_len}")
-            if isinstance(s, FastmaxDecodeState) and s.p != 2:
-                raise NotImplementedError("GraphedDecoder: a first-order FastmaxDecodeState passes its token count to the step kernel "
-                                          "by value, which a recorded graph would freeze; use FastmaxDecodeState(p=2) or "
-                                          "LinearmaxDecodeState")
+            s.check_capacity(max_len - 1, "GraphedDecoder")
+        for s in states:
+            s.check_recordable(_RECORDING_STEPS)
         from .moe import LLaMAMoE
         moes = [b.mlp for b in self._layers if isinstance(getattr(b, "mlp", None), LLaMAMoE)]
         if moes and not all(m.device_routed and m.fused_neighbours for m in moes):
@@ -532,9 +518,8 @@ class GraphedDecoder:
         dev = self.tok.device
         saved = [(s.state.clone(), s.count) for s in self.states]
         for s in self.states:
-            room = getattr(s, "max_len", None)
-            if room is not None and s.count + _RECORDING_STEPS > room:
-                s.count = room - _RECORDING_STEPS
+            if s.max_len is not None and s.count + _RECORDING_STEPS > s.max_len:
+                s.count = s.max_len - _RECORDING_STEPS
         self.tok.zero_()
         self.cursor.arm(0, 0, 0)
         self._stream = torch.cuda.Stream(device=dev)
@@ -563,7 +548,8 @@ class GraphedDecoder:
         if not self.head.fused:
             raise ValueError("GraphedDecoder: head.fused = False samples through torch's generator; the graphed route needs the HIP sampler")
         _need_device(prompt, "GraphedDecoder.generate")
-        _check_kv_capacity(self.states, max_returned_tokens - 1, "GraphedDecoder.generate")
+        for s in self.states:
+            s.check_capacity(max_returned_tokens - 1, "GraphedDecoder.generate")
         sampler = Sampler() if sampler is None else sampler
         eos = self.eos_id
         pos = torch.arange(T, device=prompt.device)
@@ -635,7 +621,8 @@ def generate(wte: torch.Tensor, blocks, head: NextTokenHead, states, prompt: tor
     B, T = _check_prompt(prompt, max_returned_tokens, cos, sin)
     _check_sampling(temperature, top_k, top_p)
     layers, run = _layers_and_run(blocks, states)
-    _check_kv_capacity(states, max_returned_tokens - 1, "generate")
+    for s in states:
+        s.check_capacity(max_returned_tokens - 1, "generate")
     sampler = Sampler() if sampler is None else sampler
     dev = prompt.device
     pos = torch.arange(max_returned_tokens, device=dev)

@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .ops import KV_LAYOUTS, _DT, _stream, group_views, rope_qkv_backward
+from .ops import KV_LAYOUTS, _DT, _call, _ptr, _stream, group_views, rope_qkv_backward
 
 NF4_CODE = torch.tensor([-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453,
                          -0.28444138169288635, -0.18477343022823334, -0.09105003625154495, 0.0,
@@ -58,11 +58,8 @@ def nf4_dequantize(packed: torch.Tensor, absmax, shape, dtype=torch.float32) -> 
     if packed.device.type == "cuda" and dtype in (torch.float32, torch.bfloat16):
         out = torch.empty(n, dtype=dtype, device=packed.device)
         sc = NF4Scales(qs)
-        with torch.cuda.device(packed.device):
-            rc = _lib.lib().fastmax_hip_nf4_dequantize_s(packed.data_ptr(), sc.ref, out.data_ptr(), n,
-                                                         _lib.F32 if dtype == torch.float32 else _lib.BF16,
-                                                         _stream(packed.device))
-        _lib.check(rc, "fastmax_hip_nf4_dequantize_s")
+        _call("fastmax_hip_nf4_dequantize_s", packed.device,
+              (packed.data_ptr(), sc.ref, out.data_ptr(), n, _lib.F32 if dtype == torch.float32 else _lib.BF16))
         return out.view(shape)
     code = NF4_CODE.to(packed.device)
     idx = torch.stack([packed >> 4, packed & 15], dim=1).reshape(-1).long()
@@ -395,12 +392,10 @@ def _decode_scratch(base: "NF4Linear", transposed: bool) -> torch.Tensor:
     if buf is None or buf.numel() < N * K:
         buf = torch.empty(N * K, dtype=torch.bfloat16, device=wq.device)
         _scratch[key] = buf
-    with torch.cuda.device(wq.device):
-        if transposed:
-            rc = _lib.lib().fastmax_hip_nf4_dequantize_transposed(wq.data_ptr(), scales.ref, buf.data_ptr(), N, K, _stream(wq.device))
-        else:
-            rc = _lib.lib().fastmax_hip_nf4_dequantize_s(wq.data_ptr(), scales.ref, buf.data_ptr(), N * K, _lib.BF16, _stream(wq.device))
-    _lib.check(rc, "fastmax_hip_nf4_dequantize")
+    if transposed:
+        _call("fastmax_hip_nf4_dequantize_transposed", wq.device, (wq.data_ptr(), scales.ref, buf.data_ptr(), N, K))
+    else:
+        _call("fastmax_hip_nf4_dequantize_s", wq.device, (wq.data_ptr(), scales.ref, buf.data_ptr(), N * K, _lib.BF16))
     return buf[: N * K].view((K, N) if transposed else (N, K))
 
 
@@ -437,6 +432,12 @@ def _weight_operand(base: nn.Module, transposed: bool, allow_resident: bool = Tr
 # ---------------------------------------------------------------------------------------------
 # the kernels' callers
 # ---------------------------------------------------------------------------------------------
+def _dropout_variant(name, dev, drop, args):
+    """(name, dev, args) of a rank-r kernel's call: with drop = (seed tensor on the device, p) its ``_dropout`` entry point,
+    which takes the seed and p behind the plain one's arguments"""
+    return (name, dev, args) if drop is None else (name + "_dropout", dev, args + (drop[0].data_ptr(), float(drop[1])))
+
+
 def lora_down(x: torch.Tensor, bt: torch.Tensor, want_t: bool = True, drop=None):
     """e (M, RP) = x (M, K) bt (RP, K)^T, and e^T (RP, roundup(M, 16)) zero padded; bf16.
     drop = (seed tensor on the device, p): x passes through the dropout mask of that seed first (scaled by 1 / (1 - p))."""
@@ -445,12 +446,8 @@ def lora_down(x: torch.Tensor, bt: torch.Tensor, want_t: bool = True, drop=None)
     e = torch.empty((M, RP), dtype=torch.bfloat16, device=x.device)
     MP = (M + 15) // 16 * 16
     et = torch.empty((RP, MP), dtype=torch.bfloat16, device=x.device) if want_t else None
-    L = _lib.lib()
-    call, extra = (L.fastmax_hip_lora_down, ()) if drop is None else (L.fastmax_hip_lora_down_dropout, (drop[0].data_ptr(), float(drop[1])))
-    with torch.cuda.device(x.device):
-        rc = call(x.data_ptr(), x.stride(0), bt.data_ptr(), bt.stride(0), e.data_ptr(), RP,
-                  None if et is None else et.data_ptr(), MP, M, K, RP, *extra, _stream(x.device))
-    _lib.check(rc, "fastmax_hip_lora_down")
+    _call(*_dropout_variant("fastmax_hip_lora_down", x.device, drop,
+                            (x.data_ptr(), x.stride(0), bt.data_ptr(), bt.stride(0), e.data_ptr(), RP, _ptr(et), MP, M, K, RP)))
     return e, et
 
 
@@ -463,9 +460,7 @@ def new_dropout_seed(device) -> torch.Tensor:
 def dropout_mask(seed: torch.Tensor, M: int, K: int, p: float) -> torch.Tensor:
     """the (M, K) keep mask the rank-r kernels regenerate from `seed` (bool tensor; tests / inspection)"""
     mask = torch.empty((M, K), dtype=torch.uint8, device=seed.device)
-    with torch.cuda.device(seed.device):
-        rc = _lib.lib().fastmax_hip_lora_dropout_mask(mask.data_ptr(), M, K, seed.data_ptr(), float(p), _stream(seed.device))
-    _lib.check(rc, "fastmax_hip_lora_dropout_mask")
+    _call("fastmax_hip_lora_dropout_mask", seed.device, (mask.data_ptr(), M, K, seed.data_ptr(), float(p)))
     return mask.bool()
 
 
@@ -481,18 +476,15 @@ def lora_tn(et: torch.Tensor, x: torch.Tensor, R: int = None, dtype=torch.float3
     M, ncols = x.shape
     RP = et.shape[0]
     R = RP if R is None else R
-    L = _lib.lib()
-    nb = L.fastmax_hip_lora_tn_workspace(M, ncols, RP)
+    nb = _lib.lib().fastmax_hip_lora_tn_workspace(M, ncols, RP)
     if nb < 0:
         raise NotImplementedError(f"lora_tn: unsupported shape M={M} ncols={ncols} RP={RP}")
     kdt = torch.bfloat16 if dtype == torch.bfloat16 else torch.float32
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     out = torch.empty((ncols, R) if transpose else (R, ncols), dtype=kdt, device=x.device)
-    call, extra = (L.fastmax_hip_lora_tn, ()) if drop is None else (L.fastmax_hip_lora_tn_dropout, (drop[0].data_ptr(), float(drop[1])))
-    with torch.cuda.device(x.device):
-        rc = call(et.data_ptr(), et.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(),
-                  _lib.BF16 if kdt == torch.bfloat16 else _lib.F32, int(transpose), R, ws.data_ptr(), M, ncols, RP, *extra, _stream(x.device))
-    _lib.check(rc, "fastmax_hip_lora_tn")
+    _call(*_dropout_variant("fastmax_hip_lora_tn", x.device, drop,
+                            (et.data_ptr(), et.stride(0), x.data_ptr(), x.stride(0), out.data_ptr(), _DT[kdt], int(transpose), R,
+                             ws.data_ptr(), M, ncols, RP)))
     return out if dtype == kdt else out.to(dtype)
 
 
@@ -500,12 +492,9 @@ def lora_up_(y: torch.Tensor, e: torch.Tensor, bn: torch.Tensor, bias=None, tran
     """y (M, N) += e (M, R) bn^T (+ bias), in place; bn is (N, R), or (R, N) with ``transposed``; bf16, bias float32.
     drop = (seed, p): the added product passes through the dropout mask of that seed (y has the shape of the dropped-out x)."""
     M, N = y.shape
-    L = _lib.lib()
-    call, extra = (L.fastmax_hip_lora_up, ()) if drop is None else (L.fastmax_hip_lora_up_dropout, (drop[0].data_ptr(), float(drop[1])))
-    with torch.cuda.device(y.device):
-        rc = call(y.data_ptr(), y.stride(0), e.data_ptr(), e.stride(0), bn.data_ptr(), bn.stride(0), int(transposed),
-                  None if bias is None else bias.data_ptr(), M, N, e.shape[1], *extra, _stream(y.device))
-    _lib.check(rc, "fastmax_hip_lora_up")
+    _call(*_dropout_variant("fastmax_hip_lora_up", y.device, drop,
+                            (y.data_ptr(), y.stride(0), e.data_ptr(), e.stride(0), bn.data_ptr(), bn.stride(0), int(transposed),
+                             _ptr(bias), M, N, e.shape[1])))
     return y
 
 
@@ -521,10 +510,8 @@ class _ScatterRowsFn(torch.autograd.Function):
     def forward(ctx, B, rowmap, ind, part, scaling, N, RP):
         Bc = B.detach().contiguous()
         et = torch.empty((RP, N), dtype=torch.bfloat16, device=B.device)
-        with torch.cuda.device(B.device):
-            rc = _lib.lib().fastmax_hip_lora_scatter(Bc.data_ptr(), _KDT[Bc.dtype], Bc.shape[1], rowmap.data_ptr(), rowmap.shape[0],
-                                                     float(scaling), et.data_ptr(), N, N, RP, _stream(B.device))
-        _lib.check(rc, "fastmax_hip_lora_scatter")
+        _call("fastmax_hip_lora_scatter", B.device,
+              (Bc.data_ptr(), _KDT[Bc.dtype], Bc.shape[1], rowmap.data_ptr(), rowmap.shape[0], float(scaling), et.data_ptr(), N, N, RP))
         ctx.save_for_backward(ind, part)
         ctx.meta = (Bc.shape, Bc.dtype, float(scaling))
         return et
@@ -537,11 +524,9 @@ class _ScatterRowsFn(torch.autograd.Function):
             d_et = d_et.float()
         d_et = d_et.contiguous()
         dB = torch.empty(shape, dtype=dt, device=d_et.device)
-        with torch.cuda.device(d_et.device):
-            rc = _lib.lib().fastmax_hip_lora_scatter_backward(d_et.data_ptr(), _KDT[d_et.dtype], d_et.stride(0), ind.data_ptr(),
-                                                              part.data_ptr(), scaling, dB.data_ptr(), _KDT[dt], shape[0], shape[1],
-                                                              _stream(d_et.device))
-        _lib.check(rc, "fastmax_hip_lora_scatter_backward")
+        _call("fastmax_hip_lora_scatter_backward", d_et.device,
+              (d_et.data_ptr(), _KDT[d_et.dtype], d_et.stride(0), ind.data_ptr(), part.data_ptr(), scaling, dB.data_ptr(), _KDT[dt],
+               shape[0], shape[1]))
         return dB, None, None, None, None, None, None
 
 
@@ -550,13 +535,9 @@ def hip_gemm(x2: torch.Tensor, w: torch.Tensor, scales, bias, ea, eb, N: int) ->
     None, else the packed NF4 codes of an (N, K) weight with their block scales (decoded inside the kernel's loop)."""
     M, K = x2.shape
     y = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
-    with torch.cuda.device(x2.device):
-        rc = _lib.lib().fastmax_hip_qlora_gemm(x2.data_ptr(), x2.stride(0), w.data_ptr(), 0 if scales is None else 1,
-                                               None if scales is None else scales.ref, None if bias is None else bias.data_ptr(),
-                                               None if ea is None else ea.data_ptr(), None if eb is None else eb.data_ptr(),
-                                               0 if ea is None else ea.shape[1], y.data_ptr(), y.stride(0), M, N, K,
-                                               _stream(x2.device))
-    _lib.check(rc, "fastmax_hip_qlora_gemm")
+    _call("fastmax_hip_qlora_gemm", x2.device,
+          (x2.data_ptr(), x2.stride(0), w.data_ptr(), 0 if scales is None else 1, None if scales is None else scales.ref, _ptr(bias),
+           _ptr(ea), _ptr(eb), 0 if ea is None else ea.shape[1], y.data_ptr(), y.stride(0), M, N, K))
     return y
 
 
@@ -567,13 +548,9 @@ def hip_gemm_rope(x2, w, bias, ea, eb, N, cos32, sin32, B, T, G, qpk, hs, rope_n
     q = torch.empty((B, G * qpk, T, hs), dtype=torch.bfloat16, device=x2.device)
     k = torch.empty((B, G, T, hs), dtype=torch.bfloat16, device=x2.device)
     v = torch.empty((B, G, T, hs), dtype=torch.bfloat16, device=x2.device)
-    with torch.cuda.device(x2.device):
-        rc = _lib.lib().fastmax_hip_qlora_gemm_rope(x2.data_ptr(), x2.stride(0), w.data_ptr(), None if bias is None else bias.data_ptr(),
-                                                    None if ea is None else ea.data_ptr(), None if eb is None else eb.data_ptr(),
-                                                    0 if ea is None else ea.shape[1], cos32.data_ptr(), sin32.data_ptr(),
-                                                    q.data_ptr(), k.data_ptr(), v.data_ptr(), M, N, K, T, G, qpk, hs, rope_n,
-                                                    1 if tables16 else 0, _stream(x2.device))
-    _lib.check(rc, "fastmax_hip_qlora_gemm_rope")
+    _call("fastmax_hip_qlora_gemm_rope", x2.device,
+          (x2.data_ptr(), x2.stride(0), w.data_ptr(), _ptr(bias), _ptr(ea), _ptr(eb), 0 if ea is None else ea.shape[1], cos32.data_ptr(),
+           sin32.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), M, N, K, T, G, qpk, hs, rope_n, 1 if tables16 else 0))
     return q, k, v
 
 
@@ -607,6 +584,8 @@ class _QLoRALinearFn(torch.autograd.Function):
         if ctx.gemm:
             return hip_gemm(x2, _weight_operand(base, False), None, bias, ea, eb, N)
         y = torch.empty((M, N), dtype=x2.dtype, device=x2.device)
+        # the decode-size product, spelled out rather than through ops._call: its host time per call came out above the two
+        # runs of the hand-written form it was measured against (profiles/r24_one_boundary.md)
         with torch.cuda.device(x2.device):
             rc = _lib.lib().fastmax_hip_nf4_linear_forward_s(
                 x2.data_ptr(), x2.stride(0), base.weight.data_ptr(), scales_of(base).ref,
@@ -628,10 +607,8 @@ class _QLoRALinearFn(torch.autograd.Function):
             dx = hip_gemm(dy, _weight_operand(base, True, allow_resident=M >= DENSE_M), None, None, None, None, K)
         elif ctx.needs_input_grad[0]:
             dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
-            with torch.cuda.device(dy.device):
-                rc = _lib.lib().fastmax_hip_nf4_linear_backward_input_s(dy.data_ptr(), N, base.weight.data_ptr(), scales_of(base).ref,
-                                                                        dx.data_ptr(), K, M, N, K, _KDT[dy.dtype], _stream(dy.device))
-            _lib.check(rc, "fastmax_hip_nf4_linear_backward_input_s")
+            _call("fastmax_hip_nf4_linear_backward_input_s", dy.device,
+                  (dy.data_ptr(), N, base.weight.data_ptr(), scales_of(base).ref, dx.data_ptr(), K, M, N, K, _KDT[dy.dtype]))
         if ea is not None:
             # the rank-r products of the backward pass as streaming HIP kernels (lora_thin.hip), one pass over dy each
             dyb = dy.to(torch.bfloat16)

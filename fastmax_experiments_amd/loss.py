@@ -15,30 +15,24 @@ from typing import List, Union
 
 import torch
 
-from . import _lib
-from .ops import _DT, _stream
+from .ops import _DT, _call, _ptr
 
 
 def _rows_forward(logits2d, targets1d, ignore_index):
     M, V = logits2d.shape
     loss = torch.empty(M, dtype=torch.float32, device=logits2d.device)
     lse = torch.empty(M, dtype=torch.float32, device=logits2d.device)
-    with torch.cuda.device(logits2d.device):
-        rc = _lib.lib().fastmax_hip_cross_entropy_forward(logits2d.data_ptr(), logits2d.stride(0), targets1d.data_ptr(),
-                                                          loss.data_ptr(), lse.data_ptr(), M, V, ignore_index, _DT[logits2d.dtype],
-                                                          _stream(logits2d.device))
-    _lib.check(rc, "fastmax_hip_cross_entropy_forward")
+    _call("fastmax_hip_cross_entropy_forward", logits2d.device,
+          (logits2d.data_ptr(), logits2d.stride(0), targets1d.data_ptr(), loss.data_ptr(), lse.data_ptr(), M, V, ignore_index,
+           _DT[logits2d.dtype]))
     return loss, lse
 
 
 def _rows_backward(logits2d, targets1d, lse, grad_loss, grad_scale, ignore_index, out):
     M, V = logits2d.shape
-    with torch.cuda.device(logits2d.device):
-        rc = _lib.lib().fastmax_hip_cross_entropy_backward(logits2d.data_ptr(), logits2d.stride(0), targets1d.data_ptr(),
-                                                           lse.data_ptr(), None if grad_loss is None else grad_loss.data_ptr(),
-                                                           ctypes.c_float(grad_scale), out.data_ptr(), out.stride(0), M, V,
-                                                           ignore_index, _DT[logits2d.dtype], _stream(logits2d.device))
-    _lib.check(rc, "fastmax_hip_cross_entropy_backward")
+    _call("fastmax_hip_cross_entropy_backward", logits2d.device,
+          (logits2d.data_ptr(), logits2d.stride(0), targets1d.data_ptr(), lse.data_ptr(), _ptr(grad_loss), ctypes.c_float(grad_scale),
+           out.data_ptr(), out.stride(0), M, V, ignore_index, _DT[logits2d.dtype]))
     return out
 
 

@@ -13,7 +13,6 @@ On a CPU bucket `step` runs the same formulas as tensor ops over the flat buffer
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import List, Optional, Sequence, Tuple
 
@@ -21,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import _DT, _call, _ptr
 
-_DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
 SEGMENT_RECORD = np.dtype([("param", "<u8"), ("offset", "<i8"), ("numel", "<i8"), ("dtype", "<i4"), ("pad", "<i4")])
 CHUNK_RECORD = np.dtype([("start", "<i8"), ("segment", "<i4"), ("len", "<i4")])
 RECORD_BYTES = 64                     # the scalar record at the head of the workspace (fastmax_hip_optim.h)
@@ -200,25 +199,18 @@ class FlatAdamW(torch.optim.Optimizer):
         if tuple(p.data_ptr() for p in params) != self._ptrs:
             raise RuntimeError("a parameter's storage moved since FlatAdamW was built (model.to(...), a re-assigned .data): "
                                "the segment table holds its old address; build the optimizer after the model is in place")
-        L = _lib.lib()
         flat = self.bucket.flat
         dev = flat.device
         b1, b2 = (float(b) for b in group["betas"])
         clip = max_norm is not None
-        ws = ctypes.c_void_p(self._ws.data_ptr())
-        with torch.cuda.device(dev):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if clip or self.skip_nonfinite:
-                _lib.check(L.fastmax_hip_adamw_norm(flat.data_ptr(), _DT[flat.dtype], flat.numel(), grad_scale, ws,
-                                                    self._ws_bytes, stream), "fastmax_hip_adamw_norm")
-            rc = L.fastmax_hip_adamw_update(
-                flat.data_ptr(), _DT[flat.dtype], flat.numel(), self.m.data_ptr(), self.v.data_ptr(),
-                None if self.master is None else self.master.data_ptr(), sum(self._lowp),
-                self._segments.data_ptr(), len(params), self._chunks.data_ptr(), self._n_chunks,
-                float(group["lr"]), None if lr is None else lr.data_ptr(), b1, b2, 1.0 - b1, 1.0 - b2, float(group["eps"]),
-                float(group["weight_decay"]), grad_scale, float(max_norm) if clip else 0.0, int(clip),
-                int(self.skip_nonfinite), int(zero_grad), ws, self._ws_bytes, stream)
-        _lib.check(rc, "fastmax_hip_adamw_update")
+        ws = (self._ws.data_ptr(), self._ws_bytes)          # the optimizer's own: the record at its head lives across steps
+        if clip or self.skip_nonfinite:
+            _call("fastmax_hip_adamw_norm", dev, (flat.data_ptr(), _DT[flat.dtype], flat.numel(), grad_scale, *ws))
+        _call("fastmax_hip_adamw_update", dev,
+              (flat.data_ptr(), _DT[flat.dtype], flat.numel(), self.m.data_ptr(), self.v.data_ptr(), _ptr(self.master),
+               sum(self._lowp), self._segments.data_ptr(), len(params), self._chunks.data_ptr(), self._n_chunks,
+               float(group["lr"]), _ptr(lr), b1, b2, 1.0 - b1, 1.0 - b2, float(group["eps"]), float(group["weight_decay"]),
+               grad_scale, float(max_norm) if clip else 0.0, int(clip), int(self.skip_nonfinite), int(zero_grad), *ws))
 
     def _step_rehearsal(self, group, grad_scale, max_norm, zero_grad, lr):
         """the kernels' formulas as float32 tensor ops over the flat buffers (CPU bucket only)"""

@@ -2,7 +2,7 @@
  * scale and bias that lit_gpt/adapter_v2.py:50-62 puts behind every linear of the model, y = adapter_scale * (linear(x) +
  * adapter_bias), as one pass forward and one pass backward that also leaves both parameter gradients.  The dtype and error enums
  * are those of fastmax_hip.h; the entry points belong to the same library and FASTMAX_ABI_VERSION (additions only) and are bound
- * by the side table ADAPTER_ABI in fastmax_experiments_amd/_lib.py.
+ * by their rows of the one table ABI in fastmax_experiments_amd/_lib.py.
  *
  * Conventions (those of fastmax_hip_block.h): every matrix operand is (M rows, N columns) with a row stride in ELEMENTS and unit
  * stride along the row; `dtype` (FASTMAX_F32 / BF16 / F16) is the activation dtype, `param_dtype` (that of scale and bias, N

@@ -2,7 +2,7 @@
  * masked polynomial attention at each new position over a cache of the K and V rows seen so far, for head sizes 1 .. 256, where
  * the carried-state caches of fastmax_hip.h stop at 128 and move (D+1)(D+2)/2 (D+1) floats per token whatever the length.  The
  * dtype and error enums are those of fastmax_hip.h; the entry points belong to the same library and FASTMAX_ABI_VERSION
- * (additions only) and are bound by the side table KV_DECODE_ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
+ * (additions only) and are bound by their rows of the one table ABI in fastmax_experiments_amd/_lib.py.  Everything runs on
  * `stream`; nothing is allocated, nothing is read back, there are no atomics, and every sum has a fixed order.
  *
  *   the state     fastmax_hip_kv_decode_state_bytes(B, Hkv, D, max_len, dtype) bytes of device memory, 16-byte aligned:

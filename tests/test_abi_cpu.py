@@ -21,7 +21,7 @@ def test_header_symbols_all_exported(lib):
     from fastmax_experiments_amd import _lib
     from test_binding_cpu import header_prototypes
     declared = {name for h in _lib.HEADERS for name, _, _ in header_prototypes(h)}
-    assert len(declared) == 98
+    assert len(declared) == 106
     assert declared == set(_lib.SYMBOLS), declared ^ set(_lib.SYMBOLS)
     for s in declared:
         assert hasattr(lib, s), s

@@ -64,7 +64,8 @@ def test_parser_reads_the_header():
 def test_each_header_declares_its_own_entry_points():
     assert _lib.HEADERS == ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h",
                             "fastmax_hip_optim.h", "fastmax_hip_next_token.h", "fastmax_hip_neox.h", "fastmax_hip_cursor.h",
-                            "fastmax_hip_nucleus.h", "fastmax_hip_moe.h", "fastmax_hip_moe_decode.h", "fastmax_hip_head.h")
+                            "fastmax_hip_nucleus.h", "fastmax_hip_moe.h", "fastmax_hip_moe_decode.h", "fastmax_hip_head.h",
+                            "fastmax_hip_adapter.h", "fastmax_hip_kv_decode.h")
     names = {h: [n for n, _, _ in header_prototypes(h)] for h in _lib.HEADERS}
     assert len(names["fastmax_hip.h"]) == 59
     assert names["fastmax_hip_generate.h"] == ["fastmax_hip_p2_decode_step_qkv_supported", "fastmax_hip_p2_decode_step_qkv"]
@@ -75,6 +76,9 @@ def test_each_header_declares_its_own_entry_points():
     assert [len(_lib.ABI[n][1]) for n in names["fastmax_hip_linearmax_decode.h"]] == [4, 15]
     # q, q_strides, k, k_strides, v, v_strides: the strides are bound as int64 pointers, not as untyped ones
     assert [t is _lib.i64p for t in _lib.ABI["fastmax_hip_linearmax_decode_advance"][1][:6]] == [False, True] * 3
+    assert len(names["fastmax_hip_adapter.h"]) == 3 and len(names["fastmax_hip_kv_decode.h"]) == 5
+    assert [t is _lib.i64p for t in _lib.ABI["fastmax_hip_kv_decode_append_attend"][1][:6]] == [False, True] * 3
+    assert [t is _lib.i64p for t in _lib.ABI["fastmax_hip_kv_decode_load"][1][:4]] == [False, True] * 2
     every = [n for h in _lib.HEADERS for n in names[h]]
     assert len(every) == len(set(every)), "a name is declared in two headers"
 
@@ -112,8 +116,10 @@ def test_binding_table_matches_every_prototype():
 
 # crc32 of the (name, return kind, parameter kinds) rows.  The first two were taken on the commit before the four tables became
 # one: its ABI alone (the 59 rows of fastmax_hip.h) and its tables concatenated in HEADERS order (68 rows).  The third on the commit
-# before the eight side headers' tables joined them: its nine tables concatenated in HEADERS order (98 rows).
-PINNED_FIRST_HEADER_CRC, PINNED_FOUR_HEADERS_CRC, PINNED_ABI_CRC = 329697078, 1240384090, 3488605058
+# before the eight side headers' tables joined them: its nine tables concatenated in HEADERS order (98 rows).  The fourth on the
+# commit before the last two side tables joined them: its ABI, then its adapter-v2 table, then its KV-cache decode table (106 rows).
+PINNED_FIRST_HEADER_CRC, PINNED_FOUR_HEADERS_CRC, PINNED_TWELVE_HEADERS_CRC = 329697078, 1240384090, 3488605058
+PINNED_ABI_CRC = 1128403750
 
 
 def test_pinned_table_and_abi_version_are_unchanged():
@@ -122,9 +128,10 @@ def test_pinned_table_and_abi_version_are_unchanged():
         return zlib.crc32(repr([(n, ctypes_kind(r), [ctypes_kind(a) for a in args]) for n, (r, args) in rows]).encode())
     rows = list(_lib.ABI.items())
     assert _lib.ABI_VERSION == 9
-    assert len(rows) == 98 and _lib.SYMBOLS == list(_lib.ABI)
+    assert len(rows) == 106 and _lib.SYMBOLS == list(_lib.ABI)
     assert digest(rows[:59]) == PINNED_FIRST_HEADER_CRC
     assert digest(rows[:68]) == PINNED_FOUR_HEADERS_CRC
+    assert digest(rows[:98]) == PINNED_TWELVE_HEADERS_CRC
     assert digest(rows) == PINNED_ABI_CRC
 
 

@@ -106,6 +106,29 @@ def test_state_host_side_contract():
             f(torch.zeros(1, 1, 4, 3, 16), row, row, 16)
 
 
+def test_any_bounded_cache_is_refused_up_front_by_its_own_max_len():
+    """the generation loops ask the cache how much it holds; they do not decide by its class.  Nothing runs on a device."""
+    from fastmax_experiments_amd import decode, generate
+    from fastmax_experiments_amd.block import Block
+
+    class Ring(decode._DecodeState):
+        """a cache kind of the test's own: nothing but a capacity"""
+        max_len = 5
+
+        def __init__(self, B):
+            self.B = B
+
+    assert not issubclass(Ring, decode.FastmaxKVDecodeState) and decode._DecodeState.max_len is None
+    blocks = [Block.from_config("pythia-14m")]
+    head = generate.NextTokenHead(128, 40)
+    wte, prompt = torch.zeros(40, 128), torch.zeros(2, 3, dtype=torch.int64)
+    kw = dict(cos=torch.zeros(16, 8), sin=torch.zeros(16, 8))
+    with pytest.raises(ValueError, match="holds at most 5"):
+        generate.generate(wte, blocks, head, [Ring(2)], prompt, 7, **kw)                # 6 tokens are fed
+    with pytest.raises(ValueError, match="holds at most 5"):
+        generate.GraphedDecoder(wte, blocks, head, [Ring(2)], max_len=7, **kw)
+
+
 @pytest.mark.parametrize("dtype,table_dtype", [(torch.float32, torch.float32), (torch.bfloat16, torch.bfloat16),
                                                (torch.bfloat16, torch.float32)])
 @pytest.mark.parametrize("B,T,G,qpk,hs,rope_n", [(2, 5, 2, 3, 16, 16), (1, 3, 1, 4, 16, 4), (2, 1, 4, 1, 8, 8)])

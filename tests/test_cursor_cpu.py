@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from fastmax_experiments_amd import _lib, build, generate
+from fastmax_experiments_amd.decode import _DecodeState
 from test_binding_cpu import header_text
 
 
@@ -72,9 +73,12 @@ def test_sample_cursor_rejects_bad_calls_before_any_launch():
 
 
 # ---- 3. the host contract ------------------------------------------------------------------------------------------------------
-class _State:
+class _State(_DecodeState):
     """stands for a decode state cache where nothing is run"""
     B, count = 2, 0
+
+    def __init__(self):
+        pass
 
 
 def test_generate_refuses_a_decoder_built_for_another_loop():

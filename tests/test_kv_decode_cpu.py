@@ -1,20 +1,19 @@
 """KV-cache decode, everything that needs no device (include/fastmax_hip_kv_decode.h, csrc/fastmax_kv_decode.hip,
 fastmax_experiments_amd/decode.py FastmaxKVDecodeState):
 
-1. the source and the header in the build's lists; every row of _lib.KV_DECODE_ABI against its prototype, exported and bound; ABI,
-   HEADERS and ABI_VERSION untouched; the header's constants against _lib's;
+1. the source in the build's list and the header's constants against _lib's (the header's rows of _lib.ABI are checked where
+   every header's are, in test_binding_cpu.py);
 2. the state and workspace sizes against the header's formulas, and 0 for what the route does not take;
 3. every rejection the header lists, with its code, returned on made-up aligned addresses before any launch;
 4. the constructor's refusals and the host-side refusals of generate() and the block."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
 from fastmax_experiments_amd import _lib, build, decode
-from test_binding_cpu import ctypes_kind, header_prototypes, header_text
+from test_binding_cpu import header_text
 
 ES = {_lib.F32: 4, _lib.BF16: 2, _lib.F16: 2}
 
@@ -22,39 +21,10 @@ ES = {_lib.F32: 4, _lib.BF16: 2, _lib.F16: 2}
 # ---- 1. the build and the binding ------------------------------------------------------------------------------------------------
 def test_the_build_compiles_the_source_and_watches_the_header():
     assert "fastmax_kv_decode.hip" in build.SOURCES
-    assert os.path.join("..", "..", "include", _lib.KV_DECODE_HEADER) in build.HEADERS
-    assert _lib.KV_DECODE_HEADER == "fastmax_hip_kv_decode.h" and _lib.KV_DECODE_HEADER not in _lib.HEADERS
-    assert '#include "fastmax_hip.h"' in header_text(_lib.KV_DECODE_HEADER)
-
-
-def test_side_table_rows_match_the_header_and_the_library():
-    protos = header_prototypes(_lib.KV_DECODE_HEADER)
-    assert [n for n, _, _ in protos] == list(_lib.KV_DECODE_ABI) and len(protos) == 5
-    raw, bound = ctypes.CDLL(_lib.LIB_PATH), _lib.lib()
-    for name, ret, kinds in protos:
-        restype, argtypes = _lib.KV_DECODE_ABI[name]
-        assert ctypes_kind(restype) == ret, name
-        assert [ctypes_kind(t) for t in argtypes] == kinds, name
-        assert hasattr(raw, name), f"{name} is not exported"
-        fn = getattr(bound, name)
-        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
-        if ret == "int":
-            assert kinds[-1] == "pointer", f"{name}: the stream comes last"
-    assert not set(_lib.KV_DECODE_ABI) & (set(_lib.ABI) | set(_lib.ADAPTER_ABI))
-    # q, k, v strides are bound as int64 pointers, not as untyped ones
-    assert [t is _lib.i64p for t in _lib.KV_DECODE_ABI["fastmax_hip_kv_decode_append_attend"][1][:6]] == [False, True] * 3
-    assert [t is _lib.i64p for t in _lib.KV_DECODE_ABI["fastmax_hip_kv_decode_load"][1][:4]] == [False, True] * 2
-
-
-def test_the_one_table_and_the_abi_version_are_untouched():
-    assert _lib.ABI_VERSION == 9 and len(_lib.ABI) == 98 and _lib.SYMBOLS == list(_lib.ABI)
-    assert len(_lib.HEADERS) == 12 and _lib.HEADERS[-1] == "fastmax_hip_head.h"
-    assert len(_lib.ADAPTER_ABI) == 3
-    assert _lib.lib().fastmax_hip_abi_version() == 9
 
 
 def test_constants_match_the_header():
-    text = header_text(_lib.KV_DECODE_HEADER)
+    text = header_text("fastmax_hip_kv_decode.h")
 
     def define(name):
         return int(re.search(rf"#define {name} (\d+)", text).group(1))

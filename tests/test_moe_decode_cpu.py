@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from fastmax_experiments_amd import _lib, build
+from fastmax_experiments_amd.decode import _DecodeState
 from test_binding_cpu import header_text
 
 
@@ -120,7 +121,7 @@ def test_the_device_route_leaves_every_other_call_where_it_was():
         layer.expert_table()
 
 
-class _State:
+class _State(_DecodeState):
     """what GraphedDecoder reads of a state cache before it touches a device"""
     def __init__(self, B):
         self.B, self.count = B, 0
