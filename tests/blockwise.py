@@ -178,3 +178,107 @@ def dense_rows(q, k, v, go=None, nt=None, p=1, mask=True, g_const=None, rows=512
         dk[:n] += dS.T @ q[r0:r1] / nt
         dv[:n] += (P / gb[:, None]).T @ G
     return (o, g) if go is None else (o, g, dq, dk, dv)
+
+
+# --------------------------------------------------------------------------------------
+# the tile kernels: a rounded model of a correct kernel (calibration) and exact results with one tile fault (power)
+# --------------------------------------------------------------------------------------
+def _rounder(dtype):
+    """float64 array -> the same values rounded to ``dtype`` ("bf16" / "f16"), back in float64"""
+    import torch
+    tdt = {"bf16": torch.bfloat16, "f16": torch.float16}[dtype]
+    return lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(tdt).double().numpy()
+
+
+def tile_model(q, k, v, go, nt, p, mask, dtype, g_const=None, tile_forward=True, unit=None):
+    """(o, g, dq, dk, dv) of one head as a correct tile kernel of ``dtype`` ("f32", "bf16", "f16") delivers them.
+
+    16-bit: float64 arithmetic (the kernels accumulate in fp32, far below the roundings kept here) with the roundings the
+    sources name: q, k, v, go exact in ``dtype``; P = f(s) rounded to ``dtype`` before P @ V and P^T @ gt, while g sums the
+    unrounded P (poly, fastmax_quad32_mfma.hip:138-165), so that o_0 = v_0 rd(P_00) / P_00 and not v_0; masked o stored in
+    ``dtype`` (unmasked: float32) and read back by the backward for c_i = G_i . o_i (bwd_prep_kernel,
+    fastmax_quad_mfma_bwd.hip:60); gt_i = G_i / g_i in ``dtype`` (fastmax_quad_mfma_bwd.hip:65, fastmax_quad32_bwd.hip:15);
+    dS rounded to ``dtype`` before dS @ K and dS^T @ Q (pack_tile, fastmax_quad32_bwd.hip:55-70); dq, dk, dv stored in
+    ``dtype``.  The first rows of dq and dk feel the two roundings of o most: dS_ij = G_i . (v_j - o_i) / g_i is a difference
+    of nearly equal terms while o_i is still an average of a few value rows.
+    ``tile_forward=False``: the forward is a scan or a vector-ALU kernel, whose o is the exact quotient rounded once.
+    ``unit`` (default: what the 32-row tiles do, launch_quad32_u, fastmax_quad32_mfma.hip:402-408, and launch_bwd32,
+    fastmax_quad32_bwd.hip:632-637): single-part bf16 operands are scaled by a = 1 / nt on load only when a is a power of
+    two.  Otherwise the score chain carries u = 1/a + q . k and what is rounded to bf16 is the unscaled polynomial,
+    P / e2 = u u + 1/a^2 (p = 2, e2 = a^2 / 2) or u (p = 1, e2 = a) (fastmax_quad32_mfma.hip:130-165), and the unscaled
+    dS / e1 = U u (p = 2, e1 = a) (fastmax_quad32_bwd.hip:177-186); e1, e2 are applied in fp32 afterwards.  The same
+    relative rounding of another number: rd(P_00 / e2) e2 / P_00 can lie on the other side of 1 than rd(P_00) / P_00, and
+    then o_0 = rd(v_0 rd(P_00) / P_00) is one bf16 step away from v_0 in every element instead of equal to it.
+    f32: the same operator evaluated in numpy float32 with no further rounding.  ``g_const`` as in ``dense_rows``."""
+    f32 = dtype == "f32"
+    if unit is None:
+        unit = dtype != "bf16" or float(np.frexp(np.float32(1.0 / nt))[0]) == 0.5
+    e2 = 1.0 if unit else ((1.0 / nt) if p == 1 else 0.5 / (nt * nt))
+    e1 = 1.0 if unit or p == 1 else 1.0 / nt
+    wt = np.float32 if f32 else np.float64
+    rd = (lambda x: x) if f32 else _rounder(dtype)
+    q, k, v, go = (np.asarray(t, wt) for t in (q, k, v, go))
+    Nq, Nk = q.shape[0], k.shape[0]
+    a = wt(1.0 / nt)
+    s = (q @ k.T) * a
+    keep = (np.arange(Nk)[None, :] <= np.arange(Nq)[:, None]) if mask else np.ones((Nq, Nk), bool)
+    P = np.where(keep, orc._f(s, p), wt(0))
+    g = P.sum(1) if mask else P.sum(1) - wt(Nk) + wt(Nq if g_const is None else g_const)
+    Pr = rd(P / e2) * e2
+    o = ((Pr if tile_forward else P) @ v) / g[:, None]
+    o = rd(o) if mask else o.astype(np.float32).astype(wt)
+    w = wt(1) / g
+    gt = rd(go * w[:, None])
+    cw = (go * o).sum(1) * w
+    dS = rd(np.where(keep, (gt @ v.T - cw[:, None]) * orc._fprime(s, p), wt(0)) / e1) * e1
+    dq, dk, dv = rd((dS @ k) * a), rd((dS.T @ q) * a), rd(Pr.T @ gt)
+    return tuple(np.asarray(t, np.float64) for t in (o, g, dq, dk, dv))
+
+
+TILE_FAULTS = ("last_key_tile_dk_zero", "last_key_tile_dv_zero", "last_query_tile_skips_first_key_tile",
+               "mask_plus_one_in_last_tile", "first_key_tile_twice_in_last_query_tile", "low_part_lost_in_last_key_tile")
+FAULT_TENSOR = dict(zip(TILE_FAULTS, ("dk", "dv", "o", "o", "dq", "dv")))
+
+
+def emulate_tiles(q, k, v, go, nt, p, mask, tile, fault=None, g_const=None):
+    """Exact float64 (o, g, dq, dk, dv) of one head, computed the way a kernel with ``tile``-row tiles would, with one
+    fault; the last tile is the ragged one, rows ``tile * ((N - 1) // tile)`` to N.  ``fault``:
+      "last_key_tile_dk_zero", "last_key_tile_dv_zero"  -- the last key tile of dk / dv is never written
+      "last_query_tile_skips_first_key_tile"            -- o and g of the last query tile miss keys 0:tile
+      "mask_plus_one_in_last_tile"                      -- the diagonal compare of the last query tile is off by one key
+                                                           (key + 1 <= row): each of its rows loses its own key in o, g
+      "first_key_tile_twice_in_last_query_tile"         -- dq of the last query tile adds keys 0:tile twice
+      "low_part_lost_in_last_key_tile"                  -- dv of the last key tile from P rounded to bf16: the low half
+                                                           of a split-bf16 operand is dropped
+    No fault: equal to ``dense_rows``."""
+    assert fault is None or fault in TILE_FAULTS, fault
+    q, k, v, go = (np.asarray(t, np.float64) for t in (q, k, v, go))
+    Nq, Nk = q.shape[0], k.shape[0]
+    a = 1.0 / nt
+    q0, k0 = tile * ((Nq - 1) // tile), tile * ((Nk - 1) // tile)
+    s = (q @ k.T) * a
+    keep = (np.arange(Nk)[None, :] <= np.arange(Nq)[:, None]) if mask else np.ones((Nq, Nk), bool)
+    const = 0.0 if mask else (Nq if g_const is None else g_const) - Nk
+    P = np.where(keep, orc._f(s, p), 0.0)
+    g = P.sum(1) + const
+    o = (P @ v) / g[:, None]
+    # the gradients take the exact o and g: a backward fault is a fault of the backward alone
+    dS = np.where(keep, (go @ v.T - (go * o).sum(1, keepdims=True)) / g[:, None] * orc._fprime(s, p), 0.0)
+    dq, dk, dv = (dS @ k) * a, (dS.T @ q) * a, (P / g[:, None]).T @ go
+    if fault in ("last_query_tile_skips_first_key_tile", "mask_plus_one_in_last_tile"):
+        Pb = P.copy()
+        if fault == "last_query_tile_skips_first_key_tile":
+            Pb[q0:, :tile] = 0.0
+        else:
+            Pb[q0:] *= (np.arange(Nk)[None, :] + 1 <= np.arange(q0, Nq)[:, None])
+        g = Pb.sum(1) + const
+        o = (Pb @ v) / g[:, None]
+    elif fault == "last_key_tile_dk_zero":
+        dk[k0:] = 0.0
+    elif fault == "last_key_tile_dv_zero":
+        dv[k0:] = 0.0
+    elif fault == "first_key_tile_twice_in_last_query_tile":
+        dq[q0:] += (dS[q0:, :tile] @ k[:tile]) * a
+    elif fault == "low_part_lost_in_last_key_tile":
+        dv[k0:] = (_rounder("bf16")(P[:, k0:]) / g[:, None]).T @ go
+    return o, g, dq, dk, dv

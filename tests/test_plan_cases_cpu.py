@@ -146,7 +146,7 @@ def test_both_sides_of_every_threshold_are_cases_and_differ(L, what, lo, hi, fie
 def test_gpu_cases_stay_small():
     for c in pc.GPU_CASES:
         B, H, Nq, Nk, D = c.shape
-        assert B * H <= 2 and max(Nq, Nk) <= 520, c.id
+        assert B * H <= 8 and max(Nq, Nk) <= 520, c.id          # 8 heads: the per-XCD workgroup mapping of the 32-row tiles
     assert len({c.id for c in pc.CASES}) == len(pc.CASES)
 
 
