@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # FASTMAX_LIB_PATH: A/B runs of tools/ against another build of the same library (never a different implementation)
 LIB_PATH = os.environ.get("FASTMAX_LIB_PATH") or os.path.join(HERE, "libfastmax_hip.so")
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16, F64 = 0, 1, 2, 3          # F64: the operator's entry points only, float64 in and out
 PATH_AUTO, PATH_QUADRATIC, PATH_RECURRENT, PATH_MFMA, PATH_QUADRATIC_MFMA = 0, 1, 2, 3, 4
 PATH_NAMES = {PATH_AUTO: "auto", PATH_QUADRATIC: "quadratic", PATH_RECURRENT: "recurrent", PATH_MFMA: "mfma", PATH_QUADRATIC_MFMA: "quadratic_mfma"}
 ABI_VERSION = 9
@@ -32,8 +32,8 @@ class Plan(ctypes.Structure):
 
 # enum fastmax_fwd_kernel / fastmax_bwd_kernel, by number
 FWD_KERNELS = ["FWD_QUADRATIC", "FWD_RECURRENT", "FWD_UNMASKED_LIN", "FWD_SCAN_V2", "FWD_SCAN_D128_2P", "FWD_SCAN_BF16", "FWD_SCAN_GEN",
-               "FWD_QUAD32", "FWD_QUAD_MFMA"]
-BWD_KERNELS = ["BWD_QUADRATIC", "BWD_UNMASKED_LIN", "BWD_LIN", "BWD_SCAN", "BWD_QUAD32", "BWD_QUAD_MFMA"]
+               "FWD_QUAD32", "FWD_QUAD_MFMA", "FWD_F64"]
+BWD_KERNELS = ["BWD_QUADRATIC", "BWD_UNMASKED_LIN", "BWD_LIN", "BWD_SCAN", "BWD_QUAD32", "BWD_QUAD_MFMA", "BWD_F64"]
 
 vp, sz, ci, i64, cf, cs = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p
 i64p, pp, planp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(Problem), ctypes.POINTER(Plan)

@@ -20,10 +20,15 @@ Differences, on purpose:
   * tensors may live on the HIP device (no .cpu() hop needed); CPU tensors are accepted like in
     lit_gpt/model.py:482-486 -- they are staged to the current HIP device, computed there, and the
     result is returned on the CPU.  Without a HIP device the call raises: there is no CPU fallback.
-  * float64 inputs are computed with float32 arithmetic (the kernels accumulate in fp32) and
-    returned as float64.
+float64 inputs are computed in float64, as the reference computes them (with 1/nt to 48 bits: it crosses the C ABI as the sum
+of two floats, a relative 2^-48 on the scores where normalize_term * sqrt(D) is no power of two): the float64 kernels (csrc/fastmax_f64.hip, the f64 matrix
+instruction) take any head size, so there is no padding, and the output and all three gradients are float64, masked and
+unmasked (the reference's float32 ``ones`` do not demote float64).  ``FP64_KERNELS`` (environment ``FASTMAX_FP64``, read once,
+default on) set to ``0`` restores the earlier route for A/B runs: float64 inputs cast to float32, the float32 kernels, the
+result cast back.
 """
 import logging
+import os
 
 import torch
 
@@ -33,6 +38,12 @@ _KERNEL_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 MAX_HEADS_PER_LAUNCH = 65535
+FP64_KERNELS = os.environ.get("FASTMAX_FP64", "1") != "0"
+
+
+def fp64_kernels():
+    """the switch as it stands now (tests and A/B tools set the module attribute)"""
+    return FP64_KERNELS
 
 
 def fastmax(q, k, v, mask=True, normalize_term=8, tensors_normalized=False, p=1, dropout_rate=0.0,
@@ -71,7 +82,7 @@ class fastattention_einops(torch.autograd.Function):
         home, in_dtype = q.device, q.dtype
         if in_dtype not in _KERNEL_DTYPES and in_dtype != torch.float64:
             raise TypeError(f"fastmax: unsupported dtype {in_dtype}")
-        kdt = torch.float32 if in_dtype == torch.float64 else in_dtype
+        kdt = torch.float32 if in_dtype == torch.float64 and not FP64_KERNELS else in_dtype
         qd, kd, vd = (ops._prep(t.detach().to(kdt), dev) for t in (q, k, v))
 
         if create_attn is not False:
@@ -85,7 +96,7 @@ class fastattention_einops(torch.autograd.Function):
         # head sizes that are not a whole number of 16-byte pieces would fall onto the vector-ALU kernels (measured 25-70x
         # slower at N = 2048): zero columns change neither q.k nor the populated columns of f(q.k) v, so pad to a multiple of 8
         # (nt keeps the true D) and slice the result
-        Dp = D if D % 8 == 0 else min(ops.MAX_HEAD_SIZE, (D + 7) // 8 * 8)
+        Dp = D if D % 8 == 0 or kdt == torch.float64 else min(ops.MAX_HEAD_SIZE, (D + 7) // 8 * 8)
         if Dp != D:
             qd, kd, vd = (torch.nn.functional.pad(t, (0, Dp - D)) for t in (qd, kd, vd))
         out_dt = _out_dtype(kdt, causal)
@@ -96,7 +107,7 @@ class fastattention_einops(torch.autograd.Function):
         ctx.home, ctx.in_dtype, ctx.forward_only, ctx.D = home, in_dtype, False, D
         if Dp != D:
             o = o[..., :D].contiguous()
-        if in_dtype == torch.float64:
+        if o.dtype != in_dtype and in_dtype == torch.float64:
             o = o.double()
         return o.to(home)
 

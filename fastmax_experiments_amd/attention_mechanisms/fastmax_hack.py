@@ -4,7 +4,9 @@ Reference: fastmax_hack.py:5-60.  Masked branch (36-60): mean-centre / max-norm 
 first- or second-order fastmax with normalize_term = 1.  Unmasked branch (6-33): same prologue,
 first order only (``p`` is ignored there), denominator constant N_k (line 21), float32 ``ones``
 promote low-precision inputs to a float32 result.
-The prologue and the attention both run in libfastmax_hip.so.  Which autograd nodes a call becomes is decided once, by
+The prologue and the attention both run in libfastmax_hip.so -- float64 inputs excepted: they are float64 end to end, the
+O(N D) prologue as differentiable float64 tensor ops on the device and the attention behind it in the float64 kernels
+(csrc/fastmax_f64.hip; ``fastmax.FP64_KERNELS`` off restores the float32-arithmetic route).  Which autograd nodes a call becomes is decided once, by
 ``linearmax_plan``; ``fastmax_hack``, ``fastmax_hack_grouped`` and the nodes below only read its record.
 """
 import functools
@@ -14,7 +16,7 @@ from typing import NamedTuple
 import torch
 
 from .. import ops
-from .fastmax import MAX_HEADS_PER_LAUNCH, _KERNEL_DTYPES, fastattention_einops
+from .fastmax import MAX_HEADS_PER_LAUNCH, _KERNEL_DTYPES, fastattention_einops, fp64_kernels
 
 # A/B switches, read once: 0 runs linearmax with gradients as two autograd nodes instead of one / hands the block's K to the
 # prologue per query head instead of per key head (tests use the routes behind them as references)
@@ -25,8 +27,9 @@ GROUPED_K = os.environ.get("FASTMAX_GROUPED_K", "1") != "0"
 class LinearmaxPlan(NamedTuple):
     operator: str      # "fused_forward" (one pass over q, k, v, no autograd node), "one_node" (_LinearmaxP1), "two_node" (two
     #                    _NormalizeQK nodes + fastattention_einops), "unmasked" (two _NormalizeQK nodes + _UnmaskedNk)
-    prologue: str      # where q, k are normalised: "in_scan" (by the scan kernels while they stage their tiles) or "cast" (the
-    #                    kernels of fastmax_normalize.hip, in the input dtype)
+    prologue: str      # where q, k are normalised: "in_scan" (by the scan kernels while they stage their tiles), "cast" (the
+    #                    kernels of fastmax_normalize.hip, in the input dtype) or "tensor_ops" (float64: differentiable float64
+    #                    tensor ops on the device, in front of the float64 kernels)
     prologue_bwd: str  # the sides whose prologue backward the scan kernels finish themselves: "both", "q" (grouped heads: the
     #                    group's dk' are summed by the prologue's own backward pass) or "none" (off the one-node route)
     k_layout: str      # "per_head", or K at its G key heads: "group_copies" (the prologue's store writes the G * rep normalised
@@ -34,7 +37,8 @@ class LinearmaxPlan(NamedTuple):
     slices: int        # batch slices the call is cut into (heads are independent; a launch takes 65535 of them)
 
 
-def linearmax_plan(dtype, B, H, Nq, Nk, D, p=1, mask=True, needs_grad=False, rep=1, views=False, train_supported=None):
+def linearmax_plan(dtype, B, H, Nq, Nk, D, p=1, mask=True, needs_grad=False, rep=1, views=False, train_supported=None,
+                   fp64_kernels=False):
     """The one decision "which nodes and kernels run for this linearmax call", from plain data (no tensor is touched).
     dtype: of q (anything but bf16 / fp16 computes in fp32); B, H: batch and heads of q AS LAUNCHED ((B*G, rep) beside group
     views); needs_grad: grad mode is on and one of q, k, v asks for a gradient; rep: query heads per key head when K arrives at
@@ -42,15 +46,22 @@ def linearmax_plan(dtype, B, H, Nq, Nk, D, p=1, mask=True, needs_grad=False, rep
     (B*G, rep, N, D) group views; train_supported: fastmax_hip_linearmax_train_supported's answer (host arithmetic) -- None asks
     the library, and only where the answer is needed.  Where the inputs live is not an argument: CPU tensors are moved to the
     device and take the same route.  A plan the library then rejects raises (_lib.check).  Launch-bound calls pay for every host
-    instruction, so the answer is kept per argument tuple; the two things it reads besides its arguments are part of that tuple."""
-    return _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, FUSED_TRAINING, ops._force_path)
+    instruction, so the answer is kept per argument tuple; the two things it reads besides its arguments are part of that tuple.
+    fp64_kernels: float64 inputs run float64 end to end ("two_node" / "unmasked" with the "tensor_ops" prologue).  fastmax_hack
+    passes fastmax.FP64_KERNELS; a caller that does not ask (the attention block) keeps the float32-arithmetic route for float64."""
+    return _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, FUSED_TRAINING, ops._force_path,
+                 bool(fp64_kernels))
 
 
 @functools.lru_cache(maxsize=4096)
-def _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, fused_training, forced_path):
-    """linearmax_plan's rules (forced_path: the kernel family ops.set_forced_path forces, which the library's answer reads)"""
+def _plan(dtype, B, H, Nq, Nk, D, p, mask, needs_grad, rep, views, train_supported, fused_training, forced_path, fp64_kernels):
+    """linearmax_plan's rules (forced_path: the kernel family ops.set_forced_path forces, which the library's answer reads;
+    fp64_kernels: fastmax.FP64_KERNELS)"""
     if D > ops.MAX_HEAD_SIZE:
         raise NotImplementedError(f"head size {D} > {ops.MAX_HEAD_SIZE} is not supported by the HIP kernels")
+    if dtype == torch.float64 and fp64_kernels and rep == 1:
+        slices = 1 if B * H <= MAX_HEADS_PER_LAUNCH or B == 1 else -(-B // max(1, MAX_HEADS_PER_LAUNCH // H))
+        return LinearmaxPlan("two_node" if mask else "unmasked", "tensor_ops", "none", "per_head", slices)
     kdt = dtype if dtype in _KERNEL_DTYPES else torch.float32
     k_layout = "per_head" if rep == 1 else ("group_views" if views else "group_copies")
     slices = 1
@@ -135,7 +146,7 @@ def fastmax_hack(q, k, v, p=1, mask=True):
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
     B, H, Nq, D = q.shape
     return linearmax(q, k, v, _plan(q.dtype, B, H, Nq, k.shape[2], D, p, mask, needs_grad, 1, False, None, FUSED_TRAINING,
-                                    ops._force_path), p, mask)
+                                    ops._force_path, fp64_kernels()), p, mask)
 
 
 def linearmax(q, k, v, plan, p=1, mask=True):
@@ -146,6 +157,13 @@ def linearmax(q, k, v, plan, p=1, mask=True):
                           for i in range(0, q.shape[0], step)], dim=0)
     dev = ops._device() if q.device.type != "cuda" else q.device
     home, in_dtype = q.device, q.dtype
+    if plan.prologue == "tensor_ops":
+        assert fp64_kernels(), "a float64 prologue in front of float32 kernels: the plan was made with fp64_kernels=True while fastmax.FP64_KERNELS is off"
+        # float64 end to end: the prologue as tensor ops autograd differentiates, the attention in the float64 kernels
+        qn, kn = _normalize_tensor_ops(q.to(dev)), _normalize_tensor_ops(k.to(dev))
+        if plan.operator == "unmasked":
+            return _UnmaskedNk.apply(qn, kn, v.to(dev), float(k.shape[2])).to(home)
+        return fastattention_einops.apply(qn, kn, v.to(dev), True, 1, True, p, 0.0, False).to(home)
     kdt = in_dtype if in_dtype in _KERNEL_DTYPES else torch.float32
     qd, kd, vd = (ops._prep(t.to(kdt), dev) for t in (q, k, v))
     if plan.operator == "fused_forward":
@@ -184,20 +202,26 @@ def fastmax_hack_grouped(q, k_groups, v, rep, p=1, plan=None):
     return fastattention_einops.apply(qn, kn, v, True, 1, True, p, 0.0, False).to(q.dtype)
 
 
+def _normalize_tensor_ops(x):
+    """the prologue (fastmax_hack.py:38-43 / 10-15) as differentiable tensor ops in x's dtype: the float64 route"""
+    x = x - x.mean(-1, keepdim=True)
+    return x / torch.linalg.norm(x, dim=3).max(dim=2).values[..., None, None]
+
+
 class _UnmaskedNk(torch.autograd.Function):
-    """Unmasked p=1 fastmax with nt=1 and the denominator constant g0 = N_k (fastmax_hack.py:17-31)."""
+    """Unmasked p=1 fastmax with nt=1 and the denominator constant g0 = N_k (fastmax_hack.py:17-31); float64 inputs (the
+    plan's "tensor_ops" prologue) stay float64, everything else computes in float32."""
 
     @staticmethod
     def forward(ctx, q, k, v, g0):
-        q, k, v = q.float(), k.float(), v.float()
-        o, g = ops.forward(ops._prep(q, q.device), ops._prep(k, q.device), ops._prep(v, q.device), 1, False, 1.0,
-                           g0, torch.float32)
+        cdt = torch.float64 if q.dtype == torch.float64 else torch.float32
+        q, k, v = (ops._prep(t.detach().to(cdt), q.device) for t in (q, k, v))
+        o, g = ops.forward(q, k, v, 1, False, 1.0, g0, cdt)
         ctx.save_for_backward(q, k, v, o, g)
         return o
 
     @staticmethod
     def backward(ctx, go):
         q, k, v, o, g = ctx.saved_tensors
-        dq, dk, dv = ops.backward(ops._prep(q, q.device), ops._prep(k, q.device), ops._prep(v, q.device), o, g,
-                                  ops._prep(go.float(), q.device), 1, False, 1.0)
+        dq, dk, dv = ops.backward(q, k, v, o, g, ops._prep(go.to(q.dtype), q.device), 1, False, 1.0)
         return dq, dk, dv, None

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libfastmax_hip.so")
 SOURCES = ["fastmax_api.hip", "fastmax_generic.hip", "fastmax_normalize.hip", "fastmax_rope.hip", "fastmax_ce.hip", "fastmax_mfma_v2.hip", "fastmax_mfma_gen.hip", "fastmax_mfma_bf16.hip", "fastmax_mfma_d128_2p.hip", "fastmax_scan_d128_2p.hip", "fastmax_mfma_split.hip", "fastmax_quad_mfma.hip",
-    "fastmax_quad32_mfma.hip", "fastmax_quad_mfma_bwd.hip", "fastmax_quad32_bwd.hip", "fastmax_mfma_bwd_lin.hip", "fastmax_decode.hip", "fastmax_decode_p2.hip", "fastmax_decode_qkv.hip", "linearmax_decode.hip", "fastmax_kv_decode.hip", "block_neighbours.hip", "neox_block.hip", "adapter_v2.hip", "flat_adamw.hip", "next_token.hip", "last_logits.hip", "decode_cursor.hip", "moe.hip", "moe_decode.hip", "nf4_lora.hip", "nf4_gemm.hip", "lora_thin.hip"]
+    "fastmax_quad32_mfma.hip", "fastmax_f64.hip", "fastmax_quad_mfma_bwd.hip", "fastmax_quad32_bwd.hip", "fastmax_mfma_bwd_lin.hip", "fastmax_decode.hip", "fastmax_decode_p2.hip", "fastmax_decode_qkv.hip", "linearmax_decode.hip", "fastmax_kv_decode.hip", "block_neighbours.hip", "neox_block.hip", "adapter_v2.hip", "flat_adamw.hip", "next_token.hip", "last_logits.hip", "decode_cursor.hip", "moe.hip", "moe_decode.hip", "nf4_lora.hip", "nf4_gemm.hip", "lora_thin.hip"]
 # csrc's own headers, then the public ones (relative to csrc, like the sources)
 HEADERS = (["fastmax_common.h", "fastmax_mfma_common.h", "fastmax_mfma32_common.h", "fastmax_decode_p2_step.h", "row_kernels.h", "fastmax_scan128.h", "next_token_sample.h", "nf4_gemv.h"] +
            [os.path.join("..", "..", "include", h) for h in _lib.HEADERS])

@@ -19,12 +19,22 @@ int validate(const fastmax_problem* p) {
         return FASTMAX_E_BAD_SHAPE;
     if (p->causal && p->Nq != p->Nk) return FASTMAX_E_BAD_SHAPE;
     if ((int64_t)p->B * p->H > 65535) return FASTMAX_E_BAD_SHAPE;       // (b,h) rides on gridDim.y in the tile kernels
-    if (p->in_dtype < 0 || p->in_dtype > 2 || p->out_dtype < 0 || p->out_dtype > 2) return FASTMAX_E_BAD_DTYPE;
+    if (p->in_dtype < 0 || p->in_dtype > FASTMAX_F64 || p->out_dtype < 0 || p->out_dtype > FASTMAX_F64) return FASTMAX_E_BAD_DTYPE;
+    // float64 in, float64 out: the double kernels neither widen nor narrow
+    if ((p->in_dtype == FASTMAX_F64) != (p->out_dtype == FASTMAX_F64)) return FASTMAX_E_BAD_DTYPE;
     return FASTMAX_OK;
+}
+bool is_f64(const fastmax_problem& p) { return p.in_dtype == FASTMAX_F64; }
+// the entry points that have no float64 kernels behind them: validate(), then float64 is a bad dtype
+int validate_no_f64(const fastmax_problem* p) {
+    const int rc = validate(p);
+    return rc ? rc : is_f64(*p) ? FASTMAX_E_BAD_DTYPE : FASTMAX_OK;
 }
 Strides3 st(const int64_t* s) { return Strides3{s[0], s[1], s[2]}; }
 
 int select(const fastmax_problem& p) {
+    // float64: one kernel family (fastmax_f64.hip); a forced family does not apply
+    if (is_f64(p)) return p.path == FASTMAX_PATH_AUTO ? FASTMAX_PATH_QUADRATIC_MFMA : FASTMAX_E_BAD_SHAPE;
     if (p.path == FASTMAX_PATH_QUADRATIC) return FASTMAX_PATH_QUADRATIC;
     if (p.path == FASTMAX_PATH_QUADRATIC_MFMA) return quad_mfma_supported(p) ? FASTMAX_PATH_QUADRATIC_MFMA : FASTMAX_E_BAD_SHAPE;
     const bool lin = (p.p == 1 && p.causal);
@@ -46,7 +56,7 @@ int select(const fastmax_problem& p) {
     return quad_mfma_supported(p) ? FASTMAX_PATH_QUADRATIC_MFMA : FASTMAX_PATH_QUADRATIC;
 }
 bool aligned16(const void* ptr, const int64_t* s, int dtype) {
-    const int64_t es = dtype == FASTMAX_F32 ? 4 : 2;
+    const int64_t es = dtype == FASTMAX_F64 ? 8 : dtype == FASTMAX_F32 ? 4 : 2;
     if (reinterpret_cast<uintptr_t>(ptr) & 15) return false;
     for (int i = 0; i < 3; ++i)
         if ((s[i] * es) & 15) return false;
@@ -104,6 +114,11 @@ FwdPlan fwd_plan(const fastmax_problem& p, unsigned lay) {
         f.rc = f.path;
         return f;
     }
+    if (is_f64(p)) {          // no misaligned fallback kernel: the caller copies
+        if (!has(lay, LAY_FWD)) f.rc = FASTMAX_E_ALIGNMENT;
+        f.kernel = FASTMAX_FWD_F64;
+        return f;
+    }
     if ((f.path == FASTMAX_PATH_MFMA || f.path == FASTMAX_PATH_QUADRATIC_MFMA) && !has(lay, LAY_FWD)) {
         if (p.path == f.path) {          // the caller forced this family
             f.rc = FASTMAX_E_ALIGNMENT;
@@ -129,7 +144,14 @@ FwdPlan fwd_plan(const fastmax_problem& p, unsigned lay) {
 }
 
 using BwdKernel = fastmax_bwd_kernel;
+// what the backward answers before it selects a kernel: float64 has one family and no misaligned fallback
+int bwd_check(const fastmax_problem& p, unsigned lay) {
+    if (!is_f64(p)) return FASTMAX_OK;
+    if (p.path != FASTMAX_PATH_AUTO) return FASTMAX_E_BAD_SHAPE;
+    return has(lay, LAY_BWD_ALL) ? FASTMAX_OK : FASTMAX_E_ALIGNMENT;
+}
 BwdKernel bwd_select(const fastmax_problem& p, unsigned lay) {
+    if (is_f64(p)) return FASTMAX_BWD_F64;
     // matrix-core tiles unless the caller forces the vector-ALU family or the layout rules it out
     if (p.path == FASTMAX_PATH_QUADRATIC || !quad_mfma_bwd_supported(p) || !has(lay, LAY_BWD_TILES)) return FASTMAX_BWD_QUADRATIC;
     // the linear-time kernels, unless the caller asks for the tile kernels; they also read o in 16-byte pieces
@@ -268,6 +290,7 @@ int fastmax_hip_forward(const fastmax_problem* prob, const void* q, const int64_
         case FASTMAX_FWD_RECURRENT: return launch_fwd_recurrent_p1(a);
         case FASTMAX_FWD_QUAD32: return launch_fwd_quad32(a);
         case FASTMAX_FWD_QUAD_MFMA: return launch_fwd_quad_mfma(a);
+        case FASTMAX_FWD_F64: return launch_fwd_f64(a);
         case FASTMAX_FWD_QUADRATIC: break;
     }
     return launch_fwd_quadratic(a);
@@ -275,6 +298,7 @@ int fastmax_hip_forward(const fastmax_problem* prob, const void* q, const int64_
 
 size_t fastmax_hip_backward_workspace(const fastmax_problem* prob) {
     if (validate(prob)) return 0;
+    if (is_f64(*prob)) return f64_bwd_workspace(*prob);
     const size_t a = bwd_quadratic_workspace(*prob), b = lin_bwd_workspace(*prob);
     size_t c = scan_bwd_supported(*prob) ? scan_bwd_workspace(*prob) : 0;
     const size_t d = unmasked_lin_bwd_workspace(*prob);
@@ -301,6 +325,8 @@ int fastmax_hip_backward_with_states(const fastmax_problem* prob, const void* q,
     BwdArgs a{*prob, q, k, v, o, grad_o, g, st(q_strides), st(k_strides), st(v_strides), st(go_strides), dq, dk, dv,
               workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)};
     const unsigned lay = layout(*prob, q, q_strides, k, k_strides, v, v_strides, o, grad_o, go_strides, dq, dk, dv);
+    rc = bwd_check(*prob, lay);
+    if (rc) return rc;
     // the caller's records are taken when they cover what this forward leaves (a rejected or unsplit forward leaves none)
     const FwdPlan fwd = fwd_plan(*prob, lay);
     if (fwd_states && fwd_state_bytes > 0 && fwd_state_bytes >= (fwd.rc ? 0 : fwd.state_bytes) && !(reinterpret_cast<uintptr_t>(fwd_states) & 15))
@@ -311,6 +337,7 @@ int fastmax_hip_backward_with_states(const fastmax_problem* prob, const void* q,
         case FASTMAX_BWD_SCAN: return launch_bwd_scan(a);
         case FASTMAX_BWD_QUAD32: return launch_bwd_quad32(a);
         case FASTMAX_BWD_QUAD_MFMA: return launch_bwd_quad_mfma(a);
+        case FASTMAX_BWD_F64: return launch_bwd_f64(a);          // ignores the caller's states: this forward leaves none
         case FASTMAX_BWD_QUADRATIC: break;
     }
     return launch_bwd_quadratic(a);
@@ -349,6 +376,7 @@ int fastmax_hip_plan(const fastmax_problem* prob, const void* q, const int64_t* 
         split = fwd.path == FASTMAX_PATH_MFMA && prob->causal;
     }
     if (with_bwd) {          // the backward does not ask whether the forward was accepted
+        if (!out->rc) out->rc = bwd_check(*prob, lay);
         out->bwd_kernel = bwd_select(*prob, lay);
         split = split || out->bwd_kernel == FASTMAX_BWD_LIN;
     }
@@ -450,7 +478,7 @@ int fastmax_hip_normalize_backward_expand(const void* x, const int64_t* x_stride
 static int linearmax_fwd_check(const fastmax_problem* prob, const void* q, const int64_t* q_strides, const void* k,
                                const int64_t* k_strides, const void* v, const int64_t* v_strides, const float* q_inv_norm,
                                const float* k_inv_norm, const void* o) {
-    const int rc = validate(prob);
+    const int rc = validate_no_f64(prob);
     if (rc) return rc;
     if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !q_inv_norm || !k_inv_norm) return FASTMAX_E_NULL;
     if (!mfma_gen_supported(*prob, true) && !mfma_d128_2p_supported(*prob)) return FASTMAX_E_BAD_SHAPE;
@@ -480,7 +508,7 @@ static size_t linearmax_stats_bytes(int B, int H, int N) {
 static size_t linearmax_fwd_bytes(const fastmax_problem& p) { return (fwd_plan(p, LAY_FWD).workspace + 255) & ~(size_t)255; }
 
 size_t fastmax_hip_linearmax_forward_auto_workspace(const fastmax_problem* prob) {
-    if (validate(prob)) return 0;
+    if (validate_no_f64(prob)) return 0;
     return linearmax_fwd_bytes(*prob) + linearmax_stats_bytes(prob->B, prob->H, prob->Nq);
 }
 
@@ -506,7 +534,7 @@ int fastmax_hip_linearmax_forward_auto(const fastmax_problem* prob, const void* 
 // applies the prologue's backward to its dK tile itself and dk is the gradient wrt the raw k (one k head per query head only).  fwd_states = the forward's workspace (its prefix
 // states), or null.  FASTMAX_E_BAD_SHAPE where the linear-time backward does not cover the problem (fastmax_hip_linearmax_train_supported).
 int fastmax_hip_linearmax_train_supported(const fastmax_problem* prob) {
-    if (validate(prob)) return 0;
+    if (validate_no_f64(prob)) return 0;
     if (!(prob->p == 1 && prob->causal) || prob->in_dtype != prob->out_dtype) return 0;
     return (mfma_gen_supported(*prob, true) && lin_bwd_supported(*prob)) ? 1 : 0;
 }
@@ -516,7 +544,7 @@ int fastmax_hip_linearmax_backward(const fastmax_problem* prob, const void* q, c
                                    const void* grad_o, const int64_t* go_strides, const float* q_inv_norm, const float* k_inv_norm,
                                    const int* q_nstar, const int* k_nstar, void* dq, void* dk, void* dv, void* workspace, size_t workspace_bytes,
                                    const void* fwd_states, size_t fwd_state_bytes, int flags, void* stream) {
-    int rc = validate(prob);
+    int rc = validate_no_f64(prob);
     if (rc) return rc;
     if (!q || !k || !v || !o || !g || !grad_o || !dq || !dk || !dv || !q_strides || !k_strides || !v_strides || !go_strides ||
         !q_inv_norm || !k_inv_norm)

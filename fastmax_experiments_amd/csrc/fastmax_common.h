@@ -186,6 +186,10 @@ bool scan_bwd_supported(const fastmax_problem& p);
 size_t scan_bwd_workspace(const fastmax_problem& p);
 bool lin_bwd_supported(const fastmax_problem& p);
 size_t bwd_quadratic_workspace(const fastmax_problem& p);
+// float64 problems (fastmax_f64.hip): every shape the entry points accept
+int launch_fwd_f64(const FwdArgs& a);
+int launch_bwd_f64(const BwdArgs& a);
+size_t f64_bwd_workspace(const fastmax_problem& p);
 int launch_normalize(const void* x, Strides3 xs, int dtype, float* y, float* inv_norm, int B, int H, int N, int D,
                      void* workspace, hipStream_t stream);
 }  // namespace fastmax

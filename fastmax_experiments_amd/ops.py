@@ -13,6 +13,9 @@ import torch
 from . import _lib
 
 _DT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+# float64 is the operator's alone (forward, backward, their plan and sizes): every other entry point keeps looking its dtype up
+# in _DT, where a float64 tensor is a KeyError on the host and never reaches the library
+_OP_DT = {**_DT, torch.float64: _lib.F64}
 _force_path = _lib.PATH_AUTO
 
 
@@ -34,7 +37,14 @@ def _prep(t, dev):
         t = t.to(dev, non_blocking=False)
     es = t.element_size()
     ok = t.stride(3) == 1 and all((s * es) % 16 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
+    if ok:
+        return t
+    if t.dtype == torch.float64 and t.shape[3] % 2:
+        # the float64 kernels have no misaligned fallback: rows of an odd head size are copied to an even row stride
+        B, H, N, D = t.shape
+        padded = torch.empty((B, H, N, D + 1), dtype=t.dtype, device=t.device)[..., :D]
+        return padded.copy_(t)
+    return t.contiguous()
 
 
 def _strides(t):
@@ -76,13 +86,17 @@ def _call(name, dev, args, ws=None, tail=()):
 
 def _problem(q, k, in_dt, out_dt, p, causal, nt, g0):
     B, H, Nq, D = q.shape
-    return _lib.Problem(B, H, Nq, k.shape[2], D, _DT[in_dt], _DT[out_dt], int(p), int(causal), 1.0 / nt,
+    if in_dt == torch.float64:
+        # 1/nt as two floats whose double sum the kernels take (struct fastmax_problem, include/fastmax_hip.h)
+        a = ctypes.c_float(1.0 / nt).value
+        return _lib.Problem(B, H, Nq, k.shape[2], D, _lib.F64, _OP_DT[out_dt], int(p), int(causal), a, 1.0 / nt - a, float(g0), _force_path)
+    return _lib.Problem(B, H, Nq, k.shape[2], D, _OP_DT[in_dt], _OP_DT[out_dt], int(p), int(causal), 1.0 / nt,
                         1.0 / (2.0 * nt * nt), float(g0), _force_path)
 
 
 def selected_path(q, k, p, causal, nt=1.0):
-    in_dt = q.dtype if q.dtype in _DT else torch.float32
-    out_dt = in_dt if causal else torch.float32          # dtype rule Q1
+    in_dt = q.dtype if q.dtype in _OP_DT else torch.float32
+    out_dt = in_dt if causal or in_dt == torch.float64 else torch.float32          # dtype rule Q1; float64 stays float64
     prob = _problem(q, k, in_dt, out_dt, p, causal, nt, 0.0)
     return _lib.lib().fastmax_hip_select_path(ctypes.byref(prob))
 
@@ -93,8 +107,8 @@ def planned_kernels(q, k, v, p, causal, o=None, grad_o=None, nt=1.0):
     ``BWD_KERNELS``; None: rejected, or no backward asked for).  Tensors are taken as forward() takes them; o and the
     gradients, which forward() and backward() allocate themselves, count as aligned unless ``o`` is given."""
     dev = q.device
-    in_dt = q.dtype if q.dtype in _DT else torch.float32
-    out_dt = o.dtype if o is not None else (in_dt if causal else torch.float32)          # dtype rule Q1
+    in_dt = q.dtype if q.dtype in _OP_DT else torch.float32
+    out_dt = o.dtype if o is not None else (in_dt if causal or in_dt == torch.float64 else torch.float32)          # dtype rule Q1
     q, k, v = (_prep(t, dev) for t in (q, k, v))
     prob = _problem(q, k, in_dt, out_dt, p, causal, nt, float(q.shape[2]))
     fresh = 256          # stands for a fresh allocation: only the alignment of an address is looked at
@@ -116,7 +130,8 @@ MAX_HEAD_SIZE = 256      # FASTMAX_MAX_D (include/fastmax_hip.h): the largest he
 
 
 def forward(q, k, v, p, causal, nt, g0, out_dtype, need_g=True, keep_states=False):
-    """q,k,v: device tensors (B,H,N,D) of one dtype in {f32,bf16,f16}. -> (o, g), or (o, g, states) with ``keep_states``:
+    """q,k,v: device tensors (B,H,N,D) of one dtype in {f32,bf16,f16,f64}; g is float32, float64 for float64 inputs (which
+    take out_dtype float64 only and need 16-byte aligned rows: `_prep`). -> (o, g), or (o, g, states) with ``keep_states``:
     the sequence-split prefix states the p=1 masked forward left in its workspace (None when this call has none), for
     ``backward(..., states=...)``"""
     L = _lib.lib()
@@ -128,7 +143,7 @@ def forward(q, k, v, p, causal, nt, g0, out_dtype, need_g=True, keep_states=Fals
         raise NotImplementedError(f"head size {D} > {MAX_HEAD_SIZE} is not supported by the HIP kernels")
     prob = _problem(q, k, q.dtype, out_dtype, p, causal, nt, g0)
     o = torch.empty((B, H, Nq, D), dtype=out_dtype, device=dev)
-    g = torch.empty((B, H, Nq), dtype=torch.float32, device=dev) if need_g else None
+    g = torch.empty((B, H, Nq), dtype=torch.float64 if q.dtype == torch.float64 else torch.float32, device=dev) if need_g else None
     wsb = _call("fastmax_hip_forward", dev, (ctypes.byref(prob), *_qkv(q, k, v), o.data_ptr(), _ptr(g)),
                 ws=L.fastmax_hip_forward_workspace(ctypes.byref(prob)))
     return (o, g, _kept_states(prob, q, k, v, o, wsb)) if keep_states else (o, g)

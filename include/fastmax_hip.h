@@ -31,7 +31,14 @@ extern "C" {
 
 #define FASTMAX_ABI_VERSION 9   /* 9: + fastmax_hip_plan (enum fastmax_fwd_kernel, enum fastmax_bwd_kernel, struct fastmax_plan); 8: the lmhead_ce_* and debug_gemm_stamps entry points are gone: the head's two products are plain library GEMMs by decision, see DESIGN.md, and the losing GEMM loop variants were removed; + fastmax_hip_tune_get, fastmax_hip_build_flags, fastmax_hip_normalize_stats2(_workspace), fastmax_hip_lora_{down,tn,up}_dropout, fastmax_hip_lora_dropout_mask, fastmax_hip_linearmax_forward_auto(_workspace), fastmax_hip_linearmax_backward, fastmax_hip_linearmax_train_supported; 7: + qlora_gemm_rope; 6: + qlora_gemm, nf4_dequantize_transposed, lmhead_ce_*; 5: + nf4 *_s entry points (double-quantised block scales); 4: + fastmax_hip_tune; 2: + normalize_cast/backward, rope_qkv_split(_backward), cross_entropy_forward/backward; 3: + lora_down/tn/up/scatter, normalize_*_expand, forward_state_bytes, backward_with_states */
 
-enum fastmax_dtype { FASTMAX_F32 = 0, FASTMAX_BF16 = 1, FASTMAX_F16 = 2 };
+enum fastmax_dtype { FASTMAX_F32 = 0, FASTMAX_BF16 = 1, FASTMAX_F16 = 2, FASTMAX_F64 = 3 };
+/* FASTMAX_F64: the operator's entry points only (forward, backward, backward_with_states, plan, select_path, the workspace and
+ * state queries), and only float64 in with float64 out: q, k, v, o, grad_o, dq, dk, dv and the (B,H,Nq) denominator g all hold
+ * doubles and every product, sum and division is a double (csrc/fastmax_f64.hip, v_mfma_f64_16x16x4_f64).  Any mix of float64
+ * with another dtype is FASTMAX_E_BAD_DTYPE.  All head sizes 1..FASTMAX_MAX_D; path must be FASTMAX_PATH_AUTO (a forced family
+ * answers FASTMAX_E_BAD_SHAPE); rows start 16-byte aligned or the call answers FASTMAX_E_ALIGNMENT -- there is no misaligned
+ * fallback kernel.  1/nt travels in the struct's two float coefficients as the double a + b (see struct fastmax_problem).
+ * The normalize*, linearmax, rope, decode and every other entry point that takes a dtype keep rejecting it. */
 
 enum fastmax_error {
     FASTMAX_OK = 0,
@@ -73,7 +80,10 @@ typedef struct fastmax_problem {
     int p;           /* 1 or 2: degree of the Taylor polynomial f                       */
     int causal;      /* 1 = `mask=True` of the reference (j <= i), needs Nq == Nk       */
     float a;         /* 1/nt          (nt: fastmax.py:78-82)                            */
-    float b;         /* 1/(2 nt^2)    (used when p == 2)                                */
+    float b;         /* 1/(2 nt^2)    (used when p == 2)
+                        FASTMAX_F64: a = 1/nt rounded to float, b = the float nearest to
+                        1/nt - a; the kernels take 1/nt = (double)a + (double)b (48 bits)
+                        and the second-order coefficient as half its square             */
     float g0;        /* constant term of the denominator when causal == 0:
                         Nq for fastmax.py:269-271, Nk for fastmax_hack.py:21            */
     int path;        /* enum fastmax_path; FASTMAX_PATH_AUTO lets the library choose    */
@@ -82,7 +92,8 @@ typedef struct fastmax_problem {
 /* ---- forward: replaces fastattention_einops.forward's F/g computation
  *      (attention_mechanisms/fastmax.py:84-97; compute_F_* 184-250, compute_g_* 252-322).
  *      o: (B,H,Nq,D) out_dtype.  g: (B,H,Nq) float32 denominator, saved for backward
- *      (fastmax.py:106); may be NULL when the caller does not need it.                   */
+ *      (fastmax.py:106); may be NULL when the caller does not need it.  For a FASTMAX_F64
+ *      problem the pointer declared `float* g` carries (B,H,Nq) DOUBLES.                 */
 size_t fastmax_hip_forward_workspace(const fastmax_problem* prob);
 int fastmax_hip_forward(const fastmax_problem* prob,
                         const void* q, const int64_t* q_strides,
@@ -95,7 +106,9 @@ int fastmax_hip_forward(const fastmax_problem* prob,
  *      gradient_o_{q,k,v}_{masked,unmasked} (383-691).  o, g: the forward's outputs.
  *      o: contiguous (B,H,Nq,D) in out_dtype.  grad_o: (B,H,Nq,D) in_dtype, strides as given.
  *      dq:(B,H,Nq,D) dk,dv:(B,H,Nk,D) contiguous, in_dtype (autograd hands each gradient
- *      back in the dtype of the input it belongs to).                                    */
+ *      back in the dtype of the input it belongs to).  For a FASTMAX_F64 problem the
+ *      pointer declared `const float* g` carries the forward's (B,H,Nq) DOUBLES, and the
+ *      workspace holds the (B,H,Nq) doubles sum_d grad_o o.                              */
 size_t fastmax_hip_backward_workspace(const fastmax_problem* prob);
 int fastmax_hip_backward(const fastmax_problem* prob,
                          const void* q, const int64_t* q_strides,
@@ -109,7 +122,8 @@ int fastmax_hip_backward(const fastmax_problem* prob,
  *      (sum k v^T, sum k) at the start of its workspace; the backward needs the same records.  A caller that keeps
  *      the forward's workspace alive hands it back here and the backward skips recomputing them:
  *      forward_state_bytes = how many leading bytes of the forward workspace hold them for this call (0: this
- *      problem / layout takes a kernel without a split -- pass NULL).                                            */
+ *      problem / layout takes a kernel without a split -- pass NULL).  FASTMAX_F64: 0, and fastmax_hip_backward_with_states
+ *      ignores fwd_states; its `const float* g` carries (B,H,Nq) doubles as in fastmax_hip_backward.              */
 size_t fastmax_hip_forward_state_bytes(const fastmax_problem* prob,
                                        const void* q, const int64_t* q_strides,
                                        const void* k, const int64_t* k_strides,
@@ -136,7 +150,9 @@ enum fastmax_fwd_kernel {
     FASTMAX_FWD_SCAN_BF16 = 5,     /* p=1 masked scan, bf16 D <= 128, all matrix-core (fastmax_mfma_bf16.hip)                 */
     FASTMAX_FWD_SCAN_GEN = 6,      /* p=1 masked scan, generic: padded head sizes, fp16, fp32 D < 64 (fastmax_mfma_gen.hip)   */
     FASTMAX_FWD_QUAD32 = 7,        /* matrix-core tiles, 32 x 32 x 16, N_q >= 256 (fastmax_quad32_mfma.hip)                   */
-    FASTMAX_FWD_QUAD_MFMA = 8      /* matrix-core tiles, 16 query rows per wave, D <= 256 (fastmax_quad_mfma.hip)             */
+    FASTMAX_FWD_QUAD_MFMA = 8,     /* matrix-core tiles, 16 query rows per wave, D <= 256 (fastmax_quad_mfma.hip)             */
+    FASTMAX_FWD_F64 = 9            /* float64 tiles on the f64 matrix instruction, every p, mask, D <= 256 (fastmax_f64.hip);
+                                      no vector-ALU double instantiation: D 1..256 all run on the matrix instruction         */
 };
 enum fastmax_bwd_kernel {
     FASTMAX_BWD_QUADRATIC = 0,     /* vector-ALU tiles: forced, not covered by the matrix cores, or a misaligned operand      */
@@ -144,10 +160,12 @@ enum fastmax_bwd_kernel {
     FASTMAX_BWD_LIN = 2,           /* p=1 masked forward / reverse scans with a carried state (fastmax_mfma_bwd_lin.hip)      */
     FASTMAX_BWD_SCAN = 3,          /* the same for fp32 / fp16 at 64 < D <= 128: one scan per gradient (fastmax_scan_d128_2p.hip) */
     FASTMAX_BWD_QUAD32 = 4,        /* matrix-core tiles, 32 x 32 x 16, N_q, N_k >= 256 (fastmax_quad32_bwd.hip)               */
-    FASTMAX_BWD_QUAD_MFMA = 5      /* matrix-core tiles, 16 rows per wave (fastmax_quad_mfma_bwd.hip)                         */
+    FASTMAX_BWD_QUAD_MFMA = 5,     /* matrix-core tiles, 16 rows per wave (fastmax_quad_mfma_bwd.hip)                         */
+    FASTMAX_BWD_F64 = 6            /* float64: row dots, dQ per query tile, dK / dV per key tile (fastmax_f64.hip)            */
 };
 typedef struct fastmax_plan {
-    int rc;              /* what the forward answers before it launches: 0, or the FASTMAX_E_* code it rejects the call with */
+    int rc;              /* what the forward answers before it launches: 0, or the FASTMAX_E_* code it rejects the call with;
+                            FASTMAX_F64 with a backward asked for: else what the backward answers (it has no fallback)       */
     int path;            /* enum fastmax_path of the forward after the layout rules; -1 when rc != 0                         */
     int fwd_kernel;      /* enum fastmax_fwd_kernel; -1 when rc != 0                                                         */
     int bwd_kernel;      /* enum fastmax_bwd_kernel; -1 for a forward-only query                                             */
