@@ -46,6 +46,11 @@ ACT_SILU, ACT_GELU = 0, 1                       # enum fastmax_gated_act (includ
 HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_decode.h", "fastmax_hip_block.h", "fastmax_hip_optim.h",
            "fastmax_hip_next_token.h", "fastmax_hip_neox.h", "fastmax_hip_cursor.h", "fastmax_hip_nucleus.h", "fastmax_hip_moe.h",
            "fastmax_hip_moe_decode.h", "fastmax_hip_head.h", "fastmax_hip_adapter.h", "fastmax_hip_kv_decode.h")
+# A second tuple, for now: tests/test_binding_cpu.py and tests/test_abi_cpu.py pin HEADERS, the rows of ABI and their checksum as
+# they stood when they were last cut, so a header added since then is listed here with its rows in ABI_EXT (bound by lib() on the
+# same handle, watched by build.HEADERS).  Both fold into HEADERS / ABI when those pinned tests are next re-cut.
+HEADERS_EXT = ("fastmax_hip_int8.h",)
+INT8_FEW_ROWS = 16                              # FASTMAX_INT8_FEW_ROWS
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
 CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
 NUCLEUS_MAX_V = 1 << 22                         # the largest V the fixed-point mass of top-p sampling admits
@@ -186,6 +191,15 @@ ABI = {
     "fastmax_hip_kv_decode_set_len": (ci, [vp, ci, ci, vp]),
 }
 SYMBOLS = list(ABI)
+# every function the HEADERS_EXT declare, as ABI does for HEADERS; tests/test_int8_cpu.py checks each row against the prototype
+ABI_EXT = {
+    # fastmax_hip_int8.h: the LLM.int8 linear (csrc/int8_linear.hip)
+    "fastmax_hip_int8_quantize_weight": (ci, [vp, i64, ci, vp, vp, ci, ci, vp]),
+    "fastmax_hip_int8_dequantize_weight": (ci, [vp, vp, vp, i64, ci, ci, ci, vp]),
+    "fastmax_hip_int8_quantize_rows": (ci, [vp, i64, ci, cf, vp, vp, vp, vp, vp, ci, ci, vp]),
+    "fastmax_hip_int8_linear_workspace": (sz, [ci, ci]),
+    "fastmax_hip_int8_linear": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, cf, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -199,7 +213,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.items():
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

@@ -21,7 +21,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
-from .lora import LoRALinear, NF4Linear
+from .lora import LoRALinear, NF4Linear, quantized_linear
 
 # Whether a new AdapterV2Linear runs the kernels: measured ahead of the tensor-op form at every training shape by far more than
 # the spread between runs (profiles/r22_adapter_v2.md).  One decode-size call in an eager loop costs the host more than the two
@@ -163,10 +163,9 @@ class AdapterV2Linear(nn.Module):
         nn.init.zeros_(self.adapter_bias)
         nn.init.ones_(self.adapter_scale)
 
-    def quantize_base(self, double_quant: bool = False) -> "AdapterV2Linear":
-        """swap the dense frozen layer for its NF4 version, as ``LoRALinear.quantize_base`` does"""
-        if not isinstance(self.linear, NF4Linear):
-            self.linear = NF4Linear.from_linear(self.linear, double_quant=double_quant)
+    def quantize_base(self, double_quant: bool = False, mode=None) -> "AdapterV2Linear":
+        """swap the dense frozen layer for its NF4 (or, with ``mode`` "bnb.int8", int8) version, as ``LoRALinear.quantize_base`` does"""
+        self.linear = quantized_linear(self.linear, double_quant, mode)
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

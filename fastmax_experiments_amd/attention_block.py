@@ -66,11 +66,11 @@ class CausalSelfAttention(nn.Module):
         self.proj = LoRALinear(self.head_size * n_head, n_embd, r=(r if to_projection else 0), lora_alpha=alpha,
                                lora_dropout=dropout, bias=bias)
 
-    def quantize_base(self, double_quant: bool = False):
+    def quantize_base(self, double_quant: bool = False, mode=None):
         """QLoRA: both frozen linears become 4-bit NF4 (what the bnb precision plugin does in the reference);
         ``double_quant`` = the "bnb.nf4-dq" mode (finetune/lora.py:38)."""
-        self.attn.quantize_base(double_quant)
-        self.proj.quantize_base(double_quant)
+        self.attn.quantize_base(double_quant, mode)
+        self.proj.quantize_base(double_quant, mode)
         return self
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, input_pos=None, state=None) -> torch.Tensor:

@@ -256,9 +256,9 @@ class LLaMAMLP(nn.Module):
         self.proj = LoRALinear(intermediate_size, n_embd, **kw)
         self.fused_neighbours = True
 
-    def quantize_base(self, double_quant: bool = False):
+    def quantize_base(self, double_quant: bool = False, mode=None):
         for lin in (self.fc_1, self.fc_2, self.proj):
-            lin.quantize_base(double_quant)
+            lin.quantize_base(double_quant, mode)
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -298,9 +298,9 @@ class DecoderBlock(nn.Module):
             if m is not None:
                 m.fused_neighbours = self._fused
 
-    def quantize_base(self, double_quant: bool = False):
-        self.attn.quantize_base(double_quant)
-        self.mlp.quantize_base(double_quant)
+    def quantize_base(self, double_quant: bool = False, mode=None):
+        self.attn.quantize_base(double_quant, mode)
+        self.mlp.quantize_base(double_quant, mode)
         return self
 
 

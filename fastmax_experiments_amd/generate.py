@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .adapter_v2 import AdapterV2Linear, adapter_forward
 from .block import BlockStack, RMSNorm, rms_norm_forward
-from .lora import NF4Linear, Params4bit, scales_cached, scales_of
+from .lora import NF4Linear, Params4bit, quant_mode, scales_cached, scales_of
 from .neox_block import LayerNorm, NeoXStack, layer_norm_forward
 
 _MASK64 = (1 << 64) - 1
@@ -249,9 +249,15 @@ class NextTokenHead(nn.Module):
         self.vocab_size = vocab_size
         self.fused = True                     # False: the tensor-op restatement (whole (B, T, V) head, topk + softmax + multinomial)
 
-    def quantize_base(self, double_quant: bool = False) -> "NextTokenHead":
+    def quantize_base(self, double_quant: bool = False, mode=None) -> "NextTokenHead":
         """``lm_head`` becomes an ``NF4Linear`` of the same weight (block 64; ``double_quant``: 8-bit block scales), the bias
-        stays; the state-dict keys are ``NF4Linear``'s.  Called again, nothing happens; the other scale form is refused."""
+        stays; the state-dict keys are ``NF4Linear``'s.  Called again, nothing happens; the other scale form is refused.
+        ``mode``: "bnb.nf4" / "bnb.nf4-dq" instead of ``double_quant``; "bnb.int8" is refused (no int8 last-row logits kernel)."""
+        mode = quant_mode(mode, double_quant)
+        if mode == "bnb.int8":
+            raise NotImplementedError("NextTokenHead.quantize_base: the last-row logits kernel reads NF4 codes or a dense weight; "
+                                      "an int8 lm_head is not built")
+        double_quant = mode == "bnb.nf4-dq"
         lin = self._linear()
         if isinstance(lin, NF4Linear):
             if lin.double_quant != bool(double_quant):

@@ -284,6 +284,123 @@ class NF4Linear(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------
+# LLM.int8 ("bnb.int8"): int8 weight codes with one fp32 scale per row, the product on the int8 matrix cores (csrc/int8_linear.hip)
+# ---------------------------------------------------------------------------------------------
+# bitsandbytes is not in the reference tree and not installed: the codec is the one include/fastmax_hip_int8.h spells out from
+# the public description (LLM.int8, arXiv 2208.07339); parity with bitsandbytes' own kernels is UNPINNED, as for NF4.
+QUANT_MODES = ("bnb.nf4", "bnb.nf4-dq", "bnb.int8")
+_WDT = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}
+
+
+def quant_mode(mode, double_quant: bool = False) -> str:
+    """the mode a ``quantize_base(double_quant, mode)`` call asks for; ``mode`` None: NF4 as ``double_quant`` says"""
+    if mode is None:
+        return "bnb.nf4-dq" if double_quant else "bnb.nf4"
+    if mode not in QUANT_MODES:
+        raise ValueError(f"quantize_base: unknown mode {mode!r}; the modes are {', '.join(QUANT_MODES)}")
+    return mode
+
+
+def quantized_linear(lin: nn.Module, double_quant: bool = False, mode=None, threshold: float = 6.0) -> nn.Module:
+    """the frozen layer ``lin`` in the asked-for mode: an ``NF4Linear`` or an ``Int8Linear``.  One that is quantised already stays;
+    a ``mode`` named explicitly that is not the layer's own is refused (the other codec would be kept silently)"""
+    asked, mode = mode, quant_mode(mode, double_quant)
+    if isinstance(lin, (NF4Linear, Int8Linear)):
+        own = "bnb.int8" if isinstance(lin, Int8Linear) else "bnb.nf4-dq" if lin.double_quant else "bnb.nf4"
+        if asked is not None and asked != own:
+            raise ValueError(f"quantize_base(mode={asked!r}): the layer is already quantised as {own}")
+        return lin
+    if mode == "bnb.int8":
+        return Int8Linear.from_linear(lin, threshold=threshold)
+    return NF4Linear.from_linear(lin, double_quant=mode == "bnb.nf4-dq")
+
+
+def int8_quantize(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(N, K) float weight -> (codes int8 (N, K), SCB float32 (N,)): HIP kernel for device tensors, tensor ops for host tensors"""
+    N, K = w.shape
+    w = w.detach()
+    if w.device.type == "cuda":
+        if w.dtype not in _WDT or w.stride(1) != 1 or (w.stride(0) * w.element_size()) % 16 or w.data_ptr() % 16:
+            w = w.to(w.dtype if w.dtype in _WDT else torch.float32).contiguous()
+        cb = torch.empty((N, K), dtype=torch.int8, device=w.device)
+        scb = torch.empty(N, dtype=torch.float32, device=w.device)
+        _call("fastmax_hip_int8_quantize_weight", w.device, (w.data_ptr(), w.stride(0), _WDT[w.dtype], cb.data_ptr(), scb.data_ptr(), N, K))
+        return cb, scb
+    wf = w.float()
+    scb = wf.abs().amax(dim=1)
+    inv = torch.where(scb > 0, 127.0 / scb, torch.zeros_like(scb))
+    return torch.round(wf * inv[:, None]).to(torch.int8), scb
+
+
+def int8_dequantize(cb: torch.Tensor, scb: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """codes * SCB / 127, rounded once to ``dtype``"""
+    if cb.device.type == "cuda" and dtype in _WDT:
+        N, K = cb.shape
+        w = torch.empty((N, K), dtype=dtype, device=cb.device)
+        _call("fastmax_hip_int8_dequantize_weight", cb.device, (cb.data_ptr(), scb.data_ptr(), w.data_ptr(), K, _WDT[dtype], N, K))
+        return w
+    return (cb.double() * scb.double()[:, None] / 127.0).to(dtype)
+
+
+class Int8Linear(nn.Module):
+    """``torch.nn.Linear``-compatible frozen layer with int8 weight codes, inference only ("bnb.int8").  State under
+    bitsandbytes' names: ``weight`` (int8 codes), ``SCB`` (fp32 row scales), ``bias`` (fp32, as NF4Linear keeps it)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, threshold: float = 6.0, device=None):
+        super().__init__()
+        if in_features % 64 or out_features % 16:
+            raise NotImplementedError(f"the int8 linear needs in_features % 64 == 0 and out_features % 16 == 0, got {in_features}, "
+                                      f"{out_features}")
+        self.in_features, self.out_features, self.threshold = in_features, out_features, float(threshold)
+        self.weight = nn.Parameter(torch.zeros((out_features, in_features), dtype=torch.int8, device=device), requires_grad=False)
+        self.register_buffer("SCB", torch.zeros(out_features, dtype=torch.float32, device=device))
+        self.bias = nn.Parameter(torch.zeros(out_features, dtype=torch.float32, device=device),
+                                 requires_grad=False) if bias else None
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear, threshold: float = 6.0) -> "Int8Linear":
+        q = cls(lin.in_features, lin.out_features, bias=lin.bias is not None, threshold=threshold, device=lin.weight.device)
+        q.load_dense(lin.weight.data, None if lin.bias is None else lin.bias.data)
+        return q
+
+    def load_dense(self, w: torch.Tensor, bias=None):
+        """(re)quantise from a dense weight, on the weight's own device and without an fp32 copy of a 16-bit weight"""
+        cb, scb = int8_quantize(w)
+        self.weight = nn.Parameter(cb, requires_grad=False)
+        self.SCB = scb
+        if bias is not None:
+            self.bias = nn.Parameter(bias.detach().float().clone(), requires_grad=False)
+
+    def _apply(self, fn, recurse=True):
+        # .to(device) moves the layer; .to(dtype) / .half() leave the codes int8 and the scales and the bias fp32 with their
+        # VALUES: where fn would cast a tensor, only its device part is applied (a cast there and back would round the scales)
+        def device_only(t):
+            out = fn(t)
+            return out if out.dtype == t.dtype else t.to(out.device)
+        return super()._apply(device_only, recurse)
+
+    def dequantize(self, dtype=torch.float32) -> torch.Tensor:
+        return int8_dequantize(self.weight.data, self.SCB, dtype)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"the int8 linear takes bf16 or fp16 activations, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError("the int8 linear runs on an MI355X only; there is no CPU fallback")
+        if x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("the int8 linear is inference only: fine-tuning through an int8 base (bnb.int8-training, the "
+                                      "backward-input product) is not built")
+        N, K = self.out_features, self.in_features
+        x2 = _rows(x, K)
+        M = x2.shape[0]
+        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+        _call("fastmax_hip_int8_linear", x.device,
+              (x2.data_ptr(), x2.stride(0), self.weight.data_ptr(), self.SCB.data_ptr(), _ptr(self.bias), y.data_ptr(), N, M, N, K,
+               _WDT[x.dtype], self.threshold), ws=_lib.lib().fastmax_hip_int8_linear_workspace(M, K))
+        return y.view(*x.shape[:-1], N)
+
+
+# ---------------------------------------------------------------------------------------------
 # the route plan: which kernels one call of a (Q)LoRA linear runs
 # ---------------------------------------------------------------------------------------------
 # From this many rows of x on, a 16-bit call decodes the frozen NF4 weight ONCE into dense bf16 (see _weight_operand) and runs the
@@ -739,11 +856,11 @@ class LoRALinear(LoRALayer):
             nn.init.kaiming_uniform_(self.lora_A, a=math.sqrt(5))
             nn.init.zeros_(self.lora_B)
 
-    def quantize_base(self, double_quant: bool = False) -> "LoRALinear":
+    def quantize_base(self, double_quant: bool = False, mode=None) -> "LoRALinear":
         """Swap the dense frozen layer for its NF4 version (what the bnb plugin does at construction); ``double_quant``:
-        the "bnb.nf4-dq" mode of finetune/lora.py:38 (block scales stored in 8 bits)."""
-        if not isinstance(self.linear, NF4Linear):
-            self.linear = NF4Linear.from_linear(self.linear, double_quant=double_quant)
+        the "bnb.nf4-dq" mode of finetune/lora.py:38 (block scales stored in 8 bits).  ``mode``: one of QUANT_MODES instead;
+        "bnb.int8" swaps in an ``Int8Linear`` (generation only: the branch stays on tensor ops around it)."""
+        self.linear = quantized_linear(self.linear, double_quant, mode)
         return self
 
     def get_lora_AB(self) -> torch.Tensor:
@@ -776,6 +893,8 @@ class LoRALinear(LoRALayer):
             if isinstance(self.linear, NF4Linear):
                 w = self.linear.dequantize(torch.float32) + lora_data.float().to(self.linear.weight.device)
                 self.linear.load_dense(w.to(self.linear.weight.quant_state[2]))      # keeps nf4 / nf4-dq as it was
+            elif isinstance(self.linear, Int8Linear):
+                self.linear.load_dense(self.linear.dequantize(torch.float32) + lora_data.float().to(self.linear.weight.device))
             elif self.linear.weight.data.dtype == lora_data.dtype:
                 self.linear.weight.data += lora_data
             else:
@@ -976,15 +1095,16 @@ def load_lora_checkpoint(model: nn.Module, file_path) -> None:
 
 def merged_state_dict(model: nn.Module, dtype=None) -> dict:
     """scripts/merge_lora.py:76-82: after merge_lora_weights, drop the LoRA parameters and the `linear.` level so the
-    result loads into the plain (non-LoRA) model; 4-bit bases are written dense."""
+    result loads into the plain (non-LoRA) model; 4-bit and int8 bases are written dense."""
     out = {}
     for name, module in model.named_modules():
-        if isinstance(module, NF4Linear):
-            w = module.dequantize(dtype or module.weight.quant_state[2])
+        if isinstance(module, (NF4Linear, Int8Linear)):
+            # an int8 layer does not remember the dtype it was quantised from: bf16 unless the caller names one
+            w = module.dequantize(dtype or (module.weight.quant_state[2] if isinstance(module, NF4Linear) else torch.bfloat16))
             out[(name + ".weight").replace("linear.", "")] = w.detach().cpu()
             if module.bias is not None:
                 out[(name + ".bias").replace("linear.", "")] = module.bias.detach().to(w.dtype).cpu()
-    quant_prefixes = tuple(n + "." for n, m in model.named_modules() if isinstance(m, NF4Linear))
+    quant_prefixes = tuple(n + "." for n, m in model.named_modules() if isinstance(m, (NF4Linear, Int8Linear)))
     for k, v in model.state_dict().items():
         if lora_filter(k, v) or k.startswith(quant_prefixes) or k.endswith("_extra_state"):
             continue

@@ -356,11 +356,11 @@ class LLaMAMoE(nn.Module):
             return False
         return not (torch.is_grad_enabled() and (x2.requires_grad or any(p.requires_grad for p in self.parameters())))
 
-    def quantize_base(self, double_quant: bool = False):
-        """NF4 for the experts' linears.  The gate stays dense: its n_expert output columns are fewer than the NF4 kernels take
+    def quantize_base(self, double_quant: bool = False, mode=None):
+        """NF4 (or ``mode``, one of lora.QUANT_MODES) for the experts' linears.  The gate stays dense: its n_expert output columns are fewer than the NF4 kernels take
         (bitsandbytes would quantize it with the rest)."""
         for expert in self.experts:
-            expert.quantize_base(double_quant)
+            expert.quantize_base(double_quant, mode)
         return self
 
     def _eager(self, x2: torch.Tensor) -> torch.Tensor:

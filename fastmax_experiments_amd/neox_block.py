@@ -243,9 +243,9 @@ class GptNeoxMLP(nn.Module):
         self.proj = LoRALinear(intermediate_size, n_embd, **kw)
         self.fused_neighbours = FUSED_NEIGHBOURS_DEFAULT
 
-    def quantize_base(self, double_quant: bool = False):
+    def quantize_base(self, double_quant: bool = False, mode=None):
         for lin in (self.fc, self.proj):
-            lin.quantize_base(double_quant)
+            lin.quantize_base(double_quant, mode)
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
