@@ -50,6 +50,9 @@ HEADERS = ("fastmax_hip.h", "fastmax_hip_generate.h", "fastmax_hip_linearmax_dec
 # they stood when they were last cut, so a header added since then is listed here with its rows in ABI_EXT (bound by lib() on the
 # same handle, watched by build.HEADERS).  Both fold into HEADERS / ABI when those pinned tests are next re-cut.
 HEADERS_EXT = ("fastmax_hip_int8.h",)
+# tests/test_int8_cpu.py in turn pins HEADERS_EXT and ABI_EXT to the int8 header alone, so the header after it gets the next pair,
+# bound and watched the same way and folded in at the same re-cut.
+HEADERS_EXT2 = ("fastmax_hip_softmax.h",)
 INT8_FEW_ROWS = 16                              # FASTMAX_INT8_FEW_ROWS
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
 CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
@@ -200,6 +203,14 @@ ABI_EXT = {
     "fastmax_hip_int8_linear_workspace": (sz, [ci, ci]),
     "fastmax_hip_int8_linear": (ci, [vp, i64, vp, vp, vp, vp, i64, ci, ci, ci, ci, cf, vp, sz, vp]),
 }
+# every function the HEADERS_EXT2 declare; tests/test_softmax_cpu.py checks each row against the prototype
+ABI_EXT2 = {
+    # fastmax_hip_softmax.h: softmax attention, the causal prefill (csrc/softmax_attention.hip) and the KV-cache decode
+    # (csrc/softmax_kv_decode.hip)
+    "fastmax_hip_softmax_forward": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
+    "fastmax_hip_softmax_kv_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
+    "fastmax_hip_softmax_kv_append_attend": (ci, QKV + [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -213,7 +224,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_EXT2.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

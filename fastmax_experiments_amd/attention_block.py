@@ -12,6 +12,10 @@ It is deliberately NOT a port of lit-gpt's GPT: no config registry, KV cache, ML
 attention sub-layer that hands tensors to the operator.  Everything outside the two LoRA linears and the
 attention operator is stock tensor plumbing.
 
+``attn_alg="quadratic"`` (the reference's default, model.py:440-441, 569-580) is causal softmax attention with scale
+1 / sqrt(head_size) on the matrix cores (ops.softmax_attention), forward only; unlike the two fastmax branches its heads ARE
+transposed back before the reshape.  It generates on a ``SoftmaxKVDecodeState``.
+
 Generation: ``forward(x, cos, sin, input_pos, state=FastmaxDecodeState(p=2, ...))`` runs the ``fastmax`` block on the
 second-order decode state cache (decode.py) in place of the reference's zero-padded KV cache (model.py:427-430): masked p=2
 fastmax over everything the state has seen plus the T new tokens, at a fixed cost per token.  ``linearmax`` blocks generate
@@ -40,7 +44,7 @@ _switches = importlib.import_module(linearmax.__module__)          # the module 
 class AttentionPlan(NamedTuple):
     qkv: str                                 # how q, k, v are produced: "gemm_epilogue", "hip_pass" or "eager"
     kv_layout: int                           # the K / V layout handed on: one of ops.KV_LAYOUTS
-    operator: Union[str, LinearmaxPlan]      # "fastmax" (p = 2), or the linearmax call's own plan
+    operator: Union[str, LinearmaxPlan]      # "fastmax" (p = 2), "softmax" (attn_alg="quadratic"), or the linearmax call's own plan
 
 
 class CausalSelfAttention(nn.Module):
@@ -55,7 +59,7 @@ class CausalSelfAttention(nn.Module):
         self.n_query_groups = n_query_groups or n_head
         self.head_size = head_size or n_embd // n_head
         self.rope_n_elem = int(rotary_percentage * self.head_size)
-        if attn_alg not in ("fastmax", "linearmax"):
+        if attn_alg not in ("fastmax", "linearmax", "quadratic"):
             raise ValueError(f"Attention algorithm {attn_alg} not supported")          # model.py:450-451
         self.attn_alg = attn_alg
         self.fused_neighbours = True          # False: tensor-op slicing instead of the one-pass HIP kernel (A/B, parity tests)
@@ -81,6 +85,9 @@ class CausalSelfAttention(nn.Module):
         B, T, C = x.size()
         if state is not None:
             y = self.attend_cached(x, cos, sin, state)
+        elif self.attn_alg == "quadratic" and input_pos is not None:
+            raise NotImplementedError("a quadratic (softmax) block decodes on a KV cache of its own: pass "
+                                      "state=SoftmaxKVDecodeState.for_attention(...) with input_pos (decode.py)")
         else:
             plan = self.plan(x, input_pos)
             G, hs, n = self.n_query_groups, self.head_size, self.rope_n_elem
@@ -98,6 +105,8 @@ class CausalSelfAttention(nn.Module):
                 q, k, v = ops.eager_rope_qkv_split(self.attn(x).view(B, T, G, q_per_kv + 2, hs), cos, sin, n)
                 k, v = (t.repeat_interleave(q_per_kv, dim=1) for t in (k, v))
             y = self._attend(q, k, v, plan.operator, input_pos is None, q_per_kv)
+        if self.attn_alg == "quadratic":
+            y = y.reshape(B, self.n_head, T, self.head_size).transpose(1, 2)          # model.py:580: this branch does transpose
         return self.proj(y.reshape(B, T, self.head_size * self.n_head))      # model.py:453-455 (no transpose: quirk Q3)
 
     def plan(self, x, input_pos=None) -> AttentionPlan:
@@ -110,7 +119,8 @@ class CausalSelfAttention(nn.Module):
           kv_layout  one of ops.KV_LAYOUTS.  Training a linearmax block with grouped-query heads keeps K at its n_query_groups
                      heads through RoPE and the prologue (statistics and gradient once per key head); group_views: neither K nor
                      V is ever copied per query head, else the prologue's store writes the copies
-          operator   "fastmax" (p = 2), or the linearmax_plan record of the call as it is launched"""
+          operator   "fastmax" (p = 2), "softmax" for attn_alg="quadratic" (forward only: ops.softmax_attention raises when a
+                     gradient is asked for), or the linearmax_plan record of the call as it is launched"""
         B, T = x.shape[:2]
         G, hs, n = self.n_query_groups, self.head_size, self.rope_n_elem
         q_per_kv = self.n_head // G
@@ -130,7 +140,7 @@ class CausalSelfAttention(nn.Module):
         else:
             qkv, layout = "eager", ops.KV_COPIES
         if self.attn_alg != "linearmax":
-            return AttentionPlan(qkv, layout, "fastmax")
+            return AttentionPlan(qkv, layout, "softmax" if self.attn_alg == "quadratic" else "fastmax")
         heads = (B * G, q_per_kv) if ops.KV_LAYOUTS[layout].v == "views" else (B, self.n_head)
         return AttentionPlan(qkv, layout, linearmax_plan(x.dtype, *heads, T, T, hs, 1, mask, needs_grad, q_per_kv if k_groups else 1,
                                                          k_groups and views))
@@ -138,6 +148,8 @@ class CausalSelfAttention(nn.Module):
     def _attend(self, q, k, v, operator, mask, q_per_kv):
         if operator == "fastmax":
             return fastmax(q, k, v, p=2, mask=mask)                # model.py:485, minus the .cpu()/.cuda() hops
+        if operator == "softmax":
+            return ops.softmax_attention(q, k, v)                  # model.py:576-579 (scale 1 / sqrt(head_size), causal)
         if operator.k_layout == "per_head":
             return linearmax(q, k, v, operator, p=1, mask=mask)      # model.py:472
         return fastmax_hack_grouped(q, k, v, q_per_kv, p=1, plan=operator)
@@ -148,7 +160,7 @@ class CausalSelfAttention(nn.Module):
         the new ones; the state advances by T.  One token onto a non-empty state is a single step straight from the QKV
         projection's output, anything else an ``extend`` (a prefill on an empty state).  A ``fastmax`` block also takes a
         ``FastmaxKVDecodeState`` (p=2; ``FastmaxKVDecodeState.for_attention``): the same function over a cache of K and V rows,
-        for head sizes up to 256."""
+        for head sizes up to 256.  A ``quadratic`` block takes a ``SoftmaxKVDecodeState`` (causal softmax over the same cache)."""
         check_block_cache(self.attn_alg, state)
         B, T, _ = x.size()
         if cos.shape[0] != T or sin.shape[0] != T:

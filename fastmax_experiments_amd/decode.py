@@ -36,6 +36,10 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
   KV cache  `FastmaxKVDecodeState` (csrc/fastmax_kv_decode.hip): the K and V rows themselves, the length a device word, and masked
        fastmax over the live prefix at every new position: O(N D) per token like the reference's cache, but the masked function,
        grouped-query heads on one K/V read, and head sizes up to 256, where the carried states stop at 128.  Opt-in like the rest.
+
+  softmax  `SoftmaxKVDecodeState` (csrc/softmax_kv_decode.hip): the same cache of K and V rows under causal softmax attention, the
+       function of `attn_alg="quadratic"` blocks (the reference's default, which every pretrained checkpoint was trained with);
+       the prompt's own rows come from the tile kernel of csrc/softmax_attention.hip.
 """
 import ctypes
 
@@ -306,40 +310,30 @@ class FastmaxDecodeState(_DecodeState):
         return self.prefill(q, k, v, chunk=self.prefill_chunk)     # None: the one-shot masked forward + state capture
 
 
-class FastmaxKVDecodeState(_DecodeState):
-    """KV-cache decode for fastmax blocks (csrc/fastmax_kv_decode.hip, include/fastmax_hip_kv_decode.h): the K and V rows of up to
-    ``max_len`` tokens in ``dtype`` (the activations'), and at each new position masked polynomial attention
-    o = sum_j f(s_j) v_j / sum_j f(s_j) over the cached rows and the new ones, in float32.  Head sizes 1 .. 256: the two config
-    shapes with 256-wide heads (pythia-1b, Gemma-2b) generate on this class only.  Per token it reads the live prefix of the
-    cache, 4 D bytes per bf16 position, where the second-order state moves (D+1)(D+2)/2 (D+1) floats whatever the length; the
-    measured crossover lengths are in profiles/r23_kv_decode.md.  Opt-in: nothing selects it automatically.
+class _KVCacheState(_DecodeState):
+    """What the two KV caches share (include/fastmax_hip_kv_decode.h): ``state`` as ONE tensor, a 64-byte header (int32 words:
+    the length, a sticky overflow flag) and the K and V rows of up to ``max_len`` tokens in ``dtype``; ``count`` as the host's
+    mirror of the header's length, lowered to truncate; ``load`` behind a subclass's masked forward over the prompt.  A subclass
+    gives ``_dtypes``, ``_masked`` (the prompt's own rows) and ``_append_attend``."""
 
-    q (B,H,T,D); k and v (B,n_query_groups,T,D) at their KV heads: one read of a K/V row serves the group's query heads.
-    ``state`` is ONE tensor: a 64-byte header (int32 words: the length, a sticky overflow flag) and both caches, so a
-    ``clone()`` / ``copy_()`` pair saves and restores everything.  The length the kernels use is the header's; ``count`` is the
-    host's mirror of it and nothing is ever read back.  A row's output bits depend on its q row and the cache prefix alone: not on
-    B, the batch row, T (a token fed alone or inside an ``extend``), ``max_len``, the inputs' strides or eager / replayed."""
-
-    def __init__(self, B, H, D, device, max_len, dtype, p=2, n_query_groups=None, normalize_term=8, tensors_normalized=False):
-        self._fastmax_of(D, p, normalize_term, tensors_normalized)
+    def _init_cache(self, B, H, D, device, max_len, dtype, n_query_groups, what, sizes):
         Hkv = _kv_heads(H, n_query_groups)
-        if dtype not in ops._DT:
-            raise ValueError(f"the KV decode cache holds float32, bfloat16 or float16, got {dtype}")
+        if dtype not in self._dtypes:
+            names = [str(d).replace("torch.", "") for d in self._dtypes]
+            raise ValueError(f"the {what} holds {', '.join(names[:-1])} or {names[-1]}, got {dtype}")
         if int(max_len) != max_len or max_len < 1 or max_len >= 2 ** 31:
             raise ValueError(f"max_len should be a number of tokens in 1 .. 2^31 - 1, got {max_len}")
         self.dtype, self.max_len = dtype, int(max_len)
-        nbytes = _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[dtype])
+        nbytes = _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[dtype]) if self._head_size_ok(D) else 0
         if nbytes and torch.device(device).type != "cuda":
-            raise RuntimeError("the KV decode cache lives on an MI355X (HIP device); there is no CPU path through the kernels")
-        super().__init__(B, H, Hkv, D, nbytes, device,
-                         f"KV decode cache: batch {B} x {Hkv} KV heads of size {D} not supported (head sizes 1 .. {_lib.KV_MAX_D}, "
-                         f"B * n_query_groups <= 65535)")
+            raise RuntimeError(f"the {what} lives on an MI355X (HIP device); there is no CPU path through the kernels")
+        _DecodeState.__init__(self, B, H, Hkv, D, nbytes, device,
+                              f"{what}: batch {B} x {Hkv} KV heads of size {D} not supported ({sizes}, B * n_query_groups <= 65535)")
         self.capacity = -(-self.max_len // _lib.KV_CHUNK) * _lib.KV_CHUNK       # positions allocated: max_len up to a whole chunk
 
-    @classmethod
-    def for_attention(cls, attn, B, max_len, device, dtype):
-        """the cache of a ``CausalSelfAttention`` (``attn_alg="fastmax"``: the block's p = 2 with its default scaling)"""
-        return cls(B, attn.n_head, attn.head_size, device, max_len, dtype, p=2, n_query_groups=attn.n_query_groups)
+    @staticmethod
+    def _head_size_ok(D):
+        return True
 
     @property
     def header(self):
@@ -375,7 +369,7 @@ class FastmaxKVDecodeState(_DecodeState):
         T = self._tokens(q, "prefill")
         qd, kd, vd = self._inputs(q, k, v, T)
         with torch.no_grad():
-            o = self._masked_fastmax(qd, kd, vd)
+            o = self._masked(qd, kd, vd)
         ops._call("fastmax_hip_kv_decode_load", self.state.device,
                   (*ops._qkv(kd, vd), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
         self._count = T
@@ -391,6 +385,34 @@ class FastmaxKVDecodeState(_DecodeState):
         new positions; bit for bit what T single steps give."""
         return self._append_attend(q, k, v, self._tokens(q, "extend"))
 
+
+class FastmaxKVDecodeState(_KVCacheState):
+    """KV-cache decode for fastmax blocks (csrc/fastmax_kv_decode.hip, include/fastmax_hip_kv_decode.h): the K and V rows of up to
+    ``max_len`` tokens in ``dtype`` (the activations'), and at each new position masked polynomial attention
+    o = sum_j f(s_j) v_j / sum_j f(s_j) over the cached rows and the new ones, in float32.  Head sizes 1 .. 256: the two config
+    shapes with 256-wide heads (pythia-1b, Gemma-2b) generate on this class only.  Per token it reads the live prefix of the
+    cache, 4 D bytes per bf16 position, where the second-order state moves (D+1)(D+2)/2 (D+1) floats whatever the length; the
+    measured crossover lengths are in profiles/r23_kv_decode.md.  Opt-in: nothing selects it automatically.
+
+    q (B,H,T,D); k and v (B,n_query_groups,T,D) at their KV heads: one read of a K/V row serves the group's query heads.
+    ``state`` is ONE tensor: a 64-byte header (int32 words: the length, a sticky overflow flag) and both caches, so a
+    ``clone()`` / ``copy_()`` pair saves and restores everything.  The length the kernels use is the header's; ``count`` is the
+    host's mirror of it and nothing is ever read back.  A row's output bits depend on its q row and the cache prefix alone: not on
+    B, the batch row, T (a token fed alone or inside an ``extend``), ``max_len``, the inputs' strides or eager / replayed."""
+
+    _dtypes = tuple(ops._DT)
+
+    def __init__(self, B, H, D, device, max_len, dtype, p=2, n_query_groups=None, normalize_term=8, tensors_normalized=False):
+        self._fastmax_of(D, p, normalize_term, tensors_normalized)
+        self._init_cache(B, H, D, device, max_len, dtype, n_query_groups, "KV decode cache", f"head sizes 1 .. {_lib.KV_MAX_D}")
+
+    _masked = _DecodeState._masked_fastmax
+
+    @classmethod
+    def for_attention(cls, attn, B, max_len, device, dtype):
+        """the cache of a ``CausalSelfAttention`` (``attn_alg="fastmax"``: the block's p = 2 with its default scaling)"""
+        return cls(B, attn.n_head, attn.head_size, device, max_len, dtype, p=2, n_query_groups=attn.n_query_groups)
+
     def _append_attend(self, q, k, v, T):
         qd, kd, vd = self._inputs(q, k, v, T)
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
@@ -402,6 +424,54 @@ class FastmaxKVDecodeState(_DecodeState):
                   ws=_lib.lib().fastmax_hip_kv_decode_workspace(B, H, Hkv, T, D, self.max_len))
         self._count += T
         return o
+
+
+class SoftmaxKVDecodeState(_KVCacheState):
+    """KV-cache decode for ``attn_alg="quadratic"`` blocks (csrc/softmax_kv_decode.hip, include/fastmax_hip_softmax.h): the cache
+    of `FastmaxKVDecodeState` -- the same header, rows, capacity, truncation and overflow flag -- under causal softmax attention
+    o = sum_j softmax_j(scale q . K_j) V_j over the cached rows and the new ones, ``scale`` = 1 / sqrt(D) by default.  bf16 and
+    fp16, head sizes that are multiples of 8 up to 256; forward only.  The prompt's own rows come from `ops.softmax_attention`.
+    A row's output bits depend on its q row and the cache prefix alone: not on B, the batch row, T, ``max_len``, the inputs'
+    strides or eager / replayed.  ``step`` / ``extend`` take ``lse=True`` for the rows' log-sum-exp (float32, (B,H,T))."""
+
+    _dtypes = (torch.bfloat16, torch.float16)
+    p = None          # not a fastmax cache: check_block_cache tells the classes apart
+
+    def __init__(self, B, H, D, device, max_len, dtype, n_query_groups=None, scale=None):
+        self.scale = 1.0 / D ** 0.5 if scale is None else float(scale)
+        self._init_cache(B, H, D, device, max_len, dtype, n_query_groups, "softmax KV decode cache",
+                         f"head sizes 8, 16, .. {_lib.KV_MAX_D}")
+
+    @staticmethod
+    def _head_size_ok(D):
+        return D % 8 == 0
+
+    @classmethod
+    def for_attention(cls, attn, B, max_len, device, dtype):
+        """the cache of a ``CausalSelfAttention`` (``attn_alg="quadratic"``: scale 1 / sqrt(head_size), model.py:576)"""
+        return cls(B, attn.n_head, attn.head_size, device, max_len, dtype, n_query_groups=attn.n_query_groups)
+
+    def _masked(self, q, k, v):
+        return ops.softmax_attention(q, k, v, scale=self.scale)
+
+    def step(self, q, k, v, lse=False):
+        return self._append_attend(q, k, v, 1, lse)
+
+    def extend(self, q, k, v, lse=False):
+        return self._append_attend(q, k, v, self._tokens(q, "extend"), lse)
+
+    def _append_attend(self, q, k, v, T, lse=False):
+        B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
+        dev = self.state.device
+        qd, kd, vd = (ops._prep(t, dev) for t in self._inputs(q, k, v, T))          # rows as whole 16-byte pieces
+        o = torch.empty((B, H, T, D), dtype=self.dtype, device=dev)
+        out_lse = torch.empty((B, H, T), dtype=torch.float32, device=dev) if lse else None
+        ops._call("fastmax_hip_softmax_kv_append_attend", dev,
+                  (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), ops._ptr(out_lse), B, H, Hkv, T, D, self.max_len,
+                   ops._DT[self.dtype], self.scale),
+                  ws=_lib.lib().fastmax_hip_softmax_kv_workspace(B, H, Hkv, T, D, self.max_len))
+        self._count += T
+        return (o, out_lse) if lse else o
 
 
 class LinearmaxDecodeState(_DecodeState):
@@ -464,7 +534,13 @@ class LinearmaxDecodeState(_DecodeState):
 
 def check_block_cache(attn_alg, state):
     """Which cache a ``CausalSelfAttention`` of ``attn_alg`` generates on: raises unless ``state`` is one."""
-    if attn_alg == "linearmax":
+    if attn_alg == "quadratic":
+        if not isinstance(state, SoftmaxKVDecodeState):
+            raise TypeError(f"a quadratic (softmax) block generates on a SoftmaxKVDecodeState, got {type(state).__name__}")
+    elif isinstance(state, SoftmaxKVDecodeState):
+        raise TypeError(f"a {attn_alg} block generates on a " + ("LinearmaxDecodeState" if attn_alg == "linearmax" else
+                        "FastmaxDecodeState(p=2) or a FastmaxKVDecodeState") + ", not on a SoftmaxKVDecodeState")
+    elif attn_alg == "linearmax":
         if isinstance(state, FastmaxDecodeState):
             raise NotImplementedError("a linearmax block generates on a LinearmaxDecodeState, not on a FastmaxDecodeState: its "
                                       "statistics run over the whole sequence, which the fastmax state caches do not carry")

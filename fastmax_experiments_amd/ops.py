@@ -426,3 +426,29 @@ def group_views(q, k, v, layout):
     def view(t):
         return t.view(B * G, 1, T, hs).expand(B * G, qpk, T, hs)
     return q.view(B * G, qpk, T, hs), (view(k) if layout.k == "views" else k), view(v)
+
+
+def softmax_attention(q, k, v, scale=None, lse=False):
+    """Causal softmax attention, forward only (csrc/softmax_attention.hip): o_i = sum_{j<=i} softmax_j(scale q_i.k_j) v_j with
+    ``scale`` = 1 / sqrt(D) by default.  q (B,H,N,D) bf16 or fp16; k, v (B,Hkv,N,D), Hkv dividing H, at their KV heads with any
+    strides (stride-0 group views included): nothing is copied per query head.  -> o (B,H,N,D) in q's dtype; with ``lse`` also
+    log sum_j exp(scale q_i.k_j), float32 (B,H,N).  D: a multiple of 8 up to 256."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise NotImplementedError("softmax_attention is forward only (generation): there is no backward pass; call it under "
+                                  "torch.no_grad() or on tensors that do not require gradients")
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:] or \
+            k.shape[1] < 1 or q.shape[1] % k.shape[1] != 0:
+        raise ValueError(f"expected q (B,H,N,D) and k, v (B,Hkv,N,D) with Hkv dividing H, got {tuple(q.shape)}, {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"softmax_attention takes bfloat16 or float16 q, k, v of one dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    B, H, N, D = q.shape
+    if D % 8 != 0 or D > MAX_HEAD_SIZE:
+        raise NotImplementedError(f"softmax_attention: head size {D} not supported (multiples of 8 up to {MAX_HEAD_SIZE})")
+    dev = q.device if q.is_cuda else _device()
+    qd, kd, vd = (_prep(t, dev) for t in (q, k, v))
+    o = torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
+    out_lse = torch.empty((B, H, N), dtype=torch.float32, device=dev) if lse else None
+    _call("fastmax_hip_softmax_forward", dev, (*_qkv(qd, kd, vd), o.data_ptr(), _ptr(out_lse), B, H, k.shape[1], N, D, _DT[q.dtype],
+                                               1.0 / math.sqrt(D) if scale is None else float(scale)))
+    return (o, out_lse) if lse else o
