@@ -210,6 +210,9 @@ ABI_EXT2 = {
     "fastmax_hip_softmax_forward": (ci, QKV + [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp]),
     "fastmax_hip_softmax_kv_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
     "fastmax_hip_softmax_kv_append_attend": (ci, QKV + [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+    # the prefill's backward (csrc/softmax_attention_bwd.hip): ..., o, lse, grad_o, go_strides, dq, dk, dv, B, H, Hkv, N, D, dtype, scale
+    "fastmax_hip_softmax_backward_workspace": (sz, [ci, ci, ci, ci]),
+    "fastmax_hip_softmax_backward": (ci, QKV + [vp, vp, vp, i64p, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
 }
 
 _lib = None

@@ -13,8 +13,9 @@ attention sub-layer that hands tensors to the operator.  Everything outside the 
 attention operator is stock tensor plumbing.
 
 ``attn_alg="quadratic"`` (the reference's default, model.py:440-441, 569-580) is causal softmax attention with scale
-1 / sqrt(head_size) on the matrix cores (ops.softmax_attention), forward only; unlike the two fastmax branches its heads ARE
-transposed back before the reshape.  It generates on a ``SoftmaxKVDecodeState``.
+1 / sqrt(head_size) on the matrix cores (ops.softmax_attention_with_grad: forward and backward in HIP, head sizes up to 128 when
+training); unlike the two fastmax branches its heads ARE transposed back before the reshape.  It generates on a
+``SoftmaxKVDecodeState``.
 
 Generation: ``forward(x, cos, sin, input_pos, state=FastmaxDecodeState(p=2, ...))`` runs the ``fastmax`` block on the
 second-order decode state cache (decode.py) in place of the reference's zero-padded KV cache (model.py:427-430): masked p=2
@@ -118,9 +119,11 @@ class CausalSelfAttention(nn.Module):
                      not take (decode with input_pos, rotary widths that are not whole 16-byte pieces)
           kv_layout  one of ops.KV_LAYOUTS.  Training a linearmax block with grouped-query heads keeps K at its n_query_groups
                      heads through RoPE and the prologue (statistics and gradient once per key head); group_views: neither K nor
-                     V is ever copied per query head, else the prologue's store writes the copies
-          operator   "fastmax" (p = 2), "softmax" for attn_alg="quadratic" (forward only: ops.softmax_attention raises when a
-                     gradient is asked for), or the linearmax_plan record of the call as it is launched"""
+                     V is ever copied per query head, else the prologue's store writes the copies.  Training a quadratic block
+                     with grouped-query heads takes the HIP pass with KV_GROUPS: the softmax kernels index K and V at their KV
+                     heads themselves, and the backward writes their gradients once per KV head, summed over the group in float32
+          operator   "fastmax" (p = 2), "softmax" for attn_alg="quadratic" (ops.softmax_attention_with_grad: forward and backward
+                     in HIP), or the linearmax_plan record of the call as it is launched"""
         B, T = x.shape[:2]
         G, hs, n = self.n_query_groups, self.head_size, self.rope_n_elem
         q_per_kv = self.n_head // G
@@ -130,7 +133,9 @@ class CausalSelfAttention(nn.Module):
         views = hip_pass and q_per_kv > 1 and self.group_views
         k_groups = (hip_pass and self.attn_alg == "linearmax" and q_per_kv > 1 and needs_grad and _switches.GROUPED_K
                     and B * self.n_head <= MAX_HEADS_PER_LAUNCH)
-        if (hip_pass and self.gemm_rope and x.dtype == torch.bfloat16 and isinstance(self.attn, LoRAQKVLinear)
+        if hip_pass and self.attn_alg == "quadratic" and needs_grad and q_per_kv > 1:
+            qkv, layout = "hip_pass", ops.KV_GROUPS
+        elif (hip_pass and self.gemm_rope and x.dtype == torch.bfloat16 and isinstance(self.attn, LoRAQKVLinear)
                 and (views or q_per_kv == 1) and self.attn.plan(x, (T, G, q_per_kv, hs, n)).rope):
             qkv, layout = "gemm_epilogue", (ops.KV_GROUPS if q_per_kv == 1 else ops.K_GROUPS_V_VIEWS if k_groups else ops.KV_VIEWS)
         elif hip_pass:
@@ -149,7 +154,7 @@ class CausalSelfAttention(nn.Module):
         if operator == "fastmax":
             return fastmax(q, k, v, p=2, mask=mask)                # model.py:485, minus the .cpu()/.cuda() hops
         if operator == "softmax":
-            return ops.softmax_attention(q, k, v)                  # model.py:576-579 (scale 1 / sqrt(head_size), causal)
+            return ops.softmax_attention_with_grad(q, k, v)        # model.py:576-579 (scale 1 / sqrt(head_size), causal)
         if operator.k_layout == "per_head":
             return linearmax(q, k, v, operator, p=1, mask=mask)      # model.py:472
         return fastmax_hack_grouped(q, k, v, q_per_kv, p=1, plan=operator)

@@ -435,7 +435,8 @@ def softmax_attention(q, k, v, scale=None, lse=False):
     log sum_j exp(scale q_i.k_j), float32 (B,H,N).  D: a multiple of 8 up to 256."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         raise NotImplementedError("softmax_attention is forward only (generation): there is no backward pass; call it under "
-                                  "torch.no_grad() or on tensors that do not require gradients")
+                                  "torch.no_grad() or on tensors that do not require gradients, or train through "
+                                  "softmax_attention_with_grad")
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:] or \
             k.shape[1] < 1 or q.shape[1] % k.shape[1] != 0:
         raise ValueError(f"expected q (B,H,N,D) and k, v (B,Hkv,N,D) with Hkv dividing H, got {tuple(q.shape)}, {tuple(k.shape)}, "
@@ -452,3 +453,46 @@ def softmax_attention(q, k, v, scale=None, lse=False):
     _call("fastmax_hip_softmax_forward", dev, (*_qkv(qd, kd, vd), o.data_ptr(), _ptr(out_lse), B, H, k.shape[1], N, D, _DT[q.dtype],
                                                1.0 / math.sqrt(D) if scale is None else float(scale)))
     return (o, out_lse) if lse else o
+
+
+SOFTMAX_BWD_MAX_HEAD_SIZE = 128      # the backward's tile kernels hold 32 rows (keys) per wave: larger heads need another work split
+
+
+class SoftmaxAttention(torch.autograd.Function):
+    """`softmax_attention` with its backward (csrc/softmax_attention_bwd.hip): the forward keeps lse, the backward is one call of
+    fastmax_hip_softmax_backward on q, k, v, o, lse and grad_o through its own strides."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        o, lse = softmax_attention(q, k, v, scale=scale, lse=True)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, grad_o):
+        q, k, v, o, lse = ctx.saved_tensors
+        dev = o.device
+        qd, kd, vd, god = (_prep(t, dev) for t in (q, k, v, grad_o))          # a transposed grad_o is taken as it is
+        (B, H, N, D), Hkv = q.shape, k.shape[1]
+        dq = torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
+        dk, dv = (torch.empty((B, Hkv, N, D), dtype=q.dtype, device=dev) for _ in range(2))
+        _call("fastmax_hip_softmax_backward", dev,
+              (*_qkv(qd, kd, vd), o.data_ptr(), lse.data_ptr(), *_qkv(god), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, H, Hkv, N, D,
+               _DT[q.dtype], ctx.scale), ws=_lib.lib().fastmax_hip_softmax_backward_workspace(B, H, N, D))
+        return dq, dk, dv, None
+
+
+def softmax_attention_with_grad(q, k, v, scale=None):
+    """`softmax_attention` that can be trained through: the same arguments, checks and output bits, and gradients of q, k, v from
+    two tile kernels with float32 sums in one order (no atomics: two calls give the same bits).  Head sizes up to 128 where a
+    gradient is needed.  k, v (B,Hkv,N,D) at their KV heads get gradients (B,Hkv,N,D), summed over each group's query heads in
+    float32 and rounded once.  Stride-0 per-head views (Hkv = H) stay correct -- autograd sums the per-head gradients -- but
+    are the slower form: r times the K/V gradient traffic and a sum of r rounded gradients."""
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))):
+        return softmax_attention(q, k, v, scale=scale)
+    if q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[3] % 8 == 0 and \
+            SOFTMAX_BWD_MAX_HEAD_SIZE < q.shape[3] <= MAX_HEAD_SIZE:
+        raise NotImplementedError(f"softmax_attention_with_grad: head size {q.shape[3]} has no backward pass (multiples of 8 up to "
+                                  f"{SOFTMAX_BWD_MAX_HEAD_SIZE}); the forward alone takes up to {MAX_HEAD_SIZE}")
+    return SoftmaxAttention.apply(q, k, v, 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale))

@@ -1,5 +1,6 @@
 /* fastmax_hip_softmax.h -- softmax ("quadratic") attention in libfastmax_hip.so (MI355X / gfx950 only): the causal prefill on the
- * matrix cores (csrc/softmax_attention.hip) and the KV-cache decode (csrc/softmax_kv_decode.hip).  Forward only, bf16 and fp16.
+ * matrix cores (csrc/softmax_attention.hip), its backward (csrc/softmax_attention_bwd.hip) and the KV-cache decode
+ * (csrc/softmax_kv_decode.hip).  bf16 and fp16.
  * The dtype and error enums are those of fastmax_hip.h; the entry points belong to the same library and FASTMAX_ABI_VERSION
  * (additions only) and are bound by their rows of ABI_EXT in fastmax_experiments_amd/_lib.py.  Everything runs on `stream`;
  * nothing is allocated, nothing is read back, there are no atomics, and every sum has a fixed order: two calls give the same bits.
@@ -31,11 +32,27 @@
  *   kv_workspace  bytes of workspace kv_append_attend needs: B * H * min(T, FASTMAX_KV_SLICE) * ((cap / FASTMAX_KV_CHUNK) *
  *                 (D + 2) + 2) * 4; 0 for a shape it rejects.
  *
+ *   backward      from the forward's q, k, v, o and lse (required here) and grad_o (B, H, N, D) through its own three strides (a
+ *                 transposed view is not copied), with c = scale log2 e, L_i = lse[b, h, i], r = H / Hkv, for j <= i:
+ *                     P_ij  = exp2(c s_ij - L_i log2 e)        s_ij = q_i . k_j, float32 on the matrix cores, never stored
+ *                     D_i   = sum_c grad_o_ic o_ic             float32, from the forward's own (rounded) o
+ *                     dS_ij = P_ij (grad_o_i . v_j - D_i)
+ *                     dq_i  = scale sum_{j <= i} dS_ij k_j
+ *                     dk_j  = scale sum_{h in group} sum_{i >= j} dS_ij q_i        dv_j = sum_{h in group} sum_{i >= j} P_ij grad_o_i
+ *                 dq (B, H, N, D); dk, dv (B, Hkv, N, D): contiguous, in `dtype`.  Any N >= 1; D a multiple of 8 in 8 .. 128.  Two
+ *                 tile kernels, each recomputing S and grad_o V^T: dq per (b, h, 128 query rows) over the key tiles in ascending
+ *                 order, which also leaves D_i in the workspace; then dk and dv per (b, KV head, 128 keys) over the group's query
+ *                 heads in ascending order and, within a head, the query tiles in ascending order.  P and dS are rounded to
+ *                 `dtype` once, as matrix operands; all three sums are float32 in that one order and are rounded once, after
+ *                 the sum over the group's heads: no atomics, two calls give the same bits.
+ *   backward_workspace   bytes of workspace backward needs: B * H * N * 4; 0 for a shape it rejects.
+ *
  * Every rejection happens before anything is launched, in this order: FASTMAX_E_NULL (a missing pointer, strides included; lse
- * may be NULL), FASTMAX_E_BAD_DTYPE (anything but FASTMAX_BF16 / FASTMAX_F16), FASTMAX_E_BAD_SHAPE (a head size that is not a
- * multiple of 8 in 8 .. 256, a count <= 0, H % Hkv != 0, B * H or B * Hkv above 65535, a shape whose state_bytes is 0, a scale
- * that is not finite), FASTMAX_E_ALIGNMENT (q, k, v, o or the state not 16-byte aligned, a stride that is not a whole number of
- * 16-byte pieces, lse not 4-byte aligned), FASTMAX_E_WORKSPACE (smaller than kv_workspace's answer). */
+ * may be NULL except for backward, whose workspace is required too), FASTMAX_E_BAD_DTYPE (anything but FASTMAX_BF16 / FASTMAX_F16), FASTMAX_E_BAD_SHAPE (a head size that is not a
+ * multiple of 8 in 8 .. 256 -- backward: 8 .. 128 --, a count <= 0, H % Hkv != 0, B * H or B * Hkv above 65535, a shape whose state_bytes is 0, a scale
+ * that is not finite), FASTMAX_E_ALIGNMENT (q, k, v, o, grad_o, dq, dk, dv or the state not 16-byte aligned, a stride that is not a whole number of
+ * 16-byte pieces, lse not 4-byte aligned), FASTMAX_E_WORKSPACE (smaller than kv_workspace's or
+ * backward_workspace's answer). */
 #ifndef FASTMAX_HIP_SOFTMAX_H
 #define FASTMAX_HIP_SOFTMAX_H
 
@@ -54,6 +71,11 @@ int fastmax_hip_softmax_kv_append_attend(const void* q, const int64_t* q_strides
                                          const void* v, const int64_t* v_strides, void* state, void* o, float* lse, int B, int H,
                                          int Hkv, int T, int D, int max_len, int dtype, float scale, void* workspace,
                                          size_t workspace_bytes, void* stream);
+size_t fastmax_hip_softmax_backward_workspace(int B, int H, int N, int D);
+int fastmax_hip_softmax_backward(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                                 const int64_t* v_strides, const void* o, const float* lse, const void* grad_o,
+                                 const int64_t* go_strides, void* dq, void* dk, void* dv, int B, int H, int Hkv, int N, int D, int dtype,
+                                 float scale, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

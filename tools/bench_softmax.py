@@ -2,6 +2,9 @@
 torch.nn.functional.scaled_dot_product_attention (K / V expanded per query head) and fastmax(p=2); one SoftmaxKVDecodeState.step,
 replayed from a captured graph, against FastmaxKVDecodeState.step, with the achieved bytes per second on the cache.
 
+``--backward`` instead times forward + backward of ops.softmax_attention_with_grad (profiles/r29_softmax_backward.md) on the two
+prefill shapes against the same two, forward + backward.
+
 Every timed call rotates over enough operand sets to pass the last-level cache (256 MiB) between two uses of one set; the figure
 is the median of ``--reps`` timings of ``--inner`` calls after ``--warmup`` untimed ones.  Prints one JSON line per case."""
 import argparse
@@ -51,6 +54,26 @@ def prefill(B, H, Hkv, N, D, a):
                           sdpa_ms=t_sdpa, fastmax_p2_ms=t_p2, operand_sets=nsets)), flush=True)
 
 
+def train(B, H, Hkv, N, D, a):
+    """forward + backward: the HIP route on K/V at their KV heads; SDPA and fastmax(p=2) on K/V expanded inside the graph"""
+    dt, r = torch.bfloat16, H // Hkv
+    nsets = max(2, math.ceil(LLC / (2 * (3 * B * H + 2 * B * Hkv) * N * D)) + 1)
+    sets = [tuple(torch.randn(B, h, N, D, device="cuda").to(dt).requires_grad_(True) for h in (H, Hkv, Hkv)) for _ in range(nsets)]
+    dO = [torch.randn(B, N, H, D, device="cuda").to(dt).transpose(1, 2) for _ in range(nsets)]          # as the block hands it back
+
+    def step(i, fn, widen):
+        q, k, v = sets[i]
+        kv = (k.repeat_interleave(r, 1), v.repeat_interleave(r, 1)) if widen else (k, v)
+        torch.autograd.grad(fn(q, *kv), (q, k, v), dO[i])
+
+    flops = (4 + 10) * B * H * N * N * D / 2          # 2 products forward, 5 backward (the tile kernels do 7)
+    t_soft = timed(lambda i: step(i, ops.softmax_attention_with_grad, False), nsets, a)
+    t_sdpa = timed(lambda i: step(i, lambda q, k, v: torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True), True), nsets, a)
+    t_p2 = timed(lambda i: step(i, lambda q, k, v: fastmax(q, k, v, p=2, mask=True), True), nsets, a)
+    print(json.dumps(dict(case="forward+backward", shape=[B, H, N, D], kv_heads=Hkv, softmax_ms=t_soft,
+                          softmax_tflops=flops / t_soft / 1e9, sdpa_ms=t_sdpa, fastmax_p2_ms=t_p2, operand_sets=nsets)), flush=True)
+
+
 def decode(name, B, H, Hkv, D, cached, a):
     dt = torch.bfloat16
     cache_bytes = 2 * B * Hkv * cached * D * 2
@@ -85,7 +108,12 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=20)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward on the two prefill shapes, nothing else")
     a = ap.parse_args()
+    if a.backward:
+        train(8, 32, 4, 2048, 64, a)
+        train(1, 32, 32, 4096, 128, a)
+        sys.exit(0)
     prefill(8, 32, 4, 2048, 64, a)
     prefill(1, 32, 32, 4096, 128, a)
     for name, H, Hkv, D in (("tiny-llama-1.1b", 32, 4, 64), ("Llama-2-7b-hf", 32, 32, 128)):
