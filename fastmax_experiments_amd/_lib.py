@@ -53,6 +53,9 @@ HEADERS_EXT = ("fastmax_hip_int8.h",)
 # tests/test_int8_cpu.py in turn pins HEADERS_EXT and ABI_EXT to the int8 header alone, so the header after it gets the next pair,
 # bound and watched the same way and folded in at the same re-cut.
 HEADERS_EXT2 = ("fastmax_hip_softmax.h",)
+# tests/test_softmax_cpu.py pins HEADERS_EXT2 and ABI_EXT2 to the softmax header alone: the next pair, on the same terms
+HEADERS_EXT3 = ("fastmax_hip_prefix.h",)
+PREFIX_MAX_ROWS, PREFIX_BWD_CHUNK = 32, 512     # FASTMAX_PREFIX_MAX_ROWS, FASTMAX_PREFIX_BWD_CHUNK
 INT8_FEW_ROWS = 16                              # FASTMAX_INT8_FEW_ROWS
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
 CURSOR_POS, CURSOR_NEXT, CURSOR_DRAW_BASE, CURSOR_SEED, CURSOR_OVERFLOW = range(5)          # enum fastmax_cursor_word
@@ -214,6 +217,15 @@ ABI_EXT2 = {
     "fastmax_hip_softmax_backward_workspace": (sz, [ci, ci, ci, ci]),
     "fastmax_hip_softmax_backward": (ci, QKV + [vp, vp, vp, i64p, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
 }
+# every function the HEADERS_EXT3 declare; tests/test_prefix_cpu.py checks each row against the prototype
+ABI_EXT3 = {
+    # fastmax_hip_prefix.h: LLaMA-Adapter's gated prefix attention (csrc/prefix_attention.hip)
+    # q, q_strides, y, y_strides, ak, av, gate, out, B, H, Hkv, N, D, aT, dtype, scale
+    "fastmax_hip_prefix_forward": (ci, [vp, i64p, vp, i64p, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp]),
+    "fastmax_hip_prefix_backward_workspace": (sz, [ci, ci, ci, ci]),
+    # q, q_strides, grad_o, go_strides, ak, av, gate, dq, dak, dav, dgate, B, H, Hkv, N, D, aT, dtype, scale
+    "fastmax_hip_prefix_backward": (ci, [vp, i64p, vp, i64p, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -227,7 +239,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_EXT2.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_EXT2.items()) + list(ABI_EXT3.items()):
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

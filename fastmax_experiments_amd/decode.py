@@ -432,10 +432,14 @@ class SoftmaxKVDecodeState(_KVCacheState):
     o = sum_j softmax_j(scale q . K_j) V_j over the cached rows and the new ones, ``scale`` = 1 / sqrt(D) by default.  bf16 and
     fp16, head sizes that are multiples of 8 up to 256; forward only.  The prompt's own rows come from `ops.softmax_attention`.
     A row's output bits depend on its q row and the cache prefix alone: not on B, the batch row, T, ``max_len``, the inputs'
-    strides or eager / replayed.  ``step`` / ``extend`` take ``lse=True`` for the rows' log-sum-exp (float32, (B,H,T))."""
+    strides or eager / replayed.  ``step`` / ``extend`` take ``lse=True`` for the rows' log-sum-exp (float32, (B,H,T)).
+    ``prefix = (ak, av, gate)`` (LLaMA-Adapter, adapter.py; set by an adapted layer's ``attend_cached``): the rows that ``step`` /
+    ``extend`` / ``prefill`` return get ``ops.prefix_attention_add``'s term from the q they were computed with, one more launch
+    in place; lse stays the causal softmax's own."""
 
     _dtypes = (torch.bfloat16, torch.float16)
     p = None          # not a fastmax cache: check_block_cache tells the classes apart
+    prefix = None
 
     def __init__(self, B, H, D, device, max_len, dtype, n_query_groups=None, scale=None):
         self.scale = 1.0 / D ** 0.5 if scale is None else float(scale)
@@ -451,8 +455,13 @@ class SoftmaxKVDecodeState(_KVCacheState):
         """the cache of a ``CausalSelfAttention`` (``attn_alg="quadratic"``: scale 1 / sqrt(head_size), model.py:576)"""
         return cls(B, attn.n_head, attn.head_size, device, max_len, dtype, n_query_groups=attn.n_query_groups)
 
+    def _add_prefix(self, o, q):
+        if self.prefix is None:
+            return o
+        return ops.prefix_attention_forward(o, q, *self.prefix, scale=self.scale, inplace=True)
+
     def _masked(self, q, k, v):
-        return ops.softmax_attention(q, k, v, scale=self.scale)
+        return self._add_prefix(ops.softmax_attention(q, k, v, scale=self.scale), q)
 
     def step(self, q, k, v, lse=False):
         return self._append_attend(q, k, v, 1, lse)
@@ -471,6 +480,7 @@ class SoftmaxKVDecodeState(_KVCacheState):
                    ops._DT[self.dtype], self.scale),
                   ws=_lib.lib().fastmax_hip_softmax_kv_workspace(B, H, Hkv, T, D, self.max_len))
         self._count += T
+        o = self._add_prefix(o, qd)
         return (o, out_lse) if lse else o
 
 

@@ -29,7 +29,9 @@ class AttentionStack(nn.Module):
     intermediate_size, both residual adds) in place of the bare attention sub-layers.  ``block="neox"``: n_layer whole
     parallel-residual blocks (neox_block.py: the LayerNorm pair, attention, the GELU MLP, the three-way add), what the pythia
     configs are.  ``method="adapter_v2"``: the same blocks without a LoRA branch, every linear an ``AdapterV2Linear`` and the
-    adapter parameters and the norms trainable (finetune/adapter_v2.py), in place of the default ``"lora"``."""
+    adapter parameters and the norms trainable (finetune/adapter_v2.py), in place of the default ``"lora"``.  ``method="adapter"``
+    (``attn_alg="quadratic"`` only): LLaMA-Adapter, every layer adapted (adapter.py) and only the prompts and gates trainable
+    (finetune/adapter.py)."""
 
     def __init__(self, config: str, n_layer: int, attn_alg: str, vocab: int = 32000, r: int = 8, alpha: int = 16,
                  lora_dropout: float = 0.05, block: str = "attention", method: str = "lora"):
@@ -38,10 +40,13 @@ class AttentionStack(nn.Module):
         from .attention_block import CONFIG_SHAPES, CausalSelfAttention
         if block not in ("attention", "full", "neox"):
             raise ValueError(f"block should be 'attention', 'full' or 'neox', got {block!r}")
-        if method not in ("lora", "adapter_v2"):
-            raise ValueError(f"method should be 'lora' or 'adapter_v2', got {method!r}")
+        if method not in ("lora", "adapter_v2", "adapter"):
+            raise ValueError(f"method should be 'lora', 'adapter_v2' or 'adapter', got {method!r}")
+        if method == "adapter" and attn_alg != "quadratic":
+            raise ValueError(f"method 'adapter' (LLaMA-Adapter) lives inside softmax attention: it needs attn_alg='quadratic', "
+                             f"got {attn_alg!r}")
         self.method = method
-        if method == "adapter_v2":
+        if method != "lora":
             r, lora_dropout = 0, 0.0
         shape = CONFIG_SHAPES[config]
         self.n_embd = shape["n_embd"]
@@ -58,6 +63,8 @@ class AttentionStack(nn.Module):
             self.blocks = nn.ModuleList(CausalSelfAttention(attn_alg=attn_alg, r=r, alpha=alpha, dropout=lora_dropout, **shape) for _ in range(n_layer))
         if method == "adapter_v2":
             self._adapt()
+        elif method == "adapter":
+            self._adapt_v1()
         else:
             for b in self.blocks:
                 attn = b if block == "attention" else b.attn
@@ -82,6 +89,20 @@ class AttentionStack(nn.Module):
                 with torch.no_grad():
                     m.adapter_scale.add_(torch.randn(m.adapter_scale.shape, generator=g) * 0.02)
                     m.adapter_bias.add_(torch.randn(m.adapter_bias.shape, generator=g) * 0.02)
+
+    def _adapt_v1(self):
+        """LLaMA-Adapter on every layer: only prompts and gates trainable, as float32 masters, the gates seeded away from the
+        reference's zero so every gradient is exercised"""
+        from .adapter import AdapterCausalSelfAttention, adapt, mark_only_adapter_as_trainable
+        adapt(self.blocks, adapter_start_layer=0)
+        mark_only_adapter_as_trainable(self.blocks)
+        g = torch.Generator().manual_seed(4321)
+        for m in self.blocks.modules():
+            if isinstance(m, AdapterCausalSelfAttention):
+                m.adapter_wte.weight.data, m.gating_factor.data = m.adapter_wte.weight.data.float(), m.gating_factor.data.float()
+                with torch.no_grad():
+                    m.gating_factor.add_((torch.rand(m.gating_factor.shape, generator=g) * 0.75 + 0.25) *
+                                         (torch.randint(0, 2, m.gating_factor.shape, generator=g) * 2 - 1))
 
     def prepare(self, device, quantize: bool = True):
         if quantize:
@@ -129,7 +150,7 @@ def run(config: str, n_layer: int, attn_alg: str, seq: int, micro_batch: int, ac
         lora_dropout: float = 0.05, block: str = "attention", optimizer: str = "torch", method: str = "lora") -> dict:
     """`warmup` untimed + `steps` timed optimizer steps; -> timings (seconds / milliseconds, this rank).
     ``optimizer``: "torch" (torch.optim.AdamW after the bucket's all-reduce-mean) or "flat" (optim.FlatAdamW: the boundary as one
-    pass over the flat bucket).  ``method``: "lora", or "adapter_v2" (``AttentionStack``)."""
+    pass over the flat bucket).  ``method``: "lora", "adapter_v2", or "adapter" with ``attn_alg="quadratic"`` (``AttentionStack``)."""
     if optimizer not in ("torch", "flat"):
         raise ValueError(f"optimizer should be 'torch' or 'flat', got {optimizer!r}")
     on_gpu = device.type == "cuda"

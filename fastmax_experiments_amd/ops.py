@@ -496,3 +496,85 @@ def softmax_attention_with_grad(q, k, v, scale=None):
         raise NotImplementedError(f"softmax_attention_with_grad: head size {q.shape[3]} has no backward pass (multiples of 8 up to "
                                   f"{SOFTMAX_BWD_MAX_HEAD_SIZE}); the forward alone takes up to {MAX_HEAD_SIZE}")
     return SoftmaxAttention.apply(q, k, v, 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale))
+
+
+PREFIX_MAX_ROWS = _lib.PREFIX_MAX_ROWS      # FASTMAX_PREFIX_MAX_ROWS: the adaption prompt is one key tile
+
+
+def _prefix_operands(what, y, q, ak, av, gate, scale, max_d):
+    """checks, then (device, y, q as the kernels take them, ak, av contiguous, gate as H floats, scale)"""
+    if q.dim() != 4 or y.shape != q.shape or ak.dim() != 3 or ak.shape != av.shape or ak.shape[0] < 1 or \
+            q.shape[1] % ak.shape[0] != 0 or ak.shape[2] != q.shape[3] or gate.numel() != q.shape[1]:
+        raise ValueError(f"{what}: expected y, q (B,H,N,D), ak, av (Hkv,aT,D) with Hkv dividing H and gate of H elements, got "
+                         f"{tuple(y.shape)}, {tuple(q.shape)}, {tuple(ak.shape)}, {tuple(av.shape)}, {tuple(gate.shape)}")
+    if not (y.dtype == q.dtype == ak.dtype == av.dtype) or q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what} takes bfloat16 or float16 y, q, ak, av of one dtype, got {y.dtype}, {q.dtype}, {ak.dtype}, {av.dtype}")
+    if not 1 <= ak.shape[1] <= PREFIX_MAX_ROWS:
+        raise ValueError(f"{what}: the prefix should have 1 .. {PREFIX_MAX_ROWS} rows, got {ak.shape[1]}")
+    D = q.shape[3]
+    if D % 8 != 0 or D > max_d:
+        raise NotImplementedError(f"{what}: head size {D} " + ("not supported" if max_d == MAX_HEAD_SIZE else "has no backward pass") +
+                                  f" (multiples of 8 up to {max_d})" +
+                                  ("" if max_d == MAX_HEAD_SIZE else f"; the forward alone takes up to {MAX_HEAD_SIZE}"))
+    dev = q.device if q.is_cuda else _device()
+    g32 = gate.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    return (dev, _prep(y, dev), _prep(q, dev), ak.detach().to(dev).contiguous(), av.detach().to(dev).contiguous(), g32,
+            1.0 / math.sqrt(D) if scale is None else float(scale))
+
+
+def prefix_attention_forward(y, q, ak, av, gate, scale=None, inplace=False):
+    """out = y + gate[h] * softmax(scale q ak^T) av, forward only (csrc/prefix_attention.hip): one launch.  ``inplace`` writes
+    into y where y is contiguous (generation: the rows the decode state just produced)."""
+    dev, yd, qd, akd, avd, g32, sc = _prefix_operands("prefix_attention_add", y, q, ak, av, gate, scale, MAX_HEAD_SIZE)
+    B, H, N, D = q.shape
+    if N == 0:
+        return y
+    out = yd if inplace and yd.is_contiguous() else torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
+    _call("fastmax_hip_prefix_forward", dev, (*_qkv(qd, yd), akd.data_ptr(), avd.data_ptr(), g32.data_ptr(), out.data_ptr(), B, H,
+                                              ak.shape[0], N, D, ak.shape[1], _DT[q.dtype], sc))
+    return out
+
+
+class PrefixAttentionAdd(torch.autograd.Function):
+    """`prefix_attention_forward` with its backward: one tile kernel (dq and the float32 partials of dak, dav, dgate) and the
+    ordered reduce, in one call of fastmax_hip_prefix_backward.  The gradient of y is grad_out itself."""
+
+    @staticmethod
+    def forward(ctx, y, q, ak, av, gate, scale):
+        out = prefix_attention_forward(y, q, ak, av, gate, scale)
+        ctx.save_for_backward(q, ak, av, gate)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, ak, av, gate = ctx.saved_tensors
+        dev, god, qd, akd, avd, g32, sc = _prefix_operands("prefix_attention_add", grad_out, q, ak, av, gate, ctx.scale,
+                                                           PREFIX_BWD_MAX_HEAD_SIZE)          # a transposed grad_out is taken as it is
+        (B, H, N, D), (Hkv, aT, _) = q.shape, ak.shape
+        dq = torch.empty((B, H, N, D), dtype=q.dtype, device=dev)
+        dak, dav = (torch.empty((Hkv, aT, D), dtype=q.dtype, device=dev) for _ in range(2))
+        dgate = torch.empty(H, dtype=torch.float32, device=dev)
+        _call("fastmax_hip_prefix_backward", dev,
+              (*_qkv(qd, god), akd.data_ptr(), avd.data_ptr(), g32.data_ptr(), dq.data_ptr(), dak.data_ptr(), dav.data_ptr(),
+               dgate.data_ptr(), B, H, Hkv, N, D, aT, _DT[q.dtype], sc), ws=_lib.lib().fastmax_hip_prefix_backward_workspace(B, H, N, D))
+        return grad_out, dq, dak, dav, dgate.view(gate.shape).to(gate.dtype), None
+
+
+PREFIX_BWD_MAX_HEAD_SIZE = SOFTMAX_BWD_MAX_HEAD_SIZE      # the backward's accumulators of dq, dak and dav fill the register file
+
+
+def prefix_attention_add(y, q, ak, av, gate, scale=None):
+    """LLaMA-Adapter's gated prefix term behind causal softmax attention (lit_gpt/adapter.py:146-149):
+        out[b,h,i] = y[b,h,i] + gate[h] * sum_{j<aT} softmax_j(scale q[b,h,i] . ak[g,j]) av[g,j],   g = h // (H // Hkv)
+    y (the causal softmax output) and q (B,H,N,D) bf16 or fp16 with any strides; ak, av (Hkv,aT,D) at their KV heads, aT 1 .. 32,
+    no RoPE, no mask; gate of H elements in any shape (the module's (1,1,H,1)) and float dtype; ``scale`` = 1 / sqrt(D) by
+    default.  D: a multiple of 8 up to 256; up to 128 where a gradient is needed.  Gradients of all five tensors (y's is
+    grad_out): float32 sums in one order, no atomics, two calls give the same bits.  gate[h] == 0 gives out == y bit for bit."""
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in (y, q, ak, av, gate))):
+        return prefix_attention_forward(y, q, ak, av, gate, scale)
+    if q.dim() == 4 and q.dtype in (torch.bfloat16, torch.float16) and q.shape[3] % 8 == 0 and \
+            PREFIX_BWD_MAX_HEAD_SIZE < q.shape[3] <= MAX_HEAD_SIZE:
+        raise NotImplementedError(f"prefix_attention_add: head size {q.shape[3]} has no backward pass (multiples of 8 up to "
+                                  f"{PREFIX_BWD_MAX_HEAD_SIZE}); the forward alone takes up to {MAX_HEAD_SIZE}")
+    return PrefixAttentionAdd.apply(y, q, ak, av, gate, None if scale is None else float(scale))
