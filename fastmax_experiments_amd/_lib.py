@@ -55,6 +55,8 @@ HEADERS_EXT = ("fastmax_hip_int8.h",)
 HEADERS_EXT2 = ("fastmax_hip_softmax.h",)
 # tests/test_softmax_cpu.py pins HEADERS_EXT2 and ABI_EXT2 to the softmax header alone: the next pair, on the same terms
 HEADERS_EXT3 = ("fastmax_hip_prefix.h",)
+# tests/test_prefix_cpu.py pins HEADERS_EXT3 and ABI_EXT3 to the prefix header alone: the next pair, on the same terms
+HEADERS_EXT4 = ("fastmax_hip_kv_fp8.h",)
 PREFIX_MAX_ROWS, PREFIX_BWD_CHUNK = 32, 512     # FASTMAX_PREFIX_MAX_ROWS, FASTMAX_PREFIX_BWD_CHUNK
 INT8_FEW_ROWS = 16                              # FASTMAX_INT8_FEW_ROWS
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
@@ -226,6 +228,14 @@ ABI_EXT3 = {
     # q, q_strides, grad_o, go_strides, ak, av, gate, dq, dak, dav, dgate, B, H, Hkv, N, D, aT, dtype, scale
     "fastmax_hip_prefix_backward": (ci, [vp, i64p, vp, i64p, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
 }
+# every function the HEADERS_EXT4 declare; tests/test_kv_fp8_cpu.py checks each row against the prototype
+ABI_EXT4 = {
+    # fastmax_hip_kv_fp8.h: the softmax KV-cache decode on e4m3 rows with a scale per row (csrc/softmax_kv_fp8.hip)
+    "fastmax_hip_kv_fp8_state_bytes": (sz, [ci, ci, ci, ci]),
+    "fastmax_hip_kv_fp8_load": (ci, [vp, i64p, vp, i64p, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "fastmax_hip_kv_fp8_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
+    "fastmax_hip_softmax_kv_fp8_append_attend": (ci, QKV + [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -239,7 +249,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_EXT.items()) + list(ABI_EXT2.items()) + list(ABI_EXT3.items()):
+    for name, (restype, argtypes) in [row for table in (ABI, ABI_EXT, ABI_EXT2, ABI_EXT3, ABI_EXT4) for row in table.items()]:
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

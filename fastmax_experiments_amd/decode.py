@@ -39,7 +39,9 @@ the decode semantics it is a separate class, not a silent replacement of `fastma
 
   softmax  `SoftmaxKVDecodeState` (csrc/softmax_kv_decode.hip): the same cache of K and V rows under causal softmax attention, the
        function of `attn_alg="quadratic"` blocks (the reference's default, which every pretrained checkpoint was trained with);
-       the prompt's own rows come from the tile kernel of csrc/softmax_attention.hip.
+       the prompt's own rows come from the tile kernel of csrc/softmax_attention.hip.  `SoftmaxFP8KVDecodeState`
+       (csrc/softmax_kv_fp8.hip) keeps the rows as e4m3 codes with a power-of-two scale per row: 2 D + 8 bytes per position and KV
+       head instead of 4 D, widened exactly to 16-bit matrix operands in registers.
 """
 import ctypes
 
@@ -324,7 +326,7 @@ class _KVCacheState(_DecodeState):
         if int(max_len) != max_len or max_len < 1 or max_len >= 2 ** 31:
             raise ValueError(f"max_len should be a number of tokens in 1 .. 2^31 - 1, got {max_len}")
         self.dtype, self.max_len = dtype, int(max_len)
-        nbytes = _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[dtype]) if self._head_size_ok(D) else 0
+        nbytes = self._state_bytes(B, Hkv, D) if self._head_size_ok(D) else 0
         if nbytes and torch.device(device).type != "cuda":
             raise RuntimeError(f"the {what} lives on an MI355X (HIP device); there is no CPU path through the kernels")
         _DecodeState.__init__(self, B, H, Hkv, D, nbytes, device,
@@ -334,6 +336,14 @@ class _KVCacheState(_DecodeState):
     @staticmethod
     def _head_size_ok(D):
         return True
+
+    def _state_bytes(self, B, Hkv, D):
+        return _lib.lib().fastmax_hip_kv_decode_state_bytes(B, Hkv, D, self.max_len, ops._DT[self.dtype])
+
+    def _load(self, k, v, T):
+        """rows 0 .. T-1 of the empty cache = k, v; the header's length = T"""
+        ops._call("fastmax_hip_kv_decode_load", self.state.device,
+                  (*ops._qkv(k, v), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
 
     @property
     def header(self):
@@ -370,8 +380,7 @@ class _KVCacheState(_DecodeState):
         qd, kd, vd = self._inputs(q, k, v, T)
         with torch.no_grad():
             o = self._masked(qd, kd, vd)
-        ops._call("fastmax_hip_kv_decode_load", self.state.device,
-                  (*ops._qkv(kd, vd), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
+        self._load(kd, vd, T)
         self._count = T
         return o
 
@@ -440,11 +449,12 @@ class SoftmaxKVDecodeState(_KVCacheState):
     _dtypes = (torch.bfloat16, torch.float16)
     p = None          # not a fastmax cache: check_block_cache tells the classes apart
     prefix = None
+    _what, _sizes = "softmax KV decode cache", f"head sizes 8, 16, .. {_lib.KV_MAX_D}"
+    _append_attend_fn, _workspace_fn = "fastmax_hip_softmax_kv_append_attend", "fastmax_hip_softmax_kv_workspace"
 
     def __init__(self, B, H, D, device, max_len, dtype, n_query_groups=None, scale=None):
         self.scale = 1.0 / D ** 0.5 if scale is None else float(scale)
-        self._init_cache(B, H, D, device, max_len, dtype, n_query_groups, "softmax KV decode cache",
-                         f"head sizes 8, 16, .. {_lib.KV_MAX_D}")
+        self._init_cache(B, H, D, device, max_len, dtype, n_query_groups, self._what, self._sizes)
 
     @staticmethod
     def _head_size_ok(D):
@@ -475,13 +485,48 @@ class SoftmaxKVDecodeState(_KVCacheState):
         qd, kd, vd = (ops._prep(t, dev) for t in self._inputs(q, k, v, T))          # rows as whole 16-byte pieces
         o = torch.empty((B, H, T, D), dtype=self.dtype, device=dev)
         out_lse = torch.empty((B, H, T), dtype=torch.float32, device=dev) if lse else None
-        ops._call("fastmax_hip_softmax_kv_append_attend", dev,
+        ops._call(self._append_attend_fn, dev,
                   (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), ops._ptr(out_lse), B, H, Hkv, T, D, self.max_len,
                    ops._DT[self.dtype], self.scale),
-                  ws=_lib.lib().fastmax_hip_softmax_kv_workspace(B, H, Hkv, T, D, self.max_len))
+                  ws=getattr(_lib.lib(), self._workspace_fn)(B, H, Hkv, T, D, self.max_len))
         self._count += T
         o = self._add_prefix(o, qd)
         return (o, out_lse) if lse else o
+
+
+class SoftmaxFP8KVDecodeState(SoftmaxKVDecodeState):
+    """`SoftmaxKVDecodeState` on 8-bit rows (csrc/softmax_kv_fp8.hip, include/fastmax_hip_kv_fp8.h): every K and V row is kept as D
+    OCP e4m3 codes and one float32 scale 2^e, the smallest power of two with max |row| <= 448 * 2^e, so a cached position costs
+    2 D + 8 bytes per KV head where the 16-bit cache costs 4 D.  ``dtype`` is that of q and o (bf16 or fp16); k and v arrive in it
+    and are quantised as they are appended (and by ``prefill``, whose own rows still come from the unquantised prompt).  Head sizes
+    that are multiples of 16 up to 256.  Everything else is the parent's: ``step`` / ``extend`` / ``lse=`` / the ``count``
+    truncation / ``prefix``, one ``state`` tensor, the bit-level independence of B, T, ``max_len``, strides and replay.  The rows
+    it attends over are the DEQUANTISED ones: what the format costs in accuracy and what it buys in time is in
+    profiles/r31_fp8_kv.md.  Opt-in: nothing selects it."""
+
+    _what, _sizes = "fp8 softmax KV decode cache", f"head sizes 16, 32, .. {_lib.KV_MAX_D}"
+    _append_attend_fn, _workspace_fn = "fastmax_hip_softmax_kv_fp8_append_attend", "fastmax_hip_kv_fp8_workspace"
+
+    @staticmethod
+    def _head_size_ok(D):
+        return D % 16 == 0
+
+    def _state_bytes(self, B, Hkv, D):
+        return _lib.lib().fastmax_hip_kv_fp8_state_bytes(B, Hkv, D, self.max_len)
+
+    def _load(self, k, v, T):
+        k, v = (ops._prep(t, self.state.device) for t in (k, v))          # rows as whole 16-byte pieces
+        ops._call("fastmax_hip_kv_fp8_load", self.state.device,
+                  (*ops._qkv(k, v), self.state.data_ptr(), self.B, self.Hkv, T, self.D, self.max_len, ops._DT[self.dtype]))
+
+    def codes(self):
+        """(k_codes, v_codes, k_scale, v_scale) of the live prefix, views of ``state``: uint8 (B, Hkv, count, D), the e4m3 bit
+        patterns (``.view(torch.float8_e4m3fn)`` reads them), and float32 (B, Hkv, count)"""
+        B, Hkv, D, cap, n = self.B, self.Hkv, self.D, self.capacity, self._count
+        raw, rows = self.state[_lib.KV_HEADER_WORDS:], B * Hkv * cap
+        kc, vc = (raw[i * rows * D // 4:(i + 1) * rows * D // 4].view(torch.uint8).view(B, Hkv, cap, D)[:, :, :n] for i in (0, 1))
+        ks, vs = (raw[2 * rows * D // 4 + i * rows:2 * rows * D // 4 + (i + 1) * rows].view(B, Hkv, cap)[:, :, :n] for i in (0, 1))
+        return kc, vc, ks, vs
 
 
 class LinearmaxDecodeState(_DecodeState):

@@ -12,7 +12,11 @@ forward over the whole prefix (the only route without the cache) and the second-
 `--kv`: one step of the KV-cache decode route (`FastmaxKVDecodeState`) against one p=2 state step, both replayed from a graph and
 alternating in one process, at TinyLlama, Llama-2-7b and Gemma-2b head shapes, bf16, B 1 and 8, lengths 512 .. 32768.
 `--kv-trace ORDER.json` runs the same cells eagerly under `rocprofv3 --kernel-trace --stats`; `--kv-trace-table DIR ORDER.json`
-turns that trace into per-kernel times and bytes/s on the live cache prefix."""
+turns that trace into per-kernel times and bytes/s on the live cache prefix.
+`--fp8-kv`: one graph-replayed step of `SoftmaxFP8KVDecodeState` beside one of `SoftmaxKVDecodeState` (the baseline), alternating in
+one process, at TinyLlama and Llama-2-7b heads, B 1 and 8, 2 k / 16 k / 64 k cached tokens, with the state sizes and the difference
+of o between the two caches; `--fp8-kv-trace ORDER.json` and `--fp8-kv-trace-table DIR ORDER.json` give the attend kernels' own
+times and bytes/s from a `rocprofv3 --kernel-trace --stats` run (profiles/r31_fp8_kv.md)."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -434,10 +438,136 @@ def kv_trace_table(trace_dir, path):
               + " | ".join(f"{us[k]:.1f}" for k in kinds) + f" | {rate:.2f} | {whole:.2f} | {rate / 6.3 * 100:.0f}% |")
 
 
+FP8_SHAPES = (("TinyLlama", 32, 4, 64), ("Llama-2-7b", 32, 32, 128))          # the heads of profiles/r28_softmax.md
+FP8_LENGTHS = (2048, 16384, 65536)
+FP8_LLC = 256 << 20           # the last-level cache: a step's cache must have left it before the step comes round again
+
+
+def _fp8_cells():
+    for name, H, Hkv, D in FP8_SHAPES:
+        for B in (1, 8):
+            for n in FP8_LENGTHS:
+                rows = B * Hkv * (n + 1)
+                live = {"bf16": rows * 4 * D, "fp8": rows * (2 * D + 8)}          # bytes of the live prefix a step reads
+                count = max(2, min(256, -(-FP8_LLC // live["fp8"]) + 1, KV_BUDGET // live["bf16"]))
+                yield name, H, Hkv, D, B, n, live, count
+
+
+def _fp8_arms(H, Hkv, D, B, n, count):
+    """{arm: `count` caches of the arm's class holding the same n random tokens}, and one new token"""
+    from fastmax_experiments_amd.decode import SoftmaxFP8KVDecodeState, SoftmaxKVDecodeState
+    dt = torch.bfloat16
+    k, v = (torch.randn(B, Hkv, n, D, device="cuda").to(dt) for _ in range(2))
+    arms = {}
+    for arm, cls in (("bf16", SoftmaxKVDecodeState), ("fp8", SoftmaxFP8KVDecodeState)):
+        arms[arm] = [cls(B, H, D, "cuda", n + 1, dt, n_query_groups=Hkv) for _ in range(count)]
+        for st in arms[arm]:
+            st._load(k, v, n)
+            st._count = n
+    return arms, tuple(torch.randn(B, h, 1, D, device="cuda").to(dt) for h in (H, Hkv, Hkv))
+
+
+def _fp8_steps(states, tok, n):
+    def run():
+        for st in states:
+            st.step(*tok)
+            st.count = n          # back to the cached length: every replay reads the same prefix
+    return run
+
+
+def bench_fp8_kv(rounds=7):
+    """One graph-replayed step of SoftmaxFP8KVDecodeState beside one of SoftmaxKVDecodeState (the baseline), per layer: a graph of
+    one step (and the truncation back) on each of `states` caches, enough of them to pass the last-level cache between two uses
+    of one; the arms alternate inside each round.  Event times; the attend kernels' own times come from `--fp8-kv-trace`.  The
+    difference columns are o of the fp8 cache against o of the bf16 cache on the same inputs: what the format costs."""
+    print("| heads (H, Hkv, D) | B | cached | states | state MB bf16 / fp8 | bf16 step us: median (min, spread) | fp8 step us: median "
+          "(min, spread) | fp8 / bf16 | live bytes / step time, TB/s bf16 / fp8 | o: max, rms difference |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for name, H, Hkv, D, B, n, live, count in _fp8_cells():
+        with torch.no_grad():
+            arms, tok = _fp8_arms(H, Hkv, D, B, n, count)
+            o = {a: sts[0].step(*tok).float() for a, sts in arms.items()}
+            for sts in arms.values():
+                sts[0].count = n
+            diff = o["fp8"] - o["bf16"]
+            graphs = {a: _graph_of(_fp8_steps(sts, tok, n)) for a, sts in arms.items()}
+            ts = _alternate(graphs, rounds, max(2, min(200, int(4e9 / (live["bf16"] * count)))))
+        us = {a: [x * 1e3 / count for x in t] for a, t in ts.items()}
+        med = {a: statistics.median(u) for a, u in us.items()}
+        cell = {a: f"{med[a]:.1f} ({min(u):.1f}, {(max(u) - min(u)) / med[a] * 100:.0f}%)" for a, u in us.items()}
+        mb = " / ".join(f"{arms[a][0].state.numel() * 4 / 1e6:.1f}" for a in ("bf16", "fp8"))
+        rate = " / ".join(f"{live[a] / med[a] / 1e6:.2f}" for a in ("bf16", "fp8"))
+        print(f"| {name} ({H}, {Hkv}, {D}) | {B} | {n} | {count} | {mb} | {cell['bf16']} | {cell['fp8']} | {med['fp8'] / med['bf16']:.2f} | "
+              f"{rate} | {diff.abs().max().item():.2e}, {diff.pow(2).mean().sqrt().item():.2e} |", flush=True)
+        del arms, graphs
+        torch.cuda.empty_cache()
+
+
+def fp8_kv_trace(path):
+    """for a `rocprofv3 --kernel-trace --stats` run: every cell of `--fp8-kv` in turn, KV_TRACE_STEPS eager steps on each of up
+    to 4 caches of each arm, and the cells' order written to `path` for `--fp8-kv-trace-table`"""
+    import json
+    order = []
+    with torch.no_grad():
+        for name, H, Hkv, D, B, n, live, count in _fp8_cells():
+            arms, tok = _fp8_arms(H, Hkv, D, B, n, min(count, 4))
+            for sts in arms.values():
+                run = _fp8_steps(sts, tok, n)
+                for _ in range(KV_TRACE_STEPS):
+                    run()
+            torch.cuda.synchronize()
+            order.append(dict(name=name, H=H, Hkv=Hkv, D=D, B=B, length=n, live=live, steps=KV_TRACE_STEPS * min(count, 4)))
+            del arms
+            torch.cuda.empty_cache()
+    with open(path, "w") as f:
+        json.dump(order, f)
+    print(f"{len(order)} cells -> {path}")
+
+
+def fp8_kv_trace_table(trace_dir, path):
+    """the kernel trace of a `--fp8-kv-trace` run as one row per cell: microseconds of each arm's attend kernel (mean over the
+    cell's steps, the first left out) and the bytes of the live cache prefix over that time, beside the chip's 6.3 TB/s copy rate"""
+    import csv, glob, json
+    order = json.load(open(path))
+    kinds = {"bf16": "sm_attend_kernel", "fp8": "fp8_attend_kernel"}
+    rows = []
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            arm = next((a for a, k in kinds.items() if k in r["Kernel_Name"]), None)
+            if arm:
+                rows.append((int(r["Start_Timestamp"]), arm, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
+    rows.sort()
+    per = {a: [d for _, arm, d in rows if arm == a] for a in kinds}
+    total = sum(c["steps"] for c in order)
+    for a in kinds:
+        if len(per[a]) != total:
+            raise SystemExit(f"{kinds[a]}: {len(per[a])} dispatches in the trace, the run made {total} steps")
+    print("| heads (H, Hkv, D) | B | cached | attend us bf16 / fp8 | fp8 / bf16 | attend TB/s bf16 / fp8 | of 6.3 TB/s bf16 / fp8 |")
+    print("|---|---|---|---|---|---|---|")
+    at = 0
+    for c in order:
+        sl = slice(at + 1, at + c["steps"])
+        at += c["steps"]
+        us = {a: statistics.mean(per[a][sl]) for a in kinds}
+        rate = {a: c["live"][a] / us[a] / 1e6 for a in kinds}
+        print(f"| {c['name']} ({c['H']}, {c['Hkv']}, {c['D']}) | {c['B']} | {c['length']} | {us['bf16']:.1f} / {us['fp8']:.1f} | "
+              f"{us['fp8'] / us['bf16']:.2f} | {rate['bf16']:.2f} / {rate['fp8']:.2f} | {rate['bf16'] / 6.3 * 100:.0f}% / {rate['fp8'] / 6.3 * 100:.0f}% |")
+
+
 def _case_arg(flag):
     return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
 
 
+if "--fp8-kv-trace-table" in sys.argv:
+    i = sys.argv.index("--fp8-kv-trace-table")
+    fp8_kv_trace_table(sys.argv[i + 1], sys.argv[i + 2])
+    sys.exit(0)
+if "--fp8-kv-trace" in sys.argv:
+    fp8_kv_trace(sys.argv[sys.argv.index("--fp8-kv-trace") + 1])
+    sys.exit(0)
+if "--fp8-kv" in sys.argv:
+    bench_fp8_kv()
+    sys.exit(0)
 if "--kv-trace-table" in sys.argv:
     i = sys.argv.index("--kv-trace-table")
     kv_trace_table(sys.argv[i + 1], sys.argv[i + 2])
