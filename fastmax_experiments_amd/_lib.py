@@ -57,6 +57,8 @@ HEADERS_EXT2 = ("fastmax_hip_softmax.h",)
 HEADERS_EXT3 = ("fastmax_hip_prefix.h",)
 # tests/test_prefix_cpu.py pins HEADERS_EXT3 and ABI_EXT3 to the prefix header alone: the next pair, on the same terms
 HEADERS_EXT4 = ("fastmax_hip_kv_fp8.h",)
+# tests/test_kv_fp8_cpu.py pins HEADERS_EXT4 and ABI_EXT4 to the fp8 header alone: the next pair, on the same terms
+HEADERS_EXT5 = ("fastmax_hip_softmax_block.h",)
 PREFIX_MAX_ROWS, PREFIX_BWD_CHUNK = 32, 512     # FASTMAX_PREFIX_MAX_ROWS, FASTMAX_PREFIX_BWD_CHUNK
 INT8_FEW_ROWS = 16                              # FASTMAX_INT8_FEW_ROWS
 NEOX_ACT_GELU = 0                               # enum fastmax_neox_act (include/fastmax_hip_neox.h)
@@ -67,6 +69,8 @@ MOE_DECODE_MAX_ROWS = 16                        # FASTMAX_MOE_DECODE_MAX_ROWS
 ADAPTER_ROWS_PER_BLOCK = 64                     # FASTMAX_ADAPTER_ROWS_PER_BLOCK
 KV_CHUNK, KV_SLICE, KV_MAX_D = 128, 8, 256      # FASTMAX_KV_CHUNK, FASTMAX_KV_SLICE, FASTMAX_KV_MAX_D
 KV_LEN, KV_OVERFLOW, KV_HEADER_WORDS = 0, 1, 16  # enum fastmax_kv_word
+# FASTMAX_KV_BLOCK_ROWS (_D256: head sizes above 128), FASTMAX_KV_BLOCK_SPAN, FASTMAX_KV_BLOCK_TOKENS
+KV_BLOCK_ROWS, KV_BLOCK_ROWS_D256, KV_BLOCK_SPAN, KV_BLOCK_TOKENS = 64, 16, 4, 64
 # every function the HEADERS declare, in their order and in each header's own order: name -> (restype, argtypes).
 # tests/test_binding_cpu.py checks each row against the prototype.
 ABI = {
@@ -236,6 +240,12 @@ ABI_EXT4 = {
     "fastmax_hip_kv_fp8_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
     "fastmax_hip_softmax_kv_fp8_append_attend": (ci, QKV + [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
 }
+# every function the HEADERS_EXT5 declare; tests/test_softmax_block_cpu.py checks each row against the prototype
+ABI_EXT5 = {
+    # fastmax_hip_softmax_block.h: many new tokens onto the softmax KV cache in one pass over it (csrc/softmax_kv_block.hip)
+    "fastmax_hip_softmax_kv_block_workspace": (sz, [ci, ci, ci, ci, ci, ci]),
+    "fastmax_hip_softmax_kv_append_attend_block": (ci, QKV + [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp, sz, vp]),
+}
 
 _lib = None
 
@@ -249,7 +259,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m fastmax_experiments_amd.build` "
             "(hipcc, --offload-arch=gfx950). The fastmax operator has no fallback path.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in [row for table in (ABI, ABI_EXT, ABI_EXT2, ABI_EXT3, ABI_EXT4) for row in table.items()]:
+    for name, (restype, argtypes) in [row for table in (ABI, ABI_EXT, ABI_EXT2, ABI_EXT3, ABI_EXT4, ABI_EXT5) for row in table.items()]:
         if not hasattr(L, name):
             raise RuntimeError(f"libfastmax_hip.so does not export {name}")
         fn = getattr(L, name)

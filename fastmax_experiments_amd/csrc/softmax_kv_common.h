@@ -1,6 +1,8 @@
-// What the two softmax KV-cache decode routes share (softmax_kv_decode.hip: 16-bit rows; softmax_kv_fp8.hip: e4m3 rows with a scale per
-// row): the 16-bit matrix-core operand of either dtype, the decomposition's constants, the overflow guard and the combine kernel.
-// Both attend kernels leave (m, l, D numerator floats) per query head, new token and chunk in the same workspace layout.
+// What the softmax KV-cache routes share (softmax_kv_decode.hip: 16-bit rows, a token at a time; softmax_kv_block.hip: the same rows,
+// many tokens at once; softmax_kv_fp8.hip: e4m3 rows with a scale per row): the 16-bit matrix-core operand of either dtype, the
+// decomposition's constants, the overflow guard, the 16-bit append kernel and the combine kernel.
+// Every attend kernel leaves (m, l, D numerator floats) per query head, new token and chunk (the block route: span) in the same
+// workspace layout.
 #pragma once
 #include "../../include/fastmax_hip_kv_decode.h"
 #include "fastmax_mfma_common.h"
@@ -42,6 +44,19 @@ __host__ __device__ inline int64_t cap_of(int max_len) { return ((int64_t)max_le
 __device__ __forceinline__ bool overflows(int len, int T, int max_len) { return len < 0 || (int64_t)len + T > (int64_t)max_len; }
 template <int DP> constexpr int v_row() { return 2 * DP + 64; }
 template <int DP> constexpr int attend_lds() { return CHUNK * v_row<DP>(); }
+
+// grid: (T, B * Hkv, 2 = K / V); block: 64.  Rows len .. len + T - 1, unless that passes max_len; the header is only read.
+static __global__ __launch_bounds__(64) void sm_append_kernel(const uint16_t* k, const uint16_t* v, Strides3 ks, Strides3 vs, const int* hdr,
+                                                       uint16_t* kc, uint16_t* vc, int Hkv, int Tn, int D, int max_len, int64_t cap) {
+    const int len = hdr[FASTMAX_KV_LEN];
+    if (overflows(len, Tn, max_len)) return;
+    const int t = blockIdx.x, bg = blockIdx.y, b = bg / Hkv, g = bg % Hkv;
+    const bool isv = blockIdx.z != 0;
+    const Strides3 s = isv ? vs : ks;
+    const uint16_t* src = (isv ? v : k) + (int64_t)b * s.sb + (int64_t)g * s.sh + (int64_t)t * s.sn;
+    uint16_t* dst = (isv ? vc : kc) + ((int64_t)bg * cap + len + t) * D;
+    if ((int)threadIdx.x < D / 8) reinterpret_cast<uint4*>(dst)[threadIdx.x] = reinterpret_cast<const uint4*>(src)[threadIdx.x];
+}
 
 // grid: (B * H, ts); block: 64 .. 256 threads over the columns
 template <typename T>

@@ -31,23 +31,10 @@
 //          header in that launch, and the only write to it in the call.
 // LDS of attend: 128 (2 DP + 64) + 512 bytes: DP = 32: 16,896; 64: 25,088; 128: 41,472; 256: 74,240.  Registers: 40 / 64 / 104 / 184.
 #include "../../include/fastmax_hip_softmax.h"
-#include "softmax_kv_common.h"          // Op, the constants, overflows, sm_combine_kernel, pieces: shared with softmax_kv_fp8.hip
+#include "softmax_kv_common.h"          // Op, the constants, overflows, sm_append_kernel, sm_combine_kernel, pieces: shared
 
 namespace fastmax {
 namespace smkv {
-
-// grid: (T, B * Hkv, 2 = K / V); block: 64.  Rows len .. len + T - 1, unless that passes max_len; the header is only read.
-__global__ __launch_bounds__(64) void sm_append_kernel(const uint16_t* k, const uint16_t* v, Strides3 ks, Strides3 vs, const int* hdr,
-                                                       uint16_t* kc, uint16_t* vc, int Hkv, int Tn, int D, int max_len, int64_t cap) {
-    const int len = hdr[FASTMAX_KV_LEN];
-    if (overflows(len, Tn, max_len)) return;
-    const int t = blockIdx.x, bg = blockIdx.y, b = bg / Hkv, g = bg % Hkv;
-    const bool isv = blockIdx.z != 0;
-    const Strides3 s = isv ? vs : ks;
-    const uint16_t* src = (isv ? v : k) + (int64_t)b * s.sb + (int64_t)g * s.sh + (int64_t)t * s.sn;
-    uint16_t* dst = (isv ? vc : kc) + ((int64_t)bg * cap + len + t) * D;
-    if ((int)threadIdx.x < D / 8) reinterpret_cast<uint4*>(dst)[threadIdx.x] = reinterpret_cast<const uint4*>(src)[threadIdx.x];
-}
 
 // workspace: part (B * H, ts, nchunk, D + 2) floats = (m, l, numerator), then nchunks (B * H, ts) ints
 // grid: (cap / CHUNK, B * Hkv, ts * ceil(qpk / RB)); block: NT; dynamic LDS: attend_lds<32 NS>()

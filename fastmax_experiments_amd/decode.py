@@ -442,6 +442,10 @@ class SoftmaxKVDecodeState(_KVCacheState):
     fp16, head sizes that are multiples of 8 up to 256; forward only.  The prompt's own rows come from `ops.softmax_attention`.
     A row's output bits depend on its q row and the cache prefix alone: not on B, the batch row, T, ``max_len``, the inputs'
     strides or eager / replayed.  ``step`` / ``extend`` take ``lse=True`` for the rows' log-sum-exp (float32, (B,H,T)).
+    ``extend_block`` continues by many tokens in one pass over the cache (a second turn, a prompt in pieces, draft tokens to
+    verify); ``block_extend = True`` sends every ``extend`` of more than one token there, and with it ``extend_qkv``, the
+    attention block's ``state=`` path, ``generate()`` and ``GraphedDecoder``.  Off by default: measured in
+    profiles/r32_softmax_block_extend.md.
     ``prefix = (ak, av, gate)`` (LLaMA-Adapter, adapter.py; set by an adapted layer's ``attend_cached``): the rows that ``step`` /
     ``extend`` / ``prefill`` return get ``ops.prefix_attention_add``'s term from the q they were computed with, one more launch
     in place; lse stays the causal softmax's own."""
@@ -451,6 +455,8 @@ class SoftmaxKVDecodeState(_KVCacheState):
     prefix = None
     _what, _sizes = "softmax KV decode cache", f"head sizes 8, 16, .. {_lib.KV_MAX_D}"
     _append_attend_fn, _workspace_fn = "fastmax_hip_softmax_kv_append_attend", "fastmax_hip_softmax_kv_workspace"
+    _block_fns = ("fastmax_hip_softmax_kv_append_attend_block", "fastmax_hip_softmax_kv_block_workspace")
+    block_extend = False          # True: ``extend`` of more than one token takes ``extend_block`` (other bits; step and T = 1 stay)
 
     def __init__(self, B, H, D, device, max_len, dtype, n_query_groups=None, scale=None):
         self.scale = 1.0 / D ** 0.5 if scale is None else float(scale)
@@ -477,18 +483,28 @@ class SoftmaxKVDecodeState(_KVCacheState):
         return self._append_attend(q, k, v, 1, lse)
 
     def extend(self, q, k, v, lse=False):
-        return self._append_attend(q, k, v, self._tokens(q, "extend"), lse)
+        T = self._tokens(q, "extend")
+        return self._append_attend(q, k, v, T, lse, block=self.block_extend and T > 1)
 
-    def _append_attend(self, q, k, v, T, lse=False):
+    def extend_block(self, q, k, v, lse=False):
+        """``extend`` on the many-tokens-at-once kernel (csrc/softmax_kv_block.hip, include/fastmax_hip_softmax_block.h): the T new
+        tokens share ONE pass over the cache -- `_lib.KV_BLOCK_ROWS` (token, head) rows of a KV group per workgroup, a running
+        maximum along `_lib.KV_BLOCK_SPAN` chunks -- where ``extend`` makes T.  The same shapes, checks, cache rows, ``count``,
+        ``lse`` and ``prefix`` term; a row's bits depend on its q row and the cache prefix alone (not on T, the cut into calls, B,
+        ``max_len``, strides, replay), but they are not ``extend``'s bits: the sums are taken in another order."""
+        return self._append_attend(q, k, v, self._tokens(q, "extend_block"), lse, block=True)
+
+    def _append_attend(self, q, k, v, T, lse=False, block=False):
+        fn, ws_fn = self._block_fns if block else (self._append_attend_fn, self._workspace_fn)
         B, H, Hkv, D = self.B, self.H, self.Hkv, self.D
         dev = self.state.device
         qd, kd, vd = (ops._prep(t, dev) for t in self._inputs(q, k, v, T))          # rows as whole 16-byte pieces
         o = torch.empty((B, H, T, D), dtype=self.dtype, device=dev)
         out_lse = torch.empty((B, H, T), dtype=torch.float32, device=dev) if lse else None
-        ops._call(self._append_attend_fn, dev,
+        ops._call(fn, dev,
                   (*ops._qkv(qd, kd, vd), self.state.data_ptr(), o.data_ptr(), ops._ptr(out_lse), B, H, Hkv, T, D, self.max_len,
                    ops._DT[self.dtype], self.scale),
-                  ws=getattr(_lib.lib(), self._workspace_fn)(B, H, Hkv, T, D, self.max_len))
+                  ws=getattr(_lib.lib(), ws_fn)(B, H, Hkv, T, D, self.max_len))
         self._count += T
         o = self._add_prefix(o, qd)
         return (o, out_lse) if lse else o
@@ -510,6 +526,17 @@ class SoftmaxFP8KVDecodeState(SoftmaxKVDecodeState):
     @staticmethod
     def _head_size_ok(D):
         return D % 16 == 0
+
+    _no_block = "the many-tokens-at-once route (extend_block) reads 16-bit rows: it serves SoftmaxKVDecodeState, not the fp8 cache"
+    block_extend = property(lambda self: False)
+
+    @block_extend.setter
+    def block_extend(self, on):
+        if on:
+            raise NotImplementedError(self._no_block)
+
+    def extend_block(self, q, k, v, lse=False):
+        raise NotImplementedError(self._no_block)
 
     def _state_bytes(self, B, Hkv, D):
         return _lib.lib().fastmax_hip_kv_fp8_state_bytes(B, Hkv, D, self.max_len)

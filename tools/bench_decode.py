@@ -16,7 +16,10 @@ turns that trace into per-kernel times and bytes/s on the live cache prefix.
 `--fp8-kv`: one graph-replayed step of `SoftmaxFP8KVDecodeState` beside one of `SoftmaxKVDecodeState` (the baseline), alternating in
 one process, at TinyLlama and Llama-2-7b heads, B 1 and 8, 2 k / 16 k / 64 k cached tokens, with the state sizes and the difference
 of o between the two caches; `--fp8-kv-trace ORDER.json` and `--fp8-kv-trace-table DIR ORDER.json` give the attend kernels' own
-times and bytes/s from a `rocprofv3 --kernel-trace --stats` run (profiles/r31_fp8_kv.md)."""
+times and bytes/s from a `rocprofv3 --kernel-trace --stats` run (profiles/r31_fp8_kv.md).
+`--block-extend`: `SoftmaxKVDecodeState.extend_block` beside `extend` (the baseline) for T = 4 .. 512 new tokens onto 2 k and 16 k
+cached ones, graph-replayed and alternating in one process, with the cache bytes either route must read
+(profiles/r32_softmax_block_extend.md)."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -553,11 +556,76 @@ def fp8_kv_trace_table(trace_dir, path):
         print(f"| {c['name']} ({c['H']}, {c['Hkv']}, {c['D']}) | {c['B']} | {c['length']} | {us['bf16']:.1f} / {us['fp8']:.1f} | "
               f"{us['fp8'] / us['bf16']:.2f} | {rate['bf16']:.2f} / {rate['fp8']:.2f} | {rate['bf16'] / 6.3 * 100:.0f}% / {rate['fp8'] / 6.3 * 100:.0f}% |")
 
+BLOCK_EXTEND_T = (4, 16, 64, 512)
+BLOCK_EXTEND_CACHED = (2048, 16384)
+
+
+def _block_extend_bytes(B, H, Hkv, D, n, T):
+    """cache bytes a call must read, from the shapes: every pass reads K and V rows of the live prefix (taken as n + (T + 1) / 2
+    positions, the mean over the new tokens) of each (b, KV head); `extend` makes one pass per new token and block of <= 16 query
+    heads, `extend_block` one per tile of KV_BLOCK_ROWS (token, head) rows of a slice of KV_BLOCK_TOKENS tokens"""
+    qpk, rows = H // Hkv, _lib.KV_BLOCK_ROWS if D <= 128 else _lib.KV_BLOCK_ROWS_D256
+    one = B * Hkv * (n + (T + 1) / 2) * 2 * D * 2
+    tiles = sum(-(-min(_lib.KV_BLOCK_TOKENS, T - t0) * qpk // rows) for t0 in range(0, T, _lib.KV_BLOCK_TOKENS))
+    return {"extend": one * T * -(-qpk // 16), "extend_block": one * tiles}
+
+
+def bench_block_extend(rounds=5):
+    """Per call, microseconds: a graph of one call (and the truncation back to the cached length) on each of `states` caches,
+    enough of them to pass the last-level cache between two uses of one where the budget allows; the arms share the caches and
+    alternate inside each round; every shape is warmed up and every window ends in a device synchronise.  The rates are the bytes
+    above over the CALL's time (append, attend and combine launches together), not the attend kernel's own."""
+    from fastmax_experiments_amd.decode import SoftmaxKVDecodeState
+    dt = torch.bfloat16
+    print("| heads (H, Hkv, D) | B | cached | T | states | extend us: median (min, spread) | extend_block us: median (min, spread) | "
+          "block / extend | cache GB to read: extend / block | bytes / call time, TB/s: extend / block | o: max difference |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    for name, H, Hkv, D in FP8_SHAPES:
+        for B in (1, 8):
+            for n in BLOCK_EXTEND_CACHED:
+                k, v = (torch.randn(B, Hkv, n, D, device="cuda").to(dt) for _ in range(2))
+                for T in BLOCK_EXTEND_T:
+                    need = _block_extend_bytes(B, H, Hkv, D, n, T)
+                    cache = B * Hkv * (n + T) * 4 * D
+                    count = max(2, min(32, -(-FP8_LLC // cache) + 1, (8 << 30) // cache))
+                    states = [SoftmaxKVDecodeState(B, H, D, "cuda", n + T, dt, n_query_groups=Hkv) for _ in range(count)]
+                    for st in states:
+                        st._load(k, v, n)
+                        st._count = n
+                    tok = tuple(torch.randn(B, h, T, D, device="cuda").to(dt) for h in (H, Hkv, Hkv))
+
+                    def calls(route):
+                        def run():
+                            for st in states:
+                                getattr(st, route)(*tok)
+                                st.count = n          # back to the cached length: every replay reads the same prefix
+                        return run
+
+                    with torch.no_grad():
+                        o = {}
+                        for r in need:
+                            o[r] = getattr(states[0], r)(*tok).float()
+                            states[0].count = n
+                        graphs = {r: _graph_of(calls(r)) for r in need}
+                        ts = _alternate(graphs, rounds, max(1, min(100, int(1e11 / (need["extend"] * count)))))
+                    us = {r: [x * 1e3 / count for x in t] for r, t in ts.items()}
+                    med = {r: statistics.median(u) for r, u in us.items()}
+                    cell = {r: f"{med[r]:.1f} ({min(u):.1f}, {(max(u) - min(u)) / med[r] * 100:.0f}%)" for r, u in us.items()}
+                    print(f"| {name} ({H}, {Hkv}, {D}) | {B} | {n} | {T} | {count} | {cell['extend']} | {cell['extend_block']} | "
+                          f"{med['extend_block'] / med['extend']:.2f} | {need['extend'] / 1e9:.3f} / {need['extend_block'] / 1e9:.3f} | "
+                          f"{need['extend'] / med['extend'] / 1e6:.2f} / {need['extend_block'] / med['extend_block'] / 1e6:.2f} | "
+                          f"{(o['extend_block'] - o['extend']).abs().max().item():.2e} |", flush=True)
+                    del states, graphs, tok, o
+                    torch.cuda.empty_cache()
+
 
 def _case_arg(flag):
     return tuple(int(x) for x in sys.argv[sys.argv.index(flag) + 1].split(","))
 
 
+if "--block-extend" in sys.argv:
+    bench_block_extend()
+    sys.exit(0)
 if "--fp8-kv-trace-table" in sys.argv:
     i = sys.argv.index("--fp8-kv-trace-table")
     fp8_kv_trace_table(sys.argv[i + 1], sys.argv[i + 2])
